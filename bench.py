@@ -17,6 +17,14 @@ independence, tpe.py:697-746); "weak" gives every rank 2^22 candidates per
 label of its own global index range.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+``--dump-outputs DIR`` also writes what the last timed step returned (the
+per-label winners) as DIR/<name>.npy.  Everything else the benchmark measures
+-- the per-group kernel times (an untimed pass of its own), the fp64 mode, the
+growing-history step, the drop-in and README suggest timings and the CPU
+baseline -- runs only with ``--full``.
 
 With --gpus N > 1 and no torch.distributed environment (WORLD_SIZE unset)
 the script launches itself as N ranks (torch.distributed.run, one process
@@ -458,6 +466,21 @@ def drawn_per_step(eng, space, units):
     return drawn
 
 
+OUTPUT_NAMES = ("index", "value", "score", "n_scored")
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what a level returned to its caller -- per work, in work
+    order, the winner's global candidate index, its value, its score and the
+    number of candidates scored (engine.BatchResult's columns, or the same
+    fields of a LabelResult list) -- as ``path/<name>.npy``, float64 (the
+    integer columns are far below 2^53, so exact)."""
+    os.makedirs(path, exist_ok=True)
+    for name in OUTPUT_NAMES:
+        col = [getattr(r, name) for r in res] if isinstance(res, list) else getattr(res, name)
+        np.save(os.path.join(path, name + ".npy"), np.asarray(col, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -468,9 +491,18 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=("strong", "weak"),
                     help="strong: 2^22 candidates per label in total, split over the ranks by "
                          "dist.plan_units; weak: 2^22 per label per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-group kernel times "
+                         "(group_ms), the fp64 mode, the growing-history step, the drop-in / "
+                         "README suggest timings and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-label winner index, "
+                         "value, score, candidates scored) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the fp64 line and the drop-in / README suggest timings")
+                    help="with --full: skip the fp64 line and the drop-in / README suggest "
+                         "timings")
     ap.add_argument("--upload-history", action="store_true",
                     help="pack and upload the observation lists every step instead of gathering "
                          "them from the HBM-resident history")
@@ -620,6 +652,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # dominant kernel: unquantized continuous scoring of this rank's continuous labels
     if not isinstance(works, list):
@@ -645,12 +679,6 @@ def main():
         ops = exec_pairs * FLOPS_PER_PAIR
         work = {"flops_per_pair": FLOPS_PER_PAIR, "evaluated_pairs_per_launch": exec_pairs}
     builder_tflops = ops / sec / 1e12 if sec > 0 else float("nan")
-    all_timers = {}
-    for k in range(3):
-        step(args.warmup + args.steps + k, all_timers)
-    torch.cuda.synchronize()
-    group_ms = {k: round(float(np.mean([a.elapsed_time(b) for a, b in v])), 4)
-                for k, v in all_timers.items()}
 
     per_rank = sum(c for _, _, c in units)
     total_cand = (len(space) * n_cand if strong else per_rank * world) * args.steps
@@ -663,6 +691,14 @@ def main():
         t = torch.tensor([float(drawn)], dtype=torch.float64, device="cuda")
         dist.all_reduce(t)
         drawn = int(t.item())
+    group_ms = None
+    if args.full:  # every kernel group timed with HIP events, in an untimed pass of its own
+        all_timers = {}
+        for k in range(3):
+            step(args.warmup + args.steps + k, all_timers)
+        torch.cuda.synchronize()
+        group_ms = {k: round(float(np.mean([a.elapsed_time(b) for a, b in v])), 4)
+                    for k, v in all_timers.items()}
     # the headline counts candidates actually drawn and scored (VERDICT r03
     # weak #2); the decided count (every label's full 2^22-candidate argmax,
     # settled from a prefix for the quantized / categorical labels) is reported
@@ -707,8 +743,8 @@ def main():
                          "frac": builder_tflops / FP32_PEAK_TFLOPS})
     if group == "table":
         roofline["l2_gather_bytes_per_launch"] = 16 * n_cont  # one 16-B score cubic per candidate
-        roofline["build_ms"] = group_ms.get("table_build")
-        roofline["band_rescore_ms"] = group_ms.get("band")
+        roofline["build_ms"] = group_ms.get("table_build") if group_ms else None
+        roofline["band_rescore_ms"] = group_ms.get("band") if group_ms else None
     line = {
         "metric": "EI candidates scored/sec (50-dim, 10k trials)",
         "value": value,
@@ -741,7 +777,7 @@ def main():
         "group_ms": group_ms,
         "launch": dict(eng.graph_stats),
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         if args.precision == 32:  # the fp64 parity mode's throughput on the same workload
             step(0, precision=64)
             torch.cuda.synchronize()
@@ -760,7 +796,7 @@ def main():
         line["dropin_suggest_foreign"] = dropin_suggest_p50(space, vals, losses, n_cand,
                                                             foreign=True)
         line["readme_suggest"] = readme_suggest_p50()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(space, vals, losses)
     elif rank == 0:
         line["cpu_baseline"] = None

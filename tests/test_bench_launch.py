@@ -47,3 +47,25 @@ def test_bad_gpu_count():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "0"],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--gpus" in r.stderr
+
+
+def test_dump_outputs_writes_the_level_result(tmp_path):
+    """--dump-outputs: one float64 .npy per column of what a level returned,
+    from a BatchResult or from a LabelResult list, values unchanged."""
+    import numpy as np
+    from hyperopt_amd.engine import BatchResult, LabelResult
+    index = np.array([3, (1 << 22) - 1, -1], np.int64)
+    value = np.array([0.5, -2.25, 7.0])
+    score = np.array([1.5, 0.125, -np.inf])
+    n_scored = np.array([1 << 22, 1 << 16, 0], np.int64)
+    cols = dict(index=index, value=value, score=score, n_scored=n_scored)
+    as_list = [LabelResult("l%d" % i, int(index[i]), float(value[i]), float(score[i]),
+                           int(n_scored[i])) for i in range(3)]
+    for sub, res in (("batch", BatchResult(index, value, score, n_scored)), ("list", as_list)):
+        out = tmp_path / sub / "nested"  # the directory is created
+        bench.dump_outputs(str(out), res)
+        assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in bench.OUTPUT_NAMES)
+        for name in bench.OUTPUT_NAMES:
+            got = np.load(out / (name + ".npy"))
+            assert got.dtype == np.float64 and got.shape == (3,)
+            np.testing.assert_array_equal(got, cols[name].astype(np.float64))

@@ -5,7 +5,7 @@
 # at the first failure.
 set -e
 tag=$1; shift
-args=${*:---steps 3 --warmup 1 --no-cpu-baseline}
+args=${*:---full --steps 3 --warmup 1 --no-cpu-baseline}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$tag
 mkdir -p $out

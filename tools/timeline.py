@@ -7,7 +7,7 @@ level's first kernel, duration, queue and the idle gap before it on the GPU
 
 (no first kernel: levels are split at GPU idle gaps of more than 40 us)
 
-The last level of a bench.py trace is its untimed all-groups timer pass
+The last level of a `bench.py --full` trace is its untimed all-groups timer pass
 (HIP events around every kernel group, ~10 us each on the stream): look at
 the levels before it for the timed steps' timeline.
 """

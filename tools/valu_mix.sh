@@ -6,7 +6,7 @@
 #     tools/valu_mix.sh <tag> [bench args...]
 set -e
 tag=$1; shift
-args=${*:---steps 3 --warmup 1 --no-cpu-baseline --no-extras}
+args=${*:---full --steps 3 --warmup 1 --no-cpu-baseline --no-extras}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/mix_$tag
 mkdir -p $out
