@@ -56,6 +56,11 @@ BAND_DTYPE = np.dtype([("index", "<i8"), ("y", "<f4"), ("hi", "<f4")], align=Tru
 COLSPEC_DTYPE = np.dtype([("col", "<i4"), ("transform", "<i4"), ("floor", "<f8")], align=True)
 PRIOR_DTYPE = np.dtype([("kind", "<i4"), ("n_cat", "<i4"), ("a", "<f8"), ("b", "<f8"),
                         ("q", "<f8"), ("p_off", "<i8"), ("key", "<u8")], align=True)
+ANNEAL_DTYPE = np.dtype([("kind", "<i4"), ("n_cat", "<i4"), ("a", "<f8"), ("b", "<f8"),
+                         ("q", "<f8"), ("p_off", "<i8"), ("key", "<u8"), ("col", "<i4"),
+                         ("n_active", "<i4"), ("shrink", "<f8")], align=True)
+ANNEAL_DBG_DTYPE = np.dtype([("row", "<i4"), ("reused", "<i4"), ("g", "<i4"), ("pad_", "<i4"),
+                             ("p0", "<f8"), ("p1", "<f8"), ("variate", "<f8")], align=True)
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
 # tpe_run_ops record codes (tpe_hip.h TPE_OP_*): entry point -> code
@@ -137,6 +142,9 @@ _SIGNATURES = {
     "tpe_maxloc_allreduce": (_I, [_P, _P, _P, _I, _P, _P]),
     "tpe_best_scatter": (_I, [_P, _P, _I, _P, _I, _P]),
     "tpe_prior_sample": (_I, [_P, _P, _I, _P, _I64, _I64, _P, _P]),
+    "tpe_anneal_sample": (_I, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I, _P, _P, _P, _I64, _P,
+                               _I64, ctypes.c_double, _P, _P, _I, _P, _P, _P, _P]),
+    "tpe_anneal_struct_sizes": (_I, [_P, _I]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),
@@ -217,6 +225,10 @@ def load():
                           % (lib.tpe_abi_version(), ABI_VERSION))
     if tuple(sizes) != want:
         raise ImportError("hyperopt_amd: ABI struct size mismatch %s vs %s" % (tuple(sizes), want))
+    asz = (ctypes.c_int32 * 2)()
+    lib.tpe_anneal_struct_sizes(ctypes.cast(asz, _P), 2)
+    if tuple(asz) != (ANNEAL_DTYPE.itemsize, ANNEAL_DBG_DTYPE.itemsize):
+        raise ImportError("hyperopt_amd: tpe_anneal struct size mismatch %s" % (tuple(asz),))
     _lib = lib
     return lib
 

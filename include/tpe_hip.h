@@ -585,6 +585,59 @@ typedef struct tpe_prior {
 int tpe_prior_sample(const tpe_prior* priors, const tpe_prior* host_priors, int n_priors,
                      const double* p, int64_t n, int64_t base, double* out, void* stream);
 
+/* ---- annealing (anneal.suggest, hyperopt/anneal.py:100-391) ----------------
+ * One level of the annealing walk for n_trials new trials against one
+ * HBM-resident history (vals / active / ld / n_rows as tpe_gather_obs; loss:
+ * one fp64 per history row, +inf for an unfinished trial, NaN sorts last).
+ * One block per new trial visits its live labels in order (CSR: trial t's
+ * items are item_label[item_off[t] .. item_off[t + 1]), indices into recs;
+ * n_items = item_off[n_trials]).  Per label: the first row of the trial's
+ * chain (chain + t * chain_ld, chain_n[t] rows; rows chosen at earlier labels
+ * and levels -- the caller zeroes chain_n before the first level) where the
+ * label is active is reused; otherwise g = geometric(1 / avg_best_idx) - 1,
+ * clipped to [0, n_active - 1], picks the row of rank g among the column's
+ * active rows in np.argsort(loss, kind="stable") order (ascending, NaN after
+ * +inf, ties to the earlier row) by a radix select over the loss bits -- no
+ * sort -- and that row joins the chain.  The value is then drawn from the
+ * label's prior concentrated around the row's value by `shrink` (uniform
+ * kinds: half-width 0.5 (b - a) shrink around the clipped value; normal
+ * kinds: sigma b shrink; randint / categorical: (1 - shrink) onehot + shrink
+ * prior).  A record with n_active == 0 draws from its prior as
+ * tpe_prior_sample does.  Philox4x32-10 keyed by (key, new_ids[t]); the pick
+ * and the value use separate counters.
+ * out: one fp64 per item (randint: the value itself, low included).
+ * dbg (nullable): one record per item.  err: bit 4 is set when the kernel
+ * counts another number of active rows than rec.n_active (the pick is then
+ * clipped to the rows found), bit 8 on an item list or chain out of range. */
+typedef struct tpe_anneal {
+  int32_t kind;         /* TPE_PRIOR_*                                       */
+  int32_t n_cat;        /* categorical: number of categories                 */
+  double a, b, q;       /* as tpe_prior                                      */
+  int64_t p_off;        /* categorical: first prior probability in `p`       */
+  uint64_t key;         /* Philox key (seed mixed with the label)            */
+  int32_t col;          /* history column                                    */
+  int32_t n_active;     /* host's count of the column's active rows          */
+  double shrink;        /* 1 / (1 + n_active * shrink_coef)                  */
+} tpe_anneal;
+typedef struct tpe_anneal_dbg {
+  int32_t row;          /* chosen history row (-1: prior draw)               */
+  int32_t reused;       /* 1: taken from the chain, 0: a new pick            */
+  int32_t g;            /* rank of a new pick after the clip (-1 otherwise)  */
+  int32_t pad_;
+  double p0, p1;        /* (mid, half) | (mu, sigma) | (onehot index, shrink);
+                           a prior draw: (a, b)                              */
+  double variate;       /* the value draw's u in [0, 1) or standard normal z */
+} tpe_anneal_dbg;
+int tpe_anneal_sample(const double* vals, const uint8_t* active, int64_t ld, int64_t n_cols,
+                      int64_t n_rows, const double* loss, const tpe_anneal* recs,
+                      const tpe_anneal* host_recs, int n_recs, const double* p,
+                      const int32_t* item_off, const int32_t* item_label, int64_t n_items,
+                      const int64_t* new_ids, int64_t n_trials, double avg_best_idx,
+                      int32_t* chain, int32_t* chain_n, int chain_ld, double* out,
+                      tpe_anneal_dbg* dbg, int32_t* err, void* stream);
+/* host: writes sizeof(tpe_anneal, tpe_anneal_dbg) to out[0..n); returns 2 */
+int tpe_anneal_struct_sizes(int32_t* out, int n);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
