@@ -27,7 +27,7 @@ import functools
 import math
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional
 
 import numpy as np
@@ -246,6 +246,9 @@ class DeviceHistory:
         self.n_active = np.zeros(self.n_labels, np.int64)
         self._stage = self._stage_ev = None  # pinned staging of appended rows, its upload event
         self._dstage = None  # its device copy (tpe_history_append's input)
+        self._ordered = None          # (rows, columns, specs) the sorted orders are current for
+        self._order_specs_for = None  # (signature, specs, columns) of the last full pass
+        self._spec_dev = {}           # column specs on the device, by spec list
         self._grow(max(int(cap), 16))
 
     @property
@@ -332,15 +335,15 @@ class DeviceHistory:
         sig = (np.asarray(cols).tobytes(), np.asarray(transforms).tobytes(),
                np.asarray(floors, np.float64).tobytes())
         key = (self.rows,) + sig
-        if self.__dict__.get("_ordered") == key:
+        if self._ordered == key:
             return  # (the same columns and transforms, nothing appended since)
         # (merging right after each append instead, on the GPU while the host
         # plans the level: same-box A/B 1.050 vs 1.036 ms per drop-in suggest)
-        last = self.__dict__.get("_ordered")
+        last = self._ordered
         # (sig, specs, columns) of the last slow pass.  When the last pass had
         # this signature no other column set has been ordered since, so the
         # columns still carry these specs (each pass sets _ordered to its key)
-        cached = self.__dict__.get("_order_specs_for")
+        cached = self._order_specs_for
         orows = self.order_rows
         if last is not None and last[1:] == sig and cached is not None and cached[0] == sig \
                 and all(orows.get(c) == last[0] for c in cached[2]):
@@ -366,7 +369,7 @@ class DeviceHistory:
             return
         lib = eng.lib
         sp = ctypes.c_void_p(stream.cuda_stream)
-        cache = self.__dict__.setdefault("_spec_dev", {})
+        cache = self._spec_dev
         for n_old, specs in todo.items():
             hit = cache.get(tuple(specs))
             if hit is None:  # the column specs on the device (kept: the same every append)
@@ -393,29 +396,164 @@ class DeviceHistory:
         self._ordered = key
 
 
-_LAUNCH_STATE = frozenset(('BS', 'JS', '_hmark', 'band_jobs', 'base', 'cat', 'cnt_off', 'cobs_off', 'csegs', 'd_best', 'd_c32', 'd_c32n', 'd_c64', 'd_ccdf', 'd_cdf', 'd_csegs', 'd_err', 'd_fs', 'd_logp', 'd_mu', 'd_pairs', 'd_pm', 'd_segs', 'd_sig', 'd_sm', 'd_stats', 'd_w', 'd_w32', 'exchange', 'fb_jobs', 'fit_ids', 'g_arr', 'groups', 'h_arr', 'hist_mode', 'histories', 'history', 'inj', 'jobs', 'lat_off', 'lat_ready', 'max_obs', 'n_comp', 'n_jobs', 'n_obs_total', 'n_rows', 'nfs', 'o_cand', 'o_cobs', 'o_fb', 'o_g', 'o_h', 'o_isb', 'o_jobs', 'o_lcnt', 'o_obs', 'o_p', 'o_rows', 'o_slot', 'o_xslot', 'out_off', 'outputs', 'p_pool', 'posteriors', 'precision', 'qfb_off', 'sample_only', 'segs', 'sort_off', 'sorted_fit', 'sp', 'stream', 'table_scores', 'torch', 'works', 'x_comm', 'x_labels', 'x_world'))
+# The result block of a level: zeroed by the upload, written by the kernels and
+# read back with one copy (Engine._decode_results).  Byte offsets:
+RES_ERR = 0      # [0,16)  error bits (_raise_errors)
+RES_STATS = 16   # [16,40) table stats: exact candidates, failed cells, failed score cells
+RES_PAIRS = 40   # [40,48) sorted path: (candidate, component) pairs evaluated
+RES_BEST = 64    # [64,..) one tpe_best per job in launch order, then the exchange's label records
 
 
-class _LevelState:
-    """A prepared level's plan, workspace pointers and pack offsets (the locals
-    of Engine.run that its launches read; Engine._launch_level)."""
+# the fields of a recorded plan that later levels of its structure share as they are
+_PLAN_STATIC = ("cont", "quant", "cat", "fit_ids", "params", "nf", "cat_meta", "lat_ranges",
+                "fallback", "modes", "groups", "order", "fb_slice", "out_off", "lat_off",
+                "qfb_off", "sort_off", "cnt_off", "tbl_off")
+
+
+def _never(i):  # (_Plan.inj of a plan without injected candidates)
+    return False
+
+
+@dataclass(slots=True)
+class _LevelOpts:
+    """What the caller of Engine.run asked for (its keyword arguments)."""
+    prior_weight: float = 1.0
+    lf: int = DEFAULT_LF
+    precision: int = 32
+    outputs: bool = False
+    stream: object = None
+    timers: Optional[dict] = None
+    sample_only: bool = False
+    pruned: bool = True
+    scorer: Optional[str] = None
+    posteriors: bool = False
+    history: object = None
+    rows: object = None
+    is_below: object = None
+    histories: Optional[list] = None
+    timer_groups: object = None
+    table_scores: bool = False
+    defer: bool = False
+    exchange: Optional[tuple] = None
+
+    @property
+    def hist_mode(self):
+        return self.history is not None or self.histories is not None
+
+    @property
+    def hooks(self):  # per-candidate outputs / test hooks: such a level is never recorded
+        return self.outputs or self.sample_only or self.posteriors or self.table_scores
+
+    def timer_spec(self):
+        return "off" if self.timers is None else \
+            ("all" if self.timer_groups is None else frozenset(self.timer_groups))
+
+
+class _Record(object):
+    """A record with declared fields (``__slots__``): given by keyword, None
+    otherwise; reading or writing a name that is not declared raises."""
+    __slots__ = ()
 
     def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-    def __getattr__(self, name):  # (pointers of paths the level does not take)
-        if name in _LAUNCH_STATE:
-            return None
-        raise AttributeError(name)
+        for k in self.__slots__:
+            setattr(self, k, kw.pop(k, None))
+        if kw:
+            raise AttributeError("%s has no field %s" % (type(self).__name__, sorted(kw)))
 
 
-class _LaunchState:
-    """Launch-time state of one level shared by its stages (Engine._launch_level:
-    the library or recording _OpList, the streams, the output buffers, the side
-    stream's fork / join flags), and of one group's launch (its job slice)."""
+class _Plan(_Record):
+    """A level's plan: kernel groups, fit / categorical segments, the gather
+    table of a history level and the job table, ordered so every kernel call
+    takes a contiguous slice (Engine._plan_new builds it from the works;
+    _plan_fast + _jobs_fast refill a recorded one's per-call columns)."""
+    __slots__ = (
+        "works",   # the LabelWork list (a recorded plan's WorkBatch: the batch itself)
+        "pkey", "cached",  # key of the recorded plan (None: not replayable); refilled from it
+        "cont", "quant", "cat",  # work indices: unquantized continuous, quantized, categorical
+        "fit_ids", "params", "nf",  # cont + quant (two fit segments each), their posterior_params
+        "segs", "obs_pool",    # SEG_DTYPE per fit segment; upload mode: their observations
+        "n_obs_total", "n_comp", "max_obs",  # observations, mixture components, largest segment
+        "csegs", "cobs_pool", "cobs_off",  # CAT_SEG_DTYPE per categorical segment; observations
+        "p_pool", "cat_meta",  # the segments' probability pools; (categories, offset) per work
+        "lat_ranges", "fallback",  # quantized works: (kmin, slots) on a lattice / dense fallback
+        "modes", "groups", "order",  # scorer per cont work; (kind, works) per group; work per job
+        "g_arr",   # GATHER_DTYPE: the fit segments' lists, then the categorical ones
+        "inj",     # inj(i): work i brings its own candidates
+        "jobs", "cand_pool",   # JOB_DTYPE per job; the injected candidates
+        "fb_jobs", "fb_slice",  # the fallback group's jobs, drawing into the scratch candidates
+        # totals: candidates (per-candidate outputs), lattice slots, fallback draws, sorted
+        # path slots and bucket counters, table cells
+        "out_off", "lat_off", "qfb_off", "sort_off", "cnt_off", "tbl_off")
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+
+class _LevelState(_Record):
+    """A prepared level: its plan and (normalised) options, the staged pack's
+    offsets and the workspace pointers its launches read (Engine._launch_level).
+    Offsets and pointers of paths the level does not take stay None."""
+    __slots__ = (
+        "plan", "opts", "batch",  # (batch: the WorkBatch the caller gave, if any)
+        "stream", "sp",        # the level's torch stream and its handle
+        "hist_mode", "n_rows",  # (n_rows: split flags uploaded, single-history levels)
+        "nfs", "n_jobs", "tjobs",  # fit segments, jobs, the largest table / pruned64 group
+        "sorted_fit",  # the fit from the history's sorted orders (tpe_fit_sorted)
+        "lat_ready",   # lattice slots initialised by the upload
+        "native_ok",   # the level may be recorded (tpe_run_ops)
+        "pack",        # the staged _Pack
+        "nbytes", "xbytes",  # the result block read back at the end; its exchange records' share
+        "h_arr",       # HISTORY_DTYPE per history (histories=)
+        "band_jobs",   # (first, end) jobs scored by tpe_score_table_fast
+        # exchange=: communicator, label slots, ranks, slot per work
+        "x_comm", "x_labels", "x_world", "x_slots",
+        # offsets into the staged pack
+        "o_segs", "o_csegs", "o_p", "o_g", "o_h", "o_obs", "o_cobs", "o_slot", "o_lcnt",
+        "o_jobs", "o_fb", "o_cand", "o_xslot", "o_res", "o_isb", "o_rows",
+        # device pointers: the staged pack, its tables and its result block ...
+        "base", "d_segs", "d_csegs", "d_res", "d_err", "d_stats", "d_pairs", "d_best",
+        # ... and the workspace: mixtures, coefficients, fit scratch, categorical posteriors
+        # (reach windows and wide-component indices of the pruned scorers)
+        "d_w", "d_mu", "d_sig", "d_cdf", "d_c64", "d_c32", "d_fs", "d_c32n", "d_w32", "d_pm",
+        "d_sm", "d_rh", "d_rl", "d_wide", "d_logp", "d_ccdf")
+
+    def sizes(self):
+        """This call's size words of the level's records (_V arguments)."""
+        plan = self.plan
+        return dict(n_rows=self.n_rows, max_obs=plan.max_obs, n_obs_total=plan.n_obs_total,
+                    max_comp=plan.max_obs + 1, pack_size=self.pack.size)
+
+
+class _LaunchState(_Record):
+    """Launch-time state of one level shared by its stages (Engine._launch_level)."""
+    __slots__ = (
+        "lib", "ctx",          # the library or the recording _OpList; the _LaunchCtx
+        "side", "side_p",      # the side stream (None: one stream) and its handle
+        "gather_side",  # the gather runs on the side stream
+        "cat_hist",     # categorical posteriors counted in the history itself
+        "cat_early",    # categorical work starts at the gather, beside the fit
+        "lat_main",     # quantized groups on the main stream
+        "joined", "side_started", "cat_started",  # the side stream's join / fork flags
+        "table_calls", "jobs_ptr",  # jobs per table call; host address of the job table
+        "d_obs", "d_cobs", "d_cand",  # gathered / uploaded observations, injected candidates
+        # per-candidate outputs (below / above log-densities, candidates) and the
+        # table_scores hook's (fp32 scores, their bounds)
+        "d_bl", "d_al", "d_x", "d_sc", "d_eps")
+
+
+class _GroupSlice(_Record):
+    """One group's launch: its slice [a, b) of the job table on the host
+    (``hj``, address ``hjp``) and the device (``dj``), its tpe_best records
+    (``db``), its stream ``ks`` and partials buffer, the stage asked for."""
+    __slots__ = ("kind", "ids", "a", "b", "nj", "hj", "hjp", "dj", "db", "ks", "pname", "stage",
+                 "e0")
+
+
+class _Readback(_Record):
+    """What decoding a level's result block needs (Engine._decode_results)."""
+    __slots__ = (
+        "pin", "nbytes",   # the pinned copy of the block and its size
+        "n_jobs", "jobs",  # (the band fix re-scores from the job table)
+        "table", "pairs",  # the block holds table stats; report the sorted path's pair count
+        "xbytes", "xinfo",  # exchanged label records after the jobs'; Engine._exchange_fix's input
+        "after", "fix")    # reads the records' timer events; Engine._band_fix of this level
 
 
 class _LaunchCtx:
@@ -473,6 +611,16 @@ class Engine:
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
+        self._hip = L.hip()
+        self._init_host_state()
+        rc = self.lib.tpe_set_issue_threads(self.issue_threads)
+        L.check(min(rc, 0), "tpe_set_issue_threads")
+
+    def _init_host_state(self):
+        """Every attribute that needs no device: caches, switches, counters and
+        the last_* diagnostics, each with its initial value.  (Stand-in engines
+        -- tools/host_cpu_profile.make_engine -- call this and add ``torch``,
+        ``lib``, ``device`` and ``_hip`` themselves.)"""
         self._bufs = {}
         self._plans = {}  # level structure -> static descriptor arrays (_plan_record)
         self._retired = []
@@ -480,7 +628,6 @@ class Engine:
         self._res_pin = None   # pinned result block of a level's readback
         self._inflight = None  # a deferred (WorkBatch) run's _Pending until collected
         self._events = {}      # reusable HIP events (no timing) by name
-        self._hip = L.hip()
         self.host_marks = None  # set to a list to record host-side phase times (diagnostic)
         # categorical posteriors and quantized / categorical scoring run on a
         # second stream, concurrently with the continuous fit and the
@@ -550,50 +697,51 @@ class Engine:
         # main chain no longer waits while the host issues the side group
         # (tpe_set_issue_threads); TPE_ISSUE_THREADS=1: one thread
         self.issue_threads = int(_knob("TPE_ISSUE_THREADS", "2"))
-        rc = self.lib.tpe_set_issue_threads(self.issue_threads)
-        L.check(min(rc, 0), "tpe_set_issue_threads")
         self._cap_stream = None
         self._oplists = {}      # launch key -> _OpList
         self._oplist_once = None
         self._replays = {}      # signature -> _Replay of a recorded WorkBatch level
         self._staged_sig = None  # pack signature of what the pinned staging buffer holds
+        self._staged = None      # (dst, src, bytes) of the staged pack's pending upload
+        self._presized = None    # (_gen, sizes) the size-dependent buffers were last grown for
+        self._ones_arr = None    # cached all-ones words (lattice slots)
+        self._tables_slice = None  # job slice of the last fast table call (table_scores hook)
+        self.band_overflows = 0  # jobs re-scored exactly after a band overflow (_band_fix)
+        self.last_band_overflow = None  # ... of the last such level: (position, family, n)
+        self.exchange_fixes = 0  # owed second exchanges run (_exchange_fix)
+        # diagnostics of the last level: the sorted path's pair count, the table
+        # stats, (segs, csegs, gather table, jobs, plan was cached), the
+        # exchange's combined records
+        self.last_pairs = self.last_table_stats = self.last_plan = self.last_exchange = None
 
     # -- memory --------------------------------------------------------------
-    def _buf(self, name, nbytes):
+    def _buf(self, name, nbytes, zero=False):
+        """Workspace buffer ``name`` of at least ``nbytes``.  ``zero``: zero when
+        (re)allocated (kernels that use it leave it zero again: the band work)."""
         t = self._bufs.get(name)
         nbytes = max(int(nbytes), 16)
         if t is None or t.numel() < nbytes:
             if t is not None:  # may still be in use on the side stream: freed after the run
                 self._retired.append(t)
-            t = self.torch.empty(_align(int(nbytes * 1.25)), dtype=self.torch.uint8,
-                                 device=self.device)
+            new = self.torch.zeros if zero else self.torch.empty
+            t = new(_align(int(nbytes * 1.25)), dtype=self.torch.uint8, device=self.device)
             self._bufs[name] = t
             self._gen += 1  # recorded levels hold the old pointers
         return t.data_ptr()
 
-    def _zbuf(self, name, nbytes):
-        """A workspace buffer that is zero when (re)allocated (kernels that use
-        it leave it zero again, e.g. the band controls)."""
-        t = self._bufs.get(name)
-        nbytes = max(int(nbytes), 16)
-        if t is None or t.numel() < nbytes:
-            if t is not None:
-                self._retired.append(t)
-            t = self.torch.zeros(_align(int(nbytes * 1.25)), dtype=self.torch.uint8,
-                                 device=self.device)
-            self._bufs[name] = t
-            self._gen += 1
-        return t.data_ptr()
-
-    def _presize(self, n_comp, n_obs_total, max_obs, cobs_off, n_seg, tjobs, n_rows):
+    def _presize(self, plan, tjobs, n_rows):
         """Every workspace buffer whose size follows a level's per-call sizes
         (mixture pools, observation pools, fit / table scratch), grown here,
         before the launch key is formed: a level re-issued from its records
         (which hold the pointers) then finds every buffer large enough, and a
         buffer that had to grow (new pointer, _gen bumped) forces a new
-        recording."""
+        recording.  ``tjobs``: the largest table / pruned64 group; ``n_rows``:
+        history rows read by the sorted fit (0: another fit)."""
+        n_comp, n_obs_total, max_obs, cobs_off = (plan.n_comp, plan.n_obs_total, plan.max_obs,
+                                                  plan.cobs_off)
+        n_seg = len(plan.segs)
         sizes = (n_comp, n_obs_total, max_obs, cobs_off, n_seg, tjobs, n_rows)
-        last = self.__dict__.get("_presized")
+        last = self._presized
         if last is not None and last[0] == self._gen and all(
                 a <= b for a, b in zip(sizes, last[1])) and n_seg == last[1][4] and \
                 tjobs == last[1][5]:
@@ -629,7 +777,7 @@ class Engine:
 
     def _ones(self, n):
         """n all-ones uint64 words (cached)."""
-        a = self.__dict__.get("_ones_arr")
+        a = self._ones_arr
         if a is None or a.size < n:
             a = self._ones_arr = np.full(max(n, 1024), np.uint64(0xFFFFFFFFFFFFFFFF))
         return a[:n]
@@ -691,9 +839,8 @@ class Engine:
     # per call, only on the observation counts and the Philox keys.  The first
     # call of a structure builds them in Python; later calls copy the recorded
     # arrays and fill the per-call columns with a few vectorised operations.
-    def _plan_key(self, works, prior_weight, lf, precision, scorer, outputs, sample_only,
-                  hist_mode, multi):
-        if not hist_mode or outputs or sample_only:
+    def _plan_key(self, works, opts):
+        if not opts.hist_mode or opts.outputs or opts.sample_only:
             return None
         parts = []
         for w in works:
@@ -705,7 +852,8 @@ class Engine:
                 if not P["bounded"]:  # the lattice range follows the below set
                     lat = _lattice_range(w, P)
             parts.append((w.kind, w.args, int(w.n_cand), int(w.n_total), w.col, w.hist, lat))
-        key = (tuple(parts), float(prior_weight), int(lf), int(precision), scorer, multi)
+        key = (tuple(parts), float(opts.prior_weight), int(opts.lf), int(opts.precision),
+               opts.scorer, opts.histories is not None)
         try:
             hash(key)
         except TypeError:  # unhashable prior arguments (e.g. a probability list)
@@ -714,20 +862,18 @@ class Engine:
             self._plans.clear()
         return key
 
-    def _plan_record(self, works, cont, quant, cat, fit_ids, params, segs, csegs, p_pool,
-                     cat_meta, lat_ranges, fallback, modes, groups, order, gathers, jobs,
-                     fb_slice, out_off, lat_off, qfb_off, sort_off, cnt_off, tbl_off):
-        g = np.zeros(len(gathers), L.GATHER_DTYPE)
-        if gathers:
-            (g["col"], g["below"], g["dst_off"], g["offset"], g["count"], g["to_int"],
-             g["hist"]) = (np.array(c) for c in zip(*gathers))
-        return dict(cont=cont, quant=quant, cat=cat, fit_ids=fit_ids, params=params,
-                    fit_idx=np.asarray(fit_ids, np.int64), cat_idx=np.asarray(cat, np.int64),
-                    order_idx=np.asarray(order, np.int64),
-                    segs=segs.copy(), csegs=csegs.copy(), p_pool=p_pool.copy(),
-                    cat_meta=cat_meta, lat_ranges=lat_ranges, fallback=fallback, modes=modes,
-                    groups=groups, order=order, g=g, jobs=jobs.copy(), fb_slice=fb_slice,
-                    counts=(out_off, lat_off, qfb_off, sort_off, cnt_off, tbl_off))
+    def _plan_record(self, plan):
+        """What a later level of the same structure starts from: the plan's
+        per-structure fields as they are (``static``), and copies of the
+        descriptor tables whose per-call columns _plan_fast / _jobs_fast
+        refill, with the index arrays that map works to their rows."""
+        static = {k: getattr(plan, k) for k in _PLAN_STATIC}
+        static.update(p_pool=plan.p_pool.copy(), obs_pool=np.zeros(1), inj=_never,
+                      cobs_pool=np.zeros(1, np.int64), cand_pool=np.zeros(1))
+        return dict(static=static, fit_idx=np.asarray(plan.fit_ids, np.int64),
+                    cat_idx=np.asarray(plan.cat, np.int64),
+                    order_idx=np.asarray(plan.order, np.int64), segs=plan.segs.copy(),
+                    csegs=plan.csegs.copy(), g=plan.g_arr.copy(), jobs=plan.jobs.copy())
 
     def _big64(self, precision, n_above):
         """The per-call input of the scorer choice that a plan records: at fp64,
@@ -748,8 +894,11 @@ class Engine:
                 np.fromiter((w.cand_base for w in works), np.int64, n))
 
     def _plan_fast(self, P, nb, na):
-        fit_ids, cat = P["fit_ids"], P["cat"]
-        nf = len(fit_ids)
+        """A plan from the recorded one ``P`` with this call's observation
+        counts ``nb`` / ``na`` per work: segment, gather and pool sizes.  The
+        job table follows (_jobs_fast)."""
+        plan = _Plan(cached=True, **P["static"])
+        nf, cat = plan.nf, plan.cat
         segs = P["segs"].copy()
         sizes = np.empty(2 * nf, np.int64)
         fi = P["fit_idx"]
@@ -759,9 +908,9 @@ class Engine:
         obs_off = ends - sizes
         segs["obs_off"], segs["n_obs"] = obs_off, sizes
         segs["comp_off"] = np.cumsum(sizes + 1) - (sizes + 1)
-        n_obs_total = int(ends[-1]) if nf else 0
-        n_comp = n_obs_total + 2 * nf
-        max_obs = int(sizes.max()) if nf else 0
+        plan.n_obs_total = int(ends[-1]) if nf else 0
+        plan.n_comp = plan.n_obs_total + 2 * nf
+        plan.max_obs = int(sizes.max()) if nf else 0
         csegs = P["csegs"].copy()
         csizes = np.empty(2 * len(cat), np.int64)
         ci = P["cat_idx"]
@@ -770,39 +919,36 @@ class Engine:
         cends = np.cumsum(csizes)
         coff = cends - csizes
         csegs["obs_off"], csegs["n_obs"] = coff, csizes
-        cobs_off = int(cends[-1]) if cat else 0
+        plan.cobs_off = int(cends[-1]) if cat else 0
         g_arr = P["g"].copy()
         g_arr["dst_off"] = np.concatenate([obs_off, coff])
         g_arr["count"] = np.concatenate([sizes, csizes])
-        return (P["cont"], P["quant"], cat, fit_ids, P["params"], nf, segs, np.zeros(1),
-                n_obs_total, n_comp, max_obs, csegs, np.zeros(1, np.int64), P["p_pool"],
-                P["cat_meta"], cobs_off, P["lat_ranges"], P["fallback"], P["modes"],
-                P["groups"], P["order"], g_arr)
+        plan.segs, plan.csegs, plan.g_arr = segs, csegs, g_arr
+        return plan
 
-    def _jobs_fast(self, P, keys, cand_base):
+    def _jobs_fast(self, P, plan, keys, cand_base):
+        """The recorded job table with this call's Philox keys and candidate bases."""
         oi = P["order_idx"]
         jobs = P["jobs"].copy()
         jobs["key"] = keys[oi]
         jobs["cand_base"] = cand_base[oi]
-        a, b = P["fb_slice"]
+        a, b = plan.fb_slice
         fb_jobs = jobs[a:b].copy()
         fb_jobs["out_off"] = fb_jobs["cand_off"]
-        return (jobs, np.zeros(1), fb_jobs, P["fb_slice"]) + tuple(P["counts"])
+        plan.jobs, plan.fb_jobs = jobs, fb_jobs
 
-    def _choose_plan(self, works, batch, prior_weight, lf, precision, scorer, outputs,
-                     sample_only, hist_mode, multi, _hmark):
-        """A level's plan: replayed from the plan recorded for its structure
+    def _choose_plan(self, works, batch, opts):
+        """A level's plan: refilled from the plan recorded for its structure
         (_plan_fast + _jobs_fast: only the per-call columns -- counts, keys,
         candidate bases -- are filled in) or built from its works (_plan_new,
         which records it when it can be replayed).  A WorkBatch's works are
-        materialised only when its structure is new.  Returns (works, plan
-        key, recorded plan or None, the plan tuple of _plan_new; a replayed
-        plan gives the gather table where _plan_new gives the gather list)."""
+        materialised only when its structure is new."""
         if batch is not None:
-            pkey = ("batch", batch.key, float(prior_weight), int(lf), int(precision), scorer,
-                    multi, self._big64(precision, batch.n_above))
-            cached = self._plans.get(pkey)
-            if cached is None:
+            pkey = ("batch", batch.key, float(opts.prior_weight), int(opts.lf),
+                    int(opts.precision), opts.scorer, opts.histories is not None,
+                    self._big64(opts.precision, batch.n_above))
+            P = self._plans.get(pkey)
+            if P is None:
                 works = batch.materialize()
                 if len(works) != len(batch):
                     raise ValueError("WorkBatch.materialize() gave %d works for %d rows"
@@ -810,42 +956,36 @@ class Engine:
             elif len(self._plans) > 64:
                 self._plans.clear()
         else:
-            pkey = self._plan_key(works, prior_weight, lf, precision, scorer, outputs,
-                                  sample_only, hist_mode, multi)
+            pkey = self._plan_key(works, opts)
             if pkey is not None:
-                pkey += (self._big64(precision, np.fromiter(
+                pkey += (self._big64(opts.precision, np.fromiter(
                     (w.n_above if w.obs_above is None else np.size(w.obs_above) for w in works),
                     np.int64, len(works))),)
-            cached = self._plans.get(pkey) if pkey is not None else None
-        if cached is None:
-            return works, pkey, None, self._plan_new(
-                works, pkey, prior_weight, lf, precision, scorer, outputs, sample_only, hist_mode,
-                _hmark)
+            P = self._plans.get(pkey) if pkey is not None else None
+        if P is None:
+            return self._plan_new(works, pkey, opts)
         cols = (batch.n_below, batch.n_above, batch.keys, batch.cand_base) \
             if batch is not None else self._columns(works)
-        (cont, quant, cat, fit_ids, params, nf, segs, obs_pool, n_obs_total, n_comp, max_obs,
-         csegs, cobs_pool, p_pool, cat_meta, cobs_off, lat_ranges, fallback, modes, groups,
-         order, g_arr) = self._plan_fast(cached, cols[0], cols[1])
-        if batch is not None:
-            inj = lambda i: False  # noqa: E731
-        else:
-            inj = lambda i: works[i].cand is not None  # noqa: E731
-        (jobs, cand_pool, fb_jobs, fb_slice, out_off, lat_off, qfb_off, sort_off, cnt_off,
-         tbl_off) = self._jobs_fast(cached, cols[2], cols[3])
-        return works, pkey, cached, (
-            cont, quant, cat, fit_ids, params, nf, segs, obs_pool, n_obs_total, n_comp, max_obs,
-            csegs, cobs_pool, p_pool, cat_meta, cobs_off, lat_ranges, fallback, modes, groups,
-            order, g_arr, inj, jobs, cand_pool, fb_jobs, fb_slice, out_off, lat_off, qfb_off,
-            sort_off, cnt_off, tbl_off)
+        plan = self._plan_fast(P, cols[0], cols[1])
+        self._jobs_fast(P, plan, cols[2], cols[3])
+        # (a recorded plan has no injected candidates: its inj is _never)
+        plan.works, plan.pkey = works, pkey
+        return plan
 
     # -- main entry ----------------------------------------------------------
-    def _plan_new(self, works, pkey, prior_weight, lf, precision, scorer, outputs, sample_only,
-                  hist_mode, _hmark):
+    def _mark(self, name):
+        hp = self.host_marks  # diagnostic: list of (name, perf_counter) or None
+        if hp is not None:
+            hp.append((name, time.perf_counter()))
+
+    def _plan_new(self, works, pkey, opts):
         """A level's plan built from its works (the path _plan_fast replays
         from a recorded plan): kernel groups, fit / categorical segments, the
-        gather list of a history level, and the job descriptors ordered so
+        gather table of a history level, and the job descriptors ordered so
         every kernel call takes a contiguous slice.  Records the plan under
         ``pkey`` when it can be replayed."""
+        hist_mode, lf, prior_weight = opts.hist_mode, opts.lf, opts.prior_weight
+        plan = _Plan(works=works, pkey=pkey, cached=False, n_obs_total=0, n_comp=0, max_obs=0)
         cont, quant, cat = [], [], []
         for i, w in enumerate(works):
             if w.kind in CONTINUOUS:
@@ -854,16 +994,16 @@ class Engine:
                 cat.append(i)
             else:
                 raise ValueError("unsupported prior %r for label %r" % (w.kind, w.label))
+        plan.cont, plan.quant, plan.cat = cont, quant, cat
 
-        _hmark('prep')
+        self._mark('prep')
         gathers = []  # history mode: (col, below, dst_off, offset, count, to_int, hist)
         # ---- continuous / quantized segments --------------------------------
-        fit_ids = cont + quant
-        params = {i: _params(works[i].kind, works[i].args) for i in fit_ids}
-        nf = len(fit_ids)
-        segs = np.zeros(2 * nf, L.SEG_DTYPE)
-        obs_pool = None
-        n_obs_total = n_comp = max_obs = 0
+        fit_ids = plan.fit_ids = cont + quant
+        params = plan.params = {i: _params(works[i].kind, works[i].args) for i in fit_ids}
+        nf = plan.nf = len(fit_ids)
+        segs = plan.segs = np.zeros(2 * nf, L.SEG_DTYPE)
+        plan.obs_pool = np.zeros(1)
         if nf:
             if hist_mode:
                 sizes = np.empty(2 * nf, np.int64)
@@ -874,7 +1014,7 @@ class Engine:
                 parts = [np.asarray(o, dtype=np.float64).reshape(-1) for i in fit_ids
                          for o in (works[i].obs_below, works[i].obs_above)]
                 sizes = np.fromiter((o.size for o in parts), np.int64, 2 * nf)
-                obs_pool = np.concatenate(parts)
+                plan.obs_pool = np.concatenate(parts)
             ends = np.cumsum(sizes)
             obs_off = ends - sizes
             comp_off = np.cumsum(sizes + 1) - (sizes + 1)
@@ -884,24 +1024,22 @@ class Engine:
             for name in ("transform", "family", "floor", "prior_mu", "prior_sigma", "low", "high"):
                 segs[name] = np.repeat([p[name] for p in pl], 2)
             segs["bounded"] = np.repeat([int(p["bounded"]) for p in pl], 2)
-            n_obs_total = int(ends[-1])
-            n_comp = n_obs_total + 2 * nf
-            max_obs = int(sizes.max())
+            plan.n_obs_total = int(ends[-1])
+            plan.n_comp = plan.n_obs_total + 2 * nf
+            plan.max_obs = int(sizes.max())
             if hist_mode:
                 for si, i in enumerate(fit_ids):
                     for half in (0, 1):
                         k = 2 * si + half
                         gathers.append((works[i].col, 1 - half, int(obs_off[k]), 0, int(sizes[k]),
                                         0, works[i].hist))
-        if obs_pool is None:
-            obs_pool = np.zeros(1)
 
-        _hmark('segs')
+        self._mark('segs')
         # ---- categorical segments ------------------------------------------
-        csegs = np.zeros(2 * len(cat), L.CAT_SEG_DTYPE)
+        csegs = plan.csegs = np.zeros(2 * len(cat), L.CAT_SEG_DTYPE)
         cobs_parts, p_init = [], []
         cobs_off = p_off = 0
-        cat_meta = {}
+        cat_meta = plan.cat_meta = {}
         ccols = []
         for ci, i in enumerate(cat):
             w = works[i]
@@ -930,36 +1068,34 @@ class Engine:
             (csegs["obs_off"], csegs["p_off"], csegs["n_obs"], csegs["n_cat"], csegs["mode"],
              csegs["prior_p_off"]) = cc.T
             csegs["lf"], csegs["prior_weight"] = lf, prior_weight
-        cobs_pool = np.concatenate(cobs_parts) if cobs_parts else np.zeros(1, np.int64)
-        p_pool = np.concatenate(p_init) if p_init else np.zeros(1)
+        plan.cobs_off = cobs_off
+        plan.cobs_pool = np.concatenate(cobs_parts) if cobs_parts else np.zeros(1, np.int64)
+        plan.p_pool = np.concatenate(p_init) if p_init else np.zeros(1)
+        # the gather table: the fit segments' lists, then the categorical ones
+        g = plan.g_arr = np.zeros(len(gathers), L.GATHER_DTYPE)
+        if gathers:
+            (g["col"], g["below"], g["dst_off"], g["offset"], g["count"], g["to_int"],
+             g["hist"]) = (np.array(c) for c in zip(*gathers))
 
-        _hmark('cats')
-        (inj, lat_ranges, fallback, modes, groups, order, jobs, cand_pool, fb_jobs, fb_slice,
-         out_off, lat_off, qfb_off, sort_off, cnt_off, tbl_off) = self._plan_jobs(
-            works, cont, quant, cat, fit_ids, params, cat_meta, precision, scorer, outputs,
-            sample_only)
-        if pkey is not None and not any(k == "sorted" and ids for k, ids in groups):
-            self._plans[pkey] = self._plan_record(
-                works, cont, quant, cat, fit_ids, params, segs, csegs, p_pool, cat_meta,
-                lat_ranges, fallback, modes, groups, order, gathers, jobs, fb_slice, out_off,
-                lat_off, qfb_off, sort_off, cnt_off, tbl_off)
+        self._mark('cats')
+        self._plan_jobs(plan, works, opts)
+        if pkey is not None and not any(k == "sorted" and ids for k, ids in plan.groups):
+            self._plans[pkey] = self._plan_record(plan)
+        return plan
 
-        return (cont, quant, cat, fit_ids, params, nf, segs, obs_pool, n_obs_total, n_comp,
-                max_obs, csegs, cobs_pool, p_pool, cat_meta, cobs_off, lat_ranges, fallback, modes,
-                groups, order, gathers, inj, jobs, cand_pool, fb_jobs, fb_slice, out_off, lat_off,
-                qfb_off, sort_off, cnt_off, tbl_off)
-
-    def _plan_jobs(self, works, cont, quant, cat, fit_ids, params, cat_meta, precision, scorer,
-                   outputs, sample_only):
+    def _plan_jobs(self, plan, works, opts):
         """The job table of a new plan (_plan_new): each label's scorer
         (continuous: table / pruned64 / dense / sorted by precision, size and
         hooks; quantized: lattice or dense fallback; categorical), the kernel
         groups, and one tpe_job per label ordered so every kernel call takes a
         contiguous slice, with its candidate, output, lattice and table offsets."""
+        cont, quant, cat, fit_ids = plan.cont, plan.quant, plan.cat, plan.fit_ids
+        params, cat_meta = plan.params, plan.cat_meta
+        precision, scorer, outputs = opts.precision, opts.scorer, opts.outputs
         # ---- jobs, ordered so every kernel call takes a contiguous slice -----------
-        inj = lambda i: works[i].cand is not None  # noqa: E731
-        lat_ranges = {}
-        fallback = []
+        inj = plan.inj = lambda i: works[i].cand is not None  # noqa: E731
+        lat_ranges = plan.lat_ranges = {}
+        fallback = plan.fallback = []
         for i in quant:
             if not inj(i):
                 kmin, kmax = _lattice_range(works[i], params[i])
@@ -968,7 +1104,7 @@ class Engine:
                 else:
                     lat_ranges[i] = (kmin, kmax - kmin + 1)
         def cont_mode(i):
-            if sample_only:
+            if opts.sample_only:
                 return "cont"
             if precision != 32:
                 w = works[i]
@@ -991,8 +1127,8 @@ class Engine:
             if mode == "sorted" and (inj(i) or outputs):
                 mode = "cont"
             return "cont" if mode == "dense" else mode
-        modes = {i: cont_mode(i) for i in cont}
-        groups = [
+        modes = plan.modes = {i: cont_mode(i) for i in cont}
+        groups = plan.groups = [
             ("cont", [i for i in cont if inj(i) and modes[i] == "cont"]),
             ("cont", [i for i in cont if not inj(i) and modes[i] == "cont"]),
             ("sorted", [i for i in cont if modes[i] == "sorted"]),
@@ -1006,7 +1142,7 @@ class Engine:
             ("cat", [i for i in cat if inj(i)]),
             ("cat", [i for i in cat if not inj(i)]),
         ]
-        order = [i for _, ids in groups for i in ids]
+        order = plan.order = [i for _, ids in groups for i in ids]
         nj_all = len(order)
         jobs = np.zeros(nj_all, L.JOB_DTYPE)
         J = {name: np.zeros(nj_all, L.JOB_DTYPE[name]) for name in L.JOB_DTYPE.names}
@@ -1076,14 +1212,15 @@ class Engine:
             J["flags"] &= ~L.F_LATTICE_READY
         for name, col in J.items():
             jobs[name] = col
-        cand_pool = np.concatenate(cand_parts) if cand_parts else np.zeros(1)
+        plan.jobs = jobs
+        plan.cand_pool = np.concatenate(cand_parts) if cand_parts else np.zeros(1)
         # the dense fallback first materialises its draws: a job copy whose
         # out_off points into the scratch candidate buffer
-        fb_slice = _slice_of(groups, [k for k, _ in groups].index("qfb"))
-        fb_jobs = jobs[fb_slice[0]:fb_slice[1]].copy()
-        fb_jobs["out_off"] = fb_jobs["cand_off"]
-        return (inj, lat_ranges, fallback, modes, groups, order, jobs, cand_pool, fb_jobs,
-                fb_slice, out_off, lat_off, qfb_off, sort_off, cnt_off, tbl_off)
+        a, b = plan.fb_slice = _slice_of(groups, [k for k, _ in groups].index("qfb"))
+        plan.fb_jobs = jobs[a:b].copy()
+        plan.fb_jobs["out_off"] = plan.fb_jobs["cand_off"]
+        plan.out_off, plan.lat_off, plan.qfb_off = out_off, lat_off, qfb_off
+        plan.sort_off, plan.cnt_off, plan.tbl_off = sort_off, cnt_off, tbl_off
 
     def run(self, works: List[LabelWork], prior_weight=1.0, lf=DEFAULT_LF, precision=32,
             outputs=False, stream=None, timers=None, sample_only=False,
@@ -1094,59 +1231,9 @@ class Engine:
         an fp32 argmax -- injected candidates, or per-candidate ``outputs`` --
         get the exact decision afterwards (``_exact_decision``), so every
         default precision-32 winner is np.argmax of the exact scores, as the
-        suggest path's are.  Arguments: see ``_run_level``."""
-        res = self._run_level(works, prior_weight, lf, precision, outputs, stream, timers,
-                              sample_only, pruned, scorer, posteriors, history, rows, is_below,
-                              histories, timer_groups, table_scores, defer, exchange)
-        if precision == 32 and isinstance(works, list) and res and not (
-                sample_only or posteriors or table_scores or exchange is not None) and \
-                (scorer in (None, "auto") and pruned):
-            redo = [i for i, w in enumerate(works) if w.kind in EXACT32_KINDS and
-                    (w.cand is not None or outputs)]
-            if redo:
-                self._exact_decision(works, res, redo, prior_weight, lf, stream, history, rows,
-                                     is_below, histories)
-        return res
+        suggest path's are.
 
-    def _exact_decision(self, works, res, redo, prior_weight, lf, stream, history, rows,
-                        is_below, histories):
-        """The exact argmax of fp32-decided labels: their candidate values
-        (the injected ones, or the drawn ones read back with the outputs)
-        scored again in fp64 (tpe_score_pruned64 / the dense fp64 kernel,
-        index-exact against the oracle), first maximum, NaN winning
-        (np.argmax, tpe.py:649-658).  Patches index / value / score in place;
-        the fp32 per-candidate log-densities stay."""
-        import dataclasses
-        again = []
-        for i in redo:
-            w, r = works[i], res[i]
-            cand = w.cand if w.cand is not None else r.cand
-            if cand is None or np.size(cand) == 0:
-                continue
-            again.append((i, dataclasses.replace(w, cand=np.asarray(cand, np.float64),
-                                                 n_cand=int(np.size(cand)), cand_base=0)))
-        if not again:
-            return
-        kw = dict(history=history, rows=rows, is_below=is_below, histories=histories)
-        keep = tuple(getattr(self, k, None) for k in ("last_pairs", "last_table_stats",
-                                                      "last_plan"))  # the fp32 level's
-        exact = self._run_level([w for _, w in again], prior_weight, lf, 64, False, stream, None,
-                                False, True, None, False, **kw, timer_groups=None,
-                                table_scores=False, defer=False, exchange=None)
-        self.last_pairs, self.last_table_stats, self.last_plan = keep
-        for (i, w), e in zip(again, exact):
-            r = res[i]
-            local = int(e.index)
-            r.index = local if works[i].cand is not None else \
-                (int(works[i].cand_base) + local if local >= 0 else local)
-            r.value, r.score = e.value, e.score
-
-    def _run_level(self, works: List[LabelWork], prior_weight=1.0, lf=DEFAULT_LF, precision=32,
-                   outputs=False, stream=None, timers=None, sample_only=False,
-                   pruned=True, scorer=None, posteriors=False, history=None, rows=None,
-                   is_below=None, histories=None, timer_groups=None,
-                   table_scores=False, defer=False, exchange=None) -> List[LabelResult]:
-        """Run one level.  ``timers`` (optional dict) collects HIP event pairs
+        ``timers`` (optional dict) collects HIP event pairs
         per kernel group ("fit", "cat_fit", "cont", "lat", ...) on ``stream``;
         ``timer_groups`` (optional set) limits them to those groups (each event
         pair costs the stream a ~10 us timestamp barrier).
@@ -1184,137 +1271,200 @@ class Engine:
         address; tpe_maxloc_allreduce), on the level's stream; the combined
         records (BEST_DTYPE, the same on every rank) come back with the level's
         one readback as ``self.last_exchange``."""
+        opts = _LevelOpts(prior_weight, lf, precision, outputs, stream, timers, sample_only,
+                          pruned, scorer, posteriors, history, rows, is_below, histories,
+                          timer_groups, table_scores, defer, exchange)
+        res = self._run_level(works, opts)
+        if precision == 32 and isinstance(works, list) and res and not (
+                sample_only or posteriors or table_scores or exchange is not None) and \
+                (scorer in (None, "auto") and pruned):
+            redo = [i for i, w in enumerate(works) if w.kind in EXACT32_KINDS and
+                    (w.cand is not None or outputs)]
+            if redo:
+                self._exact_decision(works, res, redo, opts)
+        return res
+
+    def _exact_decision(self, works, res, redo, opts):
+        """The exact argmax of fp32-decided labels: their candidate values
+        (the injected ones, or the drawn ones read back with the outputs)
+        scored again in fp64 (tpe_score_pruned64 / the dense fp64 kernel,
+        index-exact against the oracle), first maximum, NaN winning
+        (np.argmax, tpe.py:649-658).  Patches index / value / score in place;
+        the fp32 per-candidate log-densities stay."""
+        again = []
+        for i in redo:
+            w, r = works[i], res[i]
+            cand = w.cand if w.cand is not None else r.cand
+            if cand is None or np.size(cand) == 0:
+                continue
+            again.append((i, replace(w, cand=np.asarray(cand, np.float64),
+                                     n_cand=int(np.size(cand)), cand_base=0)))
+        if not again:
+            return
+        keep = (self.last_pairs, self.last_table_stats, self.last_plan)  # the fp32 level's
+        # the same level in fp64, nothing but the winners asked for (prior
+        # weight, lf, stream and the history arguments stay the caller's)
+        exact = self._run_level([w for _, w in again], replace(
+            opts, precision=64, outputs=False, timers=None, sample_only=False, pruned=True,
+            scorer=None, posteriors=False, timer_groups=None, table_scores=False, defer=False,
+            exchange=None))
+        self.last_pairs, self.last_table_stats, self.last_plan = keep
+        for (i, w), e in zip(again, exact):
+            r = res[i]
+            local = int(e.index)
+            # (known wrong for an injected work with cand_base != 0: the local
+            # index is written -- ADVICE.md; kept as it is here)
+            r.index = local if works[i].cand is not None else \
+                (int(works[i].cand_base) + local if local >= 0 else local)
+            r.value, r.score = e.value, e.score
+
+    def _run_level(self, works, opts):
+        """Run one level, in stages: re-issue a recorded WorkBatch level
+        (_try_replay), or check the options, plan, pack and upload, size the
+        workspace, form the launch key, issue the launches (_issue_level) and
+        read the results back (_finish_level).  Arguments: see ``run``."""
         if not works:
             return []
-        stream_arg = stream
         if self._inflight is not None:  # its pinned buffers are about to be reused
             self._inflight.result()
-        if self._replays and isinstance(works, WorkBatch) and stream is None:
-            sig = _Replay.signature(self, works, prior_weight, lf, precision, outputs,
-                                    self.torch.cuda.current_stream(self.device).cuda_stream,
-                                    sample_only, pruned, scorer, posteriors, history, rows,
-                                    is_below, histories, timers, timer_groups, table_scores,
-                                    exchange)
-            rp = self._replays.get(sig) if sig is not None else None
-            # valid while the workspace is unchanged and the staging buffer
-            # still holds this level's pack (levels that differ only in their
-            # timer events share one)
-            if rp is not None and rp.gen == self._gen and self._staged_sig == rp.sig[:-1]:
-                out = rp.run(self, works, is_below, timers, defer)
-                if out is not None:
-                    return out
-        if sample_only:
+        out = self._try_replay(works, opts)
+        if out is not None:
+            return out
+        opts, batch = self._check_opts(works, opts)
+        self._retired.clear()  # every earlier run ended with a synchronising readback / collect
+        self._mark("start")
+        stream = opts.stream
+        if stream is None:
+            stream = self.torch.cuda.current_stream(self.device)
+        lv = _LevelState(plan=self._choose_plan(works, batch, opts), opts=opts, batch=batch,
+                         stream=stream, sp=ctypes.c_void_p(stream.cuda_stream),
+                         hist_mode=opts.hist_mode, n_rows=0, band_jobs=[])
+        self._mark('plan')
+        self._pack_level(lv)
+        self._workspace(lv)
+        gkey = self._launch_key(lv)
+        ctx = _LaunchCtx(self, stream, opts.timers, opts.timer_groups)
+        ops, table_calls, post = self._issue_level(lv, ctx, gkey, batch is not None)
+        if post:
+            return table_calls
+        self._mark('score launches')
+        return self._finish_level(lv, ops, table_calls, gkey)
+
+    def _try_replay(self, works, opts):
+        """Re-issue the recorded level of a WorkBatch whose signature repeats
+        (_Replay); None: take the full path."""
+        if not (self._replays and isinstance(works, WorkBatch) and opts.stream is None):
+            return None
+        sig = _Replay.signature(self, works, opts,
+                                self.torch.cuda.current_stream(self.device).cuda_stream)
+        rp = self._replays.get(sig) if sig is not None else None
+        # valid while the workspace is unchanged and the staging buffer
+        # still holds this level's pack (levels that differ only in their
+        # timer events share one)
+        if rp is not None and rp.gen == self._gen and self._staged_sig == rp.sig[:-1]:
+            return rp.run(self, works, opts)
+        return None
+
+    def _check_opts(self, works, opts):
+        """The options as the level runs them -- the hooks' implied outputs,
+        the scorer's name -- checked; and the WorkBatch, if ``works`` is one."""
+        outputs, scorer = opts.outputs, opts.scorer
+        if opts.sample_only:
             outputs = True
         if scorer is None:
-            scorer = "auto" if pruned else "dense"
+            scorer = "auto" if opts.pruned else "dense"
         if scorer not in SCORERS:
             raise ValueError("scorer must be one of %s, got %r" % (SCORERS, scorer))
-        torch = self.torch
-        self._retired.clear()  # every earlier run ended with a synchronising readback / collect
-        hp = self.host_marks  # diagnostic: list of (name, perf_counter) or None
-
-        def _hmark(name):
-            if hp is not None:
-                hp.append((name, time.perf_counter()))
-        _hmark("start")
-
-        lib = self.lib
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        sp = ctypes.c_void_p(stream.cuda_stream)
-        if history is not None and histories is not None:
+        if opts.history is not None and opts.histories is not None:
             raise ValueError("give either history or histories")
-        hist_mode = history is not None or histories is not None
-        n_rows = 0  # split flags uploaded (single-history levels)
-        if table_scores:  # the fast table path's per-candidate scores (test hook)
+        if opts.table_scores:  # the fast table path's per-candidate scores (test hook)
             outputs = False
+        if outputs != opts.outputs or scorer != opts.scorer:
+            opts = replace(opts, outputs=outputs, scorer=scorer)
         batch = works if isinstance(works, WorkBatch) else None
-        if batch is not None and (not hist_mode or outputs or sample_only or posteriors or
-                                  table_scores):
+        if batch is not None and (not opts.hist_mode or opts.hooks):
             raise ValueError("a WorkBatch runs with history= / histories= and no output hooks")
-        works, pkey, cached, plan = self._choose_plan(
-            works, batch, prior_weight, lf, precision, scorer, outputs, sample_only, hist_mode,
-            histories is not None, _hmark)
-        (cont, quant, cat, fit_ids, params, nf, segs, obs_pool, n_obs_total, n_comp, max_obs,
-         csegs, cobs_pool, p_pool, cat_meta, cobs_off, lat_ranges, fallback, modes, groups,
-         order, gathers, inj, jobs, cand_pool, fb_jobs, fb_slice, out_off, lat_off, qfb_off,
-         sort_off, cnt_off, tbl_off) = plan
-        if cached is not None:
-            g_arr = gathers  # (a cached plan gives the gather table itself)
-        pack = _Pack()
-        _hmark('plan')
-        # ---- upload (descriptors, jobs, injected candidates: one copy) -----------
-        o_segs = pack.add(segs) if segs.size else None
-        o_csegs = pack.add(csegs) if csegs.size else None
-        o_p = pack.add(p_pool)
-        if hist_mode:
-            if cached is None:
-                g_arr = np.zeros(len(gathers), L.GATHER_DTYPE)
-            if cached is None and gathers:
-                (g_arr["col"], g_arr["below"], g_arr["dst_off"], g_arr["offset"], g_arr["count"],
-                 g_arr["to_int"], g_arr["hist"]) = (np.array(c) for c in zip(*gathers))
-            o_g = pack.add(g_arr)
-            if histories is None:
-                # (the split flags and row list go last in the pack, after the
-                # result block: a level whose history grew keeps every other
-                # offset, so its records can be re-issued, _Replay)
-                isb = np.ascontiguousarray(is_below, dtype=np.uint8)
-                n_rows = isb.size
-            else:  # row lists / flags at offsets of the staged pack (the `aux` base)
-                h_arr = np.zeros(len(histories), L.HISTORY_DTYPE)
-                for h, (dh, h_rows, h_isb) in enumerate(histories):
-                    h_isb = np.ascontiguousarray(h_isb, dtype=np.uint8)
-                    h_arr[h] = (dh.vals.data_ptr(), dh.active.data_ptr(), dh.ld, dh.n_labels,
-                                h_isb.size, pack.add(np.ascontiguousarray(h_rows, np.int32))
-                                if h_rows is not None else -1, pack.add(h_isb))
-                    if h_rows is None and h_isb.size > dh.rows:
-                        raise ValueError("history %d: %d split flags for %d rows"
-                                         % (h, h_isb.size, dh.rows))
-                o_h = pack.add(h_arr)
+        return opts, batch
+
+    def _pack_level(self, lv):
+        """The level's one upload -- descriptors, jobs, injected candidates, the
+        zeroed result block -- packed and staged; its offsets and the pointers
+        into its device copy go into ``lv``."""
+        plan, opts = lv.plan, lv.opts
+        pack = lv.pack = _Pack()
+        lv.o_segs = pack.add(plan.segs) if plan.segs.size else None
+        lv.o_csegs = pack.add(plan.csegs) if plan.csegs.size else None
+        lv.o_p = pack.add(plan.p_pool)
+        isb = None
+        if opts.histories is not None:
+            lv.o_g = pack.add(plan.g_arr)
+            # row lists / flags at offsets of the staged pack (the `aux` base)
+            h_arr = lv.h_arr = np.zeros(len(opts.histories), L.HISTORY_DTYPE)
+            for h, (dh, h_rows, h_isb) in enumerate(opts.histories):
+                h_isb = np.ascontiguousarray(h_isb, dtype=np.uint8)
+                h_arr[h] = (dh.vals.data_ptr(), dh.active.data_ptr(), dh.ld, dh.n_labels,
+                            h_isb.size, pack.add(np.ascontiguousarray(h_rows, np.int32))
+                            if h_rows is not None else -1, pack.add(h_isb))
+                if h_rows is None and h_isb.size > dh.rows:
+                    raise ValueError("history %d: %d split flags for %d rows"
+                                     % (h, h_isb.size, dh.rows))
+            lv.o_h = pack.add(h_arr)
+        elif lv.hist_mode:
+            lv.o_g = pack.add(plan.g_arr)
+            # (the split flags and row list go last in the pack, after the
+            # result block: a level whose history grew keeps every other
+            # offset, so its records can be re-issued, _Replay)
+            isb = np.ascontiguousarray(opts.is_below, dtype=np.uint8)
+            lv.n_rows = isb.size
         else:
-            o_obs = pack.add(obs_pool)
-            o_cobs = pack.add(cobs_pool)
+            lv.o_obs = pack.add(plan.obs_pool)
+            lv.o_cobs = pack.add(plan.cobs_pool)
         # lattice first-index slots (all-ones) and compaction counts (zero) ride
         # in the upload when the level is small (TPE_F_LATTICE_READY): no memsets
-        lat_g = _slice_of(groups, [k for k, _ in groups].index("lat"))
-        lat_ready = lat_g[1] > lat_g[0] and bool(
-            np.all(jobs["flags"][lat_g[0]:lat_g[1]] & L.F_LATTICE_READY))
-        if lat_ready:
-            o_slot = pack.add(self._ones(lat_off))
-            o_lcnt = pack.add(np.zeros(lat_g[1] - lat_g[0], np.int64))
-        o_jobs = pack.add(jobs) if jobs.size else None
-        o_fb = pack.add(fb_jobs) if fb_jobs.size else None
-        o_cand = pack.add(cand_pool)
-        # one result block, zeroed by the upload and read back with one copy:
-        # [0,16) error bits, [16,40) table stats, [40,48) sorted-path pair
-        # count, [64,...) tpe_best per job
-        JS, BS = L.JOB_DTYPE.itemsize, L.BEST_DTYPE.itemsize
-        n_jobs = len(order)
-        xbytes = 0
-        if exchange is not None:
-            x_comm, x_labels, x_world, x_slots = exchange
+        jobs, groups = plan.jobs, plan.groups
+        la, lb = _slice_of(groups, [k for k, _ in groups].index("lat"))
+        lv.lat_ready = lb > la and bool(np.all(jobs["flags"][la:lb] & L.F_LATTICE_READY))
+        if lv.lat_ready:
+            lv.o_slot = pack.add(self._ones(plan.lat_off))
+            lv.o_lcnt = pack.add(np.zeros(lb - la, np.int64))
+        lv.o_jobs = pack.add(jobs) if jobs.size else None
+        lv.o_fb = pack.add(plan.fb_jobs) if plan.fb_jobs.size else None
+        lv.o_cand = pack.add(plan.cand_pool)
+        BS = L.BEST_DTYPE.itemsize
+        n_jobs = lv.n_jobs = len(plan.order)
+        lv.xbytes = 0
+        if opts.exchange is not None:
+            lv.x_comm, lv.x_labels, lv.x_world, x_slots = opts.exchange
             x_slots = np.asarray(x_slots, np.int32).reshape(-1)
-            if x_slots.size != len(order):
-                raise ValueError("exchange: %d slots for %d works" % (x_slots.size, len(order)))
-            o_xslot = pack.add(x_slots[np.asarray(order, np.int64)])
-            xbytes = int(x_labels) * BS
-        o_res = pack.add(np.zeros(64 + n_jobs * BS + xbytes, np.uint8))
-        o_isb = o_rows = None
-        if hist_mode and histories is None:
-            o_isb = pack.add(isb)
-            o_rows = pack.add(np.ascontiguousarray(rows, dtype=np.int32)) \
-                if rows is not None else None
-        native_ok = self.native and pkey is not None and not (
-            outputs or sample_only or posteriors or table_scores)
-        base = self._upload(pack, stream, copy=not native_ok)
-        d_segs = base + o_segs if o_segs is not None else None
-        d_csegs = base + o_csegs if o_csegs is not None else None
-        d_res = base + o_res
-        d_err, d_stats, d_pairs, d_best = d_res, d_res + 16, d_res + 40, d_res + 64
-        # every workspace pointer before the first launch: the launches then
-        # follow each other without host work in between
-        d_w = d_mu = d_sig = d_cdf = d_c64 = d_c32 = d_logp = d_ccdf = None
-        nfs = 2 * len(fit_ids)
+            if x_slots.size != n_jobs:
+                raise ValueError("exchange: %d slots for %d works" % (x_slots.size, n_jobs))
+            lv.x_slots = x_slots
+            lv.o_xslot = pack.add(x_slots[np.asarray(plan.order, np.int64)])
+            lv.xbytes = int(lv.x_labels) * BS
+        # one result block, zeroed by the upload and read back with one copy
+        # (layout: RES_ERR ... RES_BEST)
+        lv.nbytes = RES_BEST + n_jobs * BS + lv.xbytes
+        lv.o_res = pack.add(np.zeros(lv.nbytes, np.uint8))
+        if isb is not None:
+            lv.o_isb = pack.add(isb)
+            lv.o_rows = pack.add(np.ascontiguousarray(opts.rows, dtype=np.int32)) \
+                if opts.rows is not None else None
+        lv.native_ok = self.native and plan.pkey is not None and not opts.hooks
+        base = lv.base = self._upload(pack, lv.stream, copy=not lv.native_ok)
+        lv.d_segs = base + lv.o_segs if lv.o_segs is not None else None
+        lv.d_csegs = base + lv.o_csegs if lv.o_csegs is not None else None
+        d_res = lv.d_res = base + lv.o_res
+        lv.d_err, lv.d_stats = d_res + RES_ERR, d_res + RES_STATS
+        lv.d_pairs, lv.d_best = d_res + RES_PAIRS, d_res + RES_BEST
+
+    def _workspace(self, lv):
+        """Every workspace pointer before the first launch (the launches then
+        follow each other without host work in between), the size-dependent
+        buffers grown first (_presize); the history's sorted orders brought up
+        to date for the sorted fit."""
+        plan, opts, history = lv.plan, lv.opts, lv.opts.history
+        groups, fit_ids = plan.groups, plan.fit_ids
+        lv.nfs = 2 * len(fit_ids)
         prune = bool(fit_ids) and any(k == "sorted" and ids for k, ids in groups)
         # the fit from the history's sorted orders (tpe_fit_sorted): one kernel
         # instead of gather + sort + merge ranks + three coefficient kernels;
@@ -1322,123 +1472,115 @@ class Engine:
         # (it walks the history's sorted order, a permutation of rows [0, rows):
         # the split flags must cover exactly those rows -- tpe_fit_sorted reads
         # is_below[row] for every one of them)
-        sorted_fit = bool(fit_ids) and self.sorted_fit and history is not None and \
-            histories is None and rows is None and not prune and n_rows == history.rows
-        tjobs = max([b - a for a, b in (_slice_of(groups, g) for g, (k, ids) in enumerate(groups)
-                                        if k in ("table", "pruned64") and ids)], default=0)
-        self._presize(n_comp, n_obs_total, max_obs, cobs_off, len(segs), tjobs,
-                      n_rows if sorted_fit else 0)
+        lv.sorted_fit = bool(fit_ids) and self.sorted_fit and history is not None and \
+            opts.histories is None and opts.rows is None and not prune and \
+            lv.n_rows == history.rows
+        lv.tjobs = max([b - a for a, b in (_slice_of(groups, g)
+                                           for g, (k, ids) in enumerate(groups)
+                                           if k in ("table", "pruned64") and ids)], default=0)
+        self._presize(plan, lv.tjobs, lv.n_rows if lv.sorted_fit else 0)
         if fit_ids:
-            d_w, d_mu, d_sig, d_cdf = (self._bufs[k].data_ptr() for k in ("w", "mu", "sigma",
-                                                                            "wcdf"))
-            d_c64, d_c32 = self._bufs["coef64"].data_ptr(), self._bufs["coef32"].data_ptr()
-            d_fs = self._bufs["fit_scratch"].data_ptr()
-            d_c32n = d_w32 = d_pm = d_sm = None
+            lv.d_w, lv.d_mu, lv.d_sig, lv.d_cdf = (self._bufs[k].data_ptr()
+                                                   for k in ("w", "mu", "sigma", "wcdf"))
+            lv.d_c64, lv.d_c32 = self._bufs["coef64"].data_ptr(), self._bufs["coef32"].data_ptr()
+            lv.d_fs = self._bufs["fit_scratch"].data_ptr()
+            lv.d_rh, lv.d_rl, lv.d_wide = (self._bufs[k].data_ptr()
+                                           for k in ("reach_hi", "reach_lo", "wide_idx"))
             if prune:
-                d_c32n = self._buf("coef32n", 16 * n_comp)
-                d_w32 = self._buf("wide32", 16 * n_comp)
-                d_pm = self._buf("pm", 4 * n_comp)
-                d_sm = self._buf("sm", 4 * n_comp)
-        if cat:
-            d_logp = self._buf("cat_logp", 8 * p_pool.size)
-            d_ccdf = self._buf("cat_cdf", 8 * p_pool.size)
-        self.last_plan = (segs, csegs, g_arr if hist_mode else None, jobs, cached is not None)
-        if sorted_fit:
-            history.ensure_order(self, stream, g_arr["col"][:nfs:2], segs["transform"][::2],
-                                 segs["floor"][::2])
+                lv.d_c32n, lv.d_w32, lv.d_pm, lv.d_sm = (
+                    self._bufs[k].data_ptr() for k in ("coef32n", "wide32", "pm", "sm"))
+        if plan.cat:
+            lv.d_logp = self._buf("cat_logp", 8 * plan.p_pool.size)
+            lv.d_ccdf = self._buf("cat_cdf", 8 * plan.p_pool.size)
+        self.last_plan = (plan.segs, plan.csegs, plan.g_arr if lv.hist_mode else None, plan.jobs,
+                          plan.cached)
+        if lv.sorted_fit:
+            history.ensure_order(self, lv.stream, plan.g_arr["col"][:lv.nfs:2],
+                                 plan.segs["transform"][::2], plan.segs["floor"][::2])
 
-        # ---- the level's launches (eager, or recorded and re-issued) ------------
-        # Every argument below is a workspace pointer (unchanged while _gen is),
-        # an offset into the staged pack, or a size covered by the launch key;
-        # the values that change from call to call live in the uploaded pack.
-        gkey = None
-        if native_ok:
-            # (the per-call sizes -- history rows, observation totals, the largest
-            # mixture, the pack size -- are size words of the records, rewritten
-            # when a recorded level is re-issued: _Replay)
-            gkey = (pkey, self._gen, sp.value, tuple(off for off, _ in pack.parts), lat_off,
-                    (history.vals.data_ptr(), history.active.data_ptr(), history.ld,
-                     history.order.data_ptr() if sorted_fit else None, rows is None)
-                    if history is not None else None,
-                    None if exchange is None else
-                    (int(x_comm), int(x_labels), int(x_world), x_slots.tobytes()),
-                    self.side_stream, self.table_scorer, self.exact64, self.lat_prefix,
-                    self.cat_early, self.cat_issue, self.cat_hist, self.lat_main,
-                    self.lat_max_slots,
-                    "off" if timers is None else
-                    ("all" if timer_groups is None else frozenset(timer_groups)))
-        band_jobs = []  # (first, end) job positions scored by tpe_score_table_fast
-        ctx = _LaunchCtx(self, stream, timers, timer_groups)
-        here = locals()  # (outside the comprehension: its own scope)
-        lv = _LevelState(**{k: v for k, v in here.items() if k in _LAUNCH_STATE})
+    def _launch_key(self, lv):
+        """The key under which the level's launches are recorded and re-issued
+        (None: not recordable).  Every launch argument is a workspace pointer
+        (unchanged while _gen is), an offset into the staged pack, or a size
+        covered by this key; the values that change from call to call live in
+        the uploaded pack.  (The per-call sizes -- history rows, observation
+        totals, the largest mixture, the pack size -- are size words of the
+        records, rewritten when a recorded level is re-issued: _Replay.)"""
+        if not lv.native_ok:
+            return None
+        opts, history = lv.opts, lv.opts.history
+        return (lv.plan.pkey, self._gen, lv.sp.value, tuple(off for off, _ in lv.pack.parts),
+                lv.plan.lat_off,
+                (history.vals.data_ptr(), history.active.data_ptr(), history.ld,
+                 history.order.data_ptr() if lv.sorted_fit else None, opts.rows is None)
+                if history is not None else None,
+                None if opts.exchange is None else
+                (int(lv.x_comm), int(lv.x_labels), int(lv.x_world), lv.x_slots.tobytes()),
+                self.side_stream, self.table_scorer, self.exact64, self.lat_prefix,
+                self.cat_early, self.cat_issue, self.cat_hist, self.lat_main,
+                self.lat_max_slots, opts.timer_spec())
 
-        nbytes = 64 + n_jobs * BS + xbytes  # the result block read back at the end
-        ops, table_calls, band_jobs, post = self._issue_level(
-            lv, ctx, gkey, nbytes, d_res, batch is not None,
-            dict(n_rows=n_rows, max_obs=max_obs, n_obs_total=n_obs_total, max_comp=max_obs + 1,
-                 pack_size=pack.size))
-        if post:
-            return table_calls
-        _hmark('score launches')
+    def _finish_level(self, lv, ops, table_calls, gkey):
+        """The level's readback: one device->host copy of the result block into
+        pinned memory (issued by the records themselves on the native path),
+        then the results -- a WorkBatch's through a _Pending (collected now, or
+        by the caller with ``defer``), registered for re-issue when the level
+        was recorded; a work list's synchronously (_read_results)."""
+        plan, opts, sp = lv.plan, lv.opts, lv.sp
         # the exact re-score of a band that overflowed (a plateau of equal fp32
         # scores; tpe_score_table_fast leaves n_scored = -1): after the readback
         fix = None
-        if band_jobs:
-            fix = functools.partial(self._band_fix, list(band_jobs), d_segs, max_obs + 1, n_comp,
-                                    sp.value, exchange is not None)
+        if lv.band_jobs:
+            fix = functools.partial(self._band_fix, list(lv.band_jobs), lv.d_segs,
+                                    plan.max_obs + 1, plan.n_comp, sp.value)
         xinfo = None
-        if exchange is not None:  # (comm, labels, world, slot per job in launch order, stream)
-            xinfo = (int(x_comm), int(x_labels), int(x_world),
-                     x_slots[np.asarray(order, np.int64)].copy(), sp.value)
-        # ---- results: one device->host copy of the result block into pinned memory
-        # (issued by the records themselves on the native path)
-        pin = self._res_pinned(nbytes)
+        if opts.exchange is not None:  # (comm, labels, world, slot per job in launch order, stream)
+            xinfo = (int(lv.x_comm), int(lv.x_labels), int(lv.x_world),
+                     lv.x_slots[np.asarray(plan.order, np.int64)].copy(), sp.value)
+        pin = self._res_pinned(lv.nbytes)
         if ops is None:
-            L.hip_check(self._hip.hipMemcpyAsync(pin.data_ptr(), d_res, nbytes, L.D2H, sp),
+            L.hip_check(self._hip.hipMemcpyAsync(pin.data_ptr(), lv.d_res, lv.nbytes, L.D2H, sp),
                         "hipMemcpyAsync")
         after = None
-        if ops is not None and ops.timed and timers is not None:
-            after = functools.partial(ops.read_timers, self._hip, timers)
-        if batch is not None:  # queued readback (see _Pending)
-            ev = self._event("result")
-            if ops is None:
-                L.hip_check(self._hip.hipEventRecord(ev, sp), "hipEventRecord")
-            p = self._inflight = _Pending(self, ev, pin, nbytes, np.asarray(order, np.int64),
-                                          64 + n_jobs * BS if xbytes else None,
-                                          bool(table_calls), after, fix, jobs, xinfo)
-            if ops is not None and self._oplists.get(gkey) is ops and history is not None:
-                # a recorded level: the next call with the same signature only
-                # rewrites its keys and split flags in the staged pack (_Replay)
-                sig = _Replay.signature(self, works, prior_weight, lf, precision, outputs,
-                                        (sp.value or 0) if stream_arg is None else None,
-                                        sample_only,
-                                        pruned, scorer, posteriors,
-                                        history, rows, is_below, histories, timers,
-                                        timer_groups, table_scores, exchange)
-                if sig is not None:
-                    if len(self._replays) >= 8:
-                        self._replays.clear()
-                    self._replays[sig] = _Replay(
-                        sig, self._gen, ops, self._pinned[0], pkey, p, pin,
-                        dict(segs=o_segs, csegs=o_csegs, g=o_g, jobs=o_jobs, fb=o_fb, isb=o_isb),
-                        history if sorted_fit else None, tjobs,
-                        (list(band_jobs), d_segs, sp.value, exchange is not None, xinfo))
-                    self._staged_sig = sig[:-1]
-            return p if defer else p.result()
-        return self._read_results(stream, sp, ops is None, after, pin, nbytes, n_jobs, fix, jobs,
-                                  xbytes, groups, table_calls, outputs, table_scores, out_off,
-                                  works, order, cont, modes, _hmark, xinfo)
+        if ops is not None and ops.timed and opts.timers is not None:
+            after = functools.partial(ops.read_timers, self._hip, opts.timers)
+        # pairs: the sorted path's count is reported for a work list only.  A
+        # WorkBatch level can hold a sorted group (scorer="sorted"; such a plan
+        # is never recorded, so it is planned anew every call), and its
+        # _Pending has always left last_pairs at None: kept so
+        rb = _Readback(pin=pin, nbytes=lv.nbytes, n_jobs=lv.n_jobs, jobs=plan.jobs,
+                       table=bool(table_calls),
+                       pairs=lv.batch is None and any(k == "sorted" and ids
+                                                      for k, ids in plan.groups),
+                       xbytes=lv.xbytes, after=after, fix=fix, xinfo=xinfo)
+        if lv.batch is None:
+            return self._read_results(lv, rb, ops is None)
+        ev = self._event("result")  # queued readback (see _Pending)
+        if ops is None:
+            L.hip_check(self._hip.hipEventRecord(ev, sp), "hipEventRecord")
+        p = self._inflight = _Pending(self, ev, np.asarray(plan.order, np.int64), rb)
+        if ops is not None and self._oplists.get(gkey) is ops and opts.history is not None:
+            # a recorded level: the next call with the same signature only
+            # rewrites its keys and split flags in the staged pack (_Replay)
+            sig = _Replay.signature(self, lv.batch, opts,
+                                    (sp.value or 0) if opts.stream is None else None)
+            if sig is not None:
+                if len(self._replays) >= 8:
+                    self._replays.clear()
+                self._replays[sig] = _Replay(self, sig, lv, ops, p)
+                self._staged_sig = sig[:-1]
+        return p if opts.defer else p.result()
 
 
-    def _issue_level(self, lv, ctx, gkey, nbytes, d_res, queued, sizes):
+    def _issue_level(self, lv, ctx, gkey, queued):
         """Issue a prepared level's stream work: re-issue its recorded records
         from C (tpe_run_ops); record them first on the second call in a row
         with launch key ``gkey`` (None: the level is not recordable); or launch
         eagerly, the deferred upload first.  ``queued``: the recorded readback
         ends with an event (a WorkBatch, _Pending) instead of a stream sync.
-        ``sizes``: this call's size words of the records.
-        Returns (ops or None, table_calls, band_jobs, posteriors_done)."""
-        sp = lv.sp
+        The jobs scored through a band go into ``lv.band_jobs``.
+        Returns (ops or None, table_calls, posteriors_done)."""
+        sp, nbytes = lv.sp, lv.nbytes
         ops = None
         if gkey is not None:
             ops = self._oplists.get(gkey)
@@ -1456,13 +1598,13 @@ class Engine:
                 finally:
                     ctx.cap = None
                 pin = self._res_pinned(nbytes)
-                rec.add(L.OP_MEMCPY, pin.data_ptr(), d_res, nbytes, L.D2H, sp)
+                rec.add(L.OP_MEMCPY, pin.data_ptr(), lv.d_res, nbytes, L.D2H, sp)
                 if queued:
                     rec.add(L.OP_EVENT_RECORD, self._event("result"), sp)
                 else:
                     rec.add(L.OP_STREAM_SYNC, sp)
-                rec.finish((lv.jobs, lv.fb_jobs, lv.g_arr if lv.hist_mode else None,
-                            lv.h_arr if lv.histories is not None else None), sp.value or 0)
+                rec.finish((lv.plan.jobs, lv.plan.fb_jobs, lv.plan.g_arr if lv.hist_mode else None,
+                            lv.h_arr if lv.opts.histories is not None else None), sp.value or 0)
                 if self._gen == gen0:  # every recorded pointer is still the live one
                     if len(self._oplists) >= 16 or any(
                             k[1] != gen0 for k in self._oplists):
@@ -1481,16 +1623,12 @@ class Engine:
             if not post:
                 self._last_gkey = gkey
                 self.graph_stats["eager"] += 1
-            return None, table_calls, lv.band_jobs, post
-        ops.set_sizes(sizes)
-        keep = ops.keep  # the host copies the entry points validate: this call's
-        keep[0][...] = lv.jobs
-        keep[1][...] = lv.fb_jobs
-        if keep[2] is not None:
-            keep[2][...] = lv.g_arr
+            return None, table_calls, post
+        ops.refill(lv.plan, lv.sizes())
         ops.issue(self)
         self.graph_stats["native"] = self.graph_stats.get("native", 0) + 1
-        return ops, ops.table_calls, ops.band_jobs, False
+        lv.band_jobs = list(ops.band_jobs)
+        return ops, ops.table_calls, False
 
     def _launch_level(self, lv, ctx, lib=None):
         """The level's launches, in stream order: the body of run() for a prepared
@@ -1503,7 +1641,8 @@ class Engine:
         Returns (table_calls, posteriors_done)."""
         if lib is None:
             lib = self.lib
-        sp, cat, groups, hist_mode = lv.sp, lv.cat, lv.groups, lv.hist_mode
+        plan, opts = lv.plan, lv.opts
+        sp, cat, groups, hist_mode = lv.sp, plan.cat, plan.groups, lv.hist_mode
         # quantized labels on the main stream when it has no scorer of its own
         # (a level of quantized and categorical labels only -- C5's middle
         # level): the lattice work then runs beside the categorical chain on
@@ -1512,10 +1651,10 @@ class Engine:
         lat_main = self.lat_main and has_q and not any(
             ids for k, ids in groups if k not in SIDE_KINDS)
         side = None
-        if self.side_stream != "0" and not lv.sample_only and not lv.posteriors and any(
+        if self.side_stream != "0" and not opts.sample_only and not opts.posteriors and any(
                 ids for k, ids in groups if k in SIDE_KINDS and not (lat_main and k != "cat")):
             if self._side is None:
-                self._side = lv.torch.cuda.Stream(self.device)
+                self._side = self.torch.cuda.Stream(self.device)
             side = self._side
         side_p = ctypes.c_void_p(side.cuda_stream) if side is not None else sp
         st = _LaunchState(
@@ -1524,12 +1663,12 @@ class Engine:
             # observations, which only their posterior (side stream) reads: it
             # runs there, behind an event after the upload, and the main
             # stream starts with the fit
-            gather_side=hist_mode and lv.histories is None and lv.sorted_fit and
+            gather_side=hist_mode and opts.histories is None and lv.sorted_fit and
             side is not None and bool(cat) and self.cat_early,
             # the categorical posteriors can count their labels in the history
             # itself (no gathered lists): the gather then lists only the fit's
             # sets, and none with the sorted fit (it reads the history itself)
-            cat_hist=hist_mode and lv.histories is None and bool(cat) and self.cat_hist,
+            cat_hist=hist_mode and opts.histories is None and bool(cat) and self.cat_hist,
             # categorical labels need only the gathered lists: with cat_early
             # the side stream starts their posterior and scoring from an event
             # recorded after the gather, so they run beside the latency-bound
@@ -1539,10 +1678,10 @@ class Engine:
             # fit ends)
             cat_early=side is not None and bool(cat) and self.cat_early,
             joined=side is None, side_started=side is None, cat_started=False,
-            table_calls=[], jobs_ptr=lv.jobs.__array_interface__["data"][0],
-            d_obs=None, d_cobs=None, lat_main=lat_main)
+            table_calls=[], jobs_ptr=plan.jobs.__array_interface__["data"][0],
+            lat_main=lat_main)
         self._launch_gather(lv, st)
-        lv._hmark('upload+gather')
+        self._mark('upload+gather')
         # side stream (TPE_SIDE_STREAM != "0"): quantized and categorical work
         # overlaps the continuous pipeline; the categorical posterior starts on
         # it as soon as the lists are gathered (it needs nothing else)
@@ -1554,15 +1693,14 @@ class Engine:
         # categorical posterior could start at the gather, but the side
         # stream has the slack and the fork costs two more host calls)
         st.d_cand = lv.base + lv.o_cand
-        st.d_bl = st.d_al = st.d_x = st.d_sc = st.d_eps = None
-        if lv.outputs:
-            st.d_bl = self._buf("out_bl", 8 * max(lv.out_off, 1))
-            st.d_al = self._buf("out_al", 8 * max(lv.out_off, 1))
-            st.d_x = self._buf("out_x", 8 * max(lv.out_off, 1))
-        elif lv.table_scores:
-            st.d_sc = self._buf("out_sc", 8 * max(lv.out_off, 1))
-            st.d_x = self._buf("out_x", 8 * max(lv.out_off, 1))
-            st.d_eps = self._buf("out_eps", 8 * max(lv.out_off, 1))
+        if opts.outputs:
+            st.d_bl = self._buf("out_bl", 8 * max(plan.out_off, 1))
+            st.d_al = self._buf("out_al", 8 * max(plan.out_off, 1))
+            st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
+        elif opts.table_scores:
+            st.d_sc = self._buf("out_sc", 8 * max(plan.out_off, 1))
+            st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
+            st.d_eps = self._buf("out_eps", 8 * max(plan.out_off, 1))
         lv.band_jobs.clear()
         if st.cat_early:
             if not st.gather_side:
@@ -1574,12 +1712,10 @@ class Engine:
         self._launch_fit(lv, st)
         if cat and side is None:
             self._cat_fit(lv, st)
-        if lv.posteriors:
-            return self._read_posteriors(lv.works, lv.fit_ids, cat, lv.segs, lv.csegs,
-                                         lv.n_comp, lv.p_pool.size, lv.d_segs, lv.stream,
-                                         lv.o_p), True
-        lv._hmark('jobs')
-        lv._hmark('fit')
+        if opts.posteriors:
+            return self._read_posteriors(lv), True
+        self._mark('jobs')
+        self._mark('fit')
         # ---- scoring, one call per group ----------------------------------------
         # quantized and categorical groups go to the side stream (after the job
         # table has landed); continuous groups stay on `stream`
@@ -1592,8 +1728,8 @@ class Engine:
                 self._cat_fit(lv, st)
         if not st.joined:  # join before the readback
             ctx.stream_order("joined", side_p, sp)
-        if lv.exchange is not None:  # label-sharded level: the cross-rank argmax
-            BS = lv.BS
+        if opts.exchange is not None:  # label-sharded level: the cross-rank argmax
+            BS = L.BEST_DTYPE.itemsize
             d_xl = self._buf("xchg_local", lv.x_labels * BS)
             d_xg = self._buf("xchg_gathered", lv.x_world * lv.x_labels * BS)
             L.check(lib.tpe_best_scatter(lv.d_best, lv.base + lv.o_xslot, lv.n_jobs, d_xl,
@@ -1610,7 +1746,7 @@ class Engine:
         main-stream scorers -- the host issues launches at a few us each, and
         at a one-eighth label share the main stream would otherwise sit idle
         behind the side stream's launches."""
-        groups, inj = lv.groups, lv.inj
+        groups, inj = lv.plan.groups, lv.plan.inj
         if st.side is None:
             return [(g, "all") for g in range(len(groups))]
         early = None
@@ -1636,17 +1772,17 @@ class Engine:
         if not lv.hist_mode:
             st.d_obs, st.d_cobs = lv.base + lv.o_obs, lv.base + lv.o_cobs
             return
-        nfs, g_arr, base, history = lv.nfs, lv.g_arr, lv.base, lv.history
+        nfs, g_arr, base, history = lv.nfs, lv.plan.g_arr, lv.base, lv.opts.history
         g0 = nfs if lv.sorted_fit else 0
         g1 = nfs if st.cat_hist else (len(g_arr) if g_arr is not None else 0)
         # (the categorical descriptors follow the fit's)
-        st.d_obs = d_obs = self._buf("obs_dev", 8 * max(lv.n_obs_total, 1))
-        st.d_cobs = d_cobs = self._buf("cobs_dev", 8 * max(lv.cobs_off, 1))
+        st.d_obs = d_obs = self._buf("obs_dev", 8 * max(lv.plan.n_obs_total, 1))
+        st.d_cobs = d_cobs = self._buf("cobs_dev", 8 * max(lv.plan.cobs_off, 1))
         gs, gsp = (st.side, st.side_p) if st.gather_side else (None, sp)
         if st.gather_side:
             ctx.stream_order("uploaded", sp, st.side_p)
         e0 = ctx.tick("gather", gs)
-        if lv.histories is None:
+        if lv.opts.histories is None:
             if g1 > g0:
                 GI = L.GATHER_DTYPE.itemsize
                 L.check(lib.tpe_gather_obs(history.vals.data_ptr(), history.active.data_ptr(),
@@ -1668,25 +1804,26 @@ class Engine:
     def _launch_fit(self, lv, st):
         """The continuous labels' posterior fit: tpe_fit_sorted (reads the
         history in its value order) or tpe_parzen_fit (the gathered lists)."""
-        if not lv.fit_ids:
+        plan = lv.plan
+        if not plan.fit_ids:
             return
         lib, ctx, sp = st.lib, st.ctx, lv.sp
         e0 = ctx.tick("fit")
         if lv.sorted_fit:
-            history = lv.history
+            history = lv.opts.history
             d_fss = self._buf("fit_sorted_scratch",
-                              lib.tpe_fit_sorted_scratch_bytes(len(lv.segs), lv.n_rows))
+                              lib.tpe_fit_sorted_scratch_bytes(len(plan.segs), lv.n_rows))
             L.check(lib.tpe_fit_sorted(history.vals.data_ptr(), history.active.data_ptr(),
                                        history.ld, history.order.data_ptr(),
                                        _V("n_rows", lv.n_rows),
-                                       lv.base + lv.o_isb, lv.base + lv.o_g, lv.g_arr.ctypes.data,
-                                       lv.d_segs, len(lv.segs), d_fss, lv.d_w, lv.d_mu, lv.d_sig,
+                                       lv.base + lv.o_isb, lv.base + lv.o_g, plan.g_arr.ctypes.data,
+                                       lv.d_segs, len(plan.segs), d_fss, lv.d_w, lv.d_mu, lv.d_sig,
                                        lv.d_cdf, lv.d_c64, lv.d_c32, lv.d_err, sp),
                     "tpe_fit_sorted")
         else:
-            L.check(lib.tpe_parzen_fit(st.d_obs, lv.d_fs, lv.d_segs, len(lv.segs),
-                                       _V("max_obs", lv.max_obs),
-                                       _V("n_obs_total", lv.n_obs_total),
+            L.check(lib.tpe_parzen_fit(st.d_obs, lv.d_fs, lv.d_segs, len(plan.segs),
+                                       _V("max_obs", plan.max_obs),
+                                       _V("n_obs_total", plan.n_obs_total),
                                        lv.d_w, lv.d_mu, lv.d_sig, lv.d_cdf, lv.d_c64, lv.d_c32,
                                        lv.d_c32n, lv.d_w32, lv.d_pm, lv.d_sm, sp),
                     "tpe_parzen_fit")
@@ -1696,11 +1833,11 @@ class Engine:
         """The categorical posteriors (on the side stream, after its fork):
         counted in the history itself (tpe_cat_posterior_hist) or from the
         gathered lists (tpe_cat_posterior)."""
-        lib, ctx, side, side_p, csegs = st.lib, st.ctx, st.side, st.side_p, lv.csegs
+        lib, ctx, side, side_p, csegs = st.lib, st.ctx, st.side, st.side_p, lv.plan.csegs
         e0 = ctx.tick("cat_fit", side)
         d_p = lv.base + lv.o_p  # the posterior is formed in place in the staged pool
         if st.cat_hist:  # (the categorical gather descriptors follow the fit's nfs)
-            history = lv.history
+            history = lv.opts.history
             max_cat = int(csegs["n_cat"].max())
             # a long history is counted in row chunks (work sized for the
             # history's capacity: it holds while the history does)
@@ -1723,7 +1860,7 @@ class Engine:
         """One group's scorer launches (``stage``: "all", or "build" / "score"
         -- the two halves of an early-built table group), after the side
         stream's fork where the group is the first to need it."""
-        kind, ids = lv.groups[g]
+        kind, ids = lv.plan.groups[g]
         if not ids:
             return
         ctx = st.ctx
@@ -1735,23 +1872,26 @@ class Engine:
         side_kind = kind in SIDE_KINDS and not (st.lat_main and kind != "cat")
         if not st.side_started and side_kind and not (st.cat_early and kind == "cat"):
             st.side_started = True  # the side stream's groups that need the fit
+            # (with TPE_CAT_EARLY=0 and lat_main this waits on a 'fitted' event
+            # that is no longer recorded -- ADVICE.md; kept as it is here)
             ctx.stream_wait("fitted", st.side_p)
-            if lv.cat and not st.cat_early:
+            if lv.plan.cat and not st.cat_early:
                 self._cat_fit(lv, st)
-        a, b = _slice_of(lv.groups, g)
-        if lv.sample_only:
+        a, b = _slice_of(lv.plan.groups, g)
+        if lv.opts.sample_only:
             if kind in ("cont", "lat", "qfb"):
                 L.check(st.lib.tpe_sample(lv.base + lv.o_jobs + a * L.JOB_DTYPE.itemsize,
-                                          lv.jobs[a:b].ctypes.data_as(ctypes.c_void_p), b - a,
-                                          lv.d_segs, lv.d_mu, lv.d_sig, lv.d_cdf, lv.precision,
+                                          lv.plan.jobs[a:b].ctypes.data_as(ctypes.c_void_p), b - a,
+                                          lv.d_segs, lv.d_mu, lv.d_sig, lv.d_cdf, lv.opts.precision,
                                           st.d_x, lv.sp), "tpe_sample")
             return
         on_side = st.side is not None and side_kind
         kst = st.side if on_side else None
-        sl = _LaunchState(
-            kind=kind, ids=ids, a=a, b=b, nj=b - a, hj=lv.jobs[a:b],
-            hjp=st.jobs_ptr + a * lv.JS,  # host copy of the slice (plain int: no ctypes object)
-            dj=lv.base + lv.o_jobs + a * lv.JS, db=lv.d_best + a * lv.BS,
+        JS = L.JOB_DTYPE.itemsize
+        sl = _GroupSlice(
+            kind=kind, ids=ids, a=a, b=b, nj=b - a, hj=lv.plan.jobs[a:b],
+            hjp=st.jobs_ptr + a * JS,  # host copy of the slice (plain int: no ctypes object)
+            dj=lv.base + lv.o_jobs + a * JS, db=lv.d_best + a * L.BEST_DTYPE.itemsize,
             ks=st.side_p if on_side else lv.sp,
             pname="partial_side" if on_side else "partial", stage=stage,
             e0=ctx.tick({"sorted": "sort", "table": "table_build"}.get(kind, kind), kst)
@@ -1765,7 +1905,7 @@ class Engine:
         d_part = self._buf("partial", 32 * max(npart, 1))
         L.check(st.lib.tpe_score_continuous(sl.dj, sl.hjp, sl.nj, lv.d_segs, lv.d_w, lv.d_mu,
                                             lv.d_sig, lv.d_cdf, lv.d_c64, lv.d_c32, st.d_cand,
-                                            lv.precision, st.d_bl, st.d_al, st.d_x, d_part,
+                                            lv.opts.precision, st.d_bl, st.d_al, st.d_x, d_part,
                                             npart, sl.db, lv.sp), "tpe_score_continuous")
         return sl.e0
 
@@ -1775,10 +1915,10 @@ class Engine:
         lib, ctx, sp = st.lib, st.ctx, lv.sp
         npart = lib.tpe_score_partials(sl.hjp, sl.nj) * 2
         d_part = self._buf("partial", 32 * max(npart, 1))
-        d_cnt = self._buf("sort_cnt", 8 * max(lv.cnt_off, 1))
-        d_gen = self._buf("sort_gen", 4 * max(lv.sort_off, 1))
-        d_sx = self._buf("sort_x", 4 * max(lv.sort_off, 1))
-        d_si = self._buf("sort_i", 4 * max(lv.sort_off, 1))
+        d_cnt = self._buf("sort_cnt", 8 * max(lv.plan.cnt_off, 1))
+        d_gen = self._buf("sort_gen", 4 * max(lv.plan.sort_off, 1))
+        d_sx = self._buf("sort_x", 4 * max(lv.plan.sort_off, 1))
+        d_si = self._buf("sort_i", 4 * max(lv.plan.sort_off, 1))
         L.check(lib.tpe_sort_candidates(sl.dj, sl.hjp, sl.nj, lv.d_segs, lv.d_mu, lv.d_sig,
                                         lv.d_cdf, d_cnt, d_gen, d_sx, d_si, sp),
                 "tpe_sort_candidates")
@@ -1796,17 +1936,15 @@ class Engine:
         tpe_band_rescore).  Stage "build" / "score": the two halves of an
         early-built group."""
         lib, ctx, sp = st.lib, st.ctx, lv.sp
-        hj, hjp, dj, nj, stage, n_comp = sl.hj, sl.hjp, sl.dj, sl.nj, sl.stage, lv.n_comp
+        hj, hjp, dj, nj, stage = sl.hj, sl.hjp, sl.dj, sl.nj, sl.stage
         npart = lib.tpe_table_partials(hjp, nj)
         d_part = self._buf("partial", 32 * max(npart, 1))
         d_tab = self._buf("tables", L.TABLE_DTYPE.itemsize * nj)
         d_cells = self._buf("cells", 128 * int(hj["tbl_off"].max() + TABLE_CAP
                                                - hj["tbl_off"].min()))
         d_cells -= 128 * int(hj["tbl_off"].min())
-        d_rh = self._buf("reach_hi", 8 * n_comp)
-        d_rl = self._buf("reach_lo", 8 * n_comp)
-        d_wide = self._buf("wide_idx", 4 * n_comp)
-        max_comp = _V("max_comp", lv.max_obs + 1)
+        d_rh, d_rl, d_wide = lv.d_rh, lv.d_rl, lv.d_wide
+        max_comp = _V("max_comp", lv.plan.max_obs + 1)
         d_tsc = self._buf("table_scratch", lib.tpe_table_scratch_bytes(nj, max_comp))
         if stage != "score":
             L.check(lib.tpe_table_build(dj, hjp, nj, lv.d_segs, lv.d_mu, lv.d_sig, lv.d_c64,
@@ -1819,7 +1957,7 @@ class Engine:
             ctx.stream_order("joined", st.side_p, sp)
             st.joined = True
         e0 = ctx.tick("table")
-        if lv.outputs or lv.inj(sl.ids[0]) or self.table_scorer == "poly":
+        if lv.opts.outputs or lv.plan.inj(sl.ids[0]) or self.table_scorer == "poly":
             L.check(lib.tpe_score_table(dj, hjp, nj, lv.d_segs, lv.d_mu, lv.d_sig, lv.d_cdf,
                                         lv.d_c32, d_tab, d_cells, st.d_cand, st.d_bl, st.d_al,
                                         st.d_x, d_part, npart, sl.db, lv.d_stats, sp),
@@ -1829,7 +1967,7 @@ class Engine:
             nbb = lib.tpe_band_bytes(hjp, nj, ctypes.byref(ctl_b), ctypes.byref(work_b))
             d_band = self._buf("band", nbb)
             d_bctl = self._buf("band_ctl", ctl_b.value)
-            d_bwork = self._zbuf("band_work", work_b.value)
+            d_bwork = self._buf("band_work", work_b.value, zero=True)
             L.check(lib.tpe_score_table_fast(dj, hjp, nj, lv.d_segs, lv.d_mu, lv.d_sig,
                                              lv.d_cdf, lv.d_c32, d_tab, d_cells, d_band, d_bctl,
                                              st.d_sc, st.d_x, st.d_eps, d_part, npart,
@@ -1849,14 +1987,12 @@ class Engine:
     def _score_pruned64(self, lv, st, sl):
         """The fp32 candidate stream scored exactly in fp64 with component
         pruning (tpe_score_pruned64; sampled labels below TABLE_MIN_CAND)."""
-        lib, n_comp = st.lib, lv.n_comp
+        lib = st.lib
         npart = lib.tpe_pruned64_partials(sl.hjp, sl.nj)
         d_part = self._buf("partial", 32 * max(npart, 1))
         d_tab = self._buf("tables", L.TABLE_DTYPE.itemsize * sl.nj)
-        d_rh = self._buf("reach_hi", 8 * n_comp)
-        d_rl = self._buf("reach_lo", 8 * n_comp)
-        d_wide = self._buf("wide_idx", 4 * n_comp)
-        max_comp = _V("max_comp", lv.max_obs + 1)
+        d_rh, d_rl, d_wide = lv.d_rh, lv.d_rl, lv.d_wide
+        max_comp = _V("max_comp", lv.plan.max_obs + 1)
         d_tsc = self._buf("table_scratch", lib.tpe_table_scratch_bytes(sl.nj, max_comp))
         L.check(lib.tpe_score_pruned64(sl.dj, sl.hjp, sl.nj, lv.d_segs, lv.d_mu, lv.d_sig,
                                        lv.d_cdf, lv.d_c64, max_comp, d_rh, d_rl, d_wide, d_tsc,
@@ -1870,14 +2006,13 @@ class Engine:
         lattice values' component windows come from k_qreach, on the quantized
         jobs' own components of the reach arrays."""
         lib, hj, hjp, dj, nj, ks = st.lib, sl.hj, sl.hjp, sl.dj, sl.nj, sl.ks
-        d_rh = self._buf("reach_hi", 8 * lv.n_comp)
-        d_rl = self._buf("reach_lo", 8 * lv.n_comp)
-        d_vals = self._buf("lat_vals", 8 * lv.lat_off)
-        d_first = self._buf("lat_first", 8 * lv.lat_off)
+        d_rh, d_rl = lv.d_rh, lv.d_rl
+        d_vals = self._buf("lat_vals", 8 * lv.plan.lat_off)
+        d_first = self._buf("lat_first", 8 * lv.plan.lat_off)
         if lv.lat_ready:
             d_slot, d_cnt = lv.base + lv.o_slot, lv.base + lv.o_lcnt
         else:
-            d_slot = self._buf("lat_slot", 8 * lv.lat_off)
+            d_slot = self._buf("lat_slot", 8 * lv.plan.lat_off)
             d_cnt = self._buf("lat_cnt", 8 * nj)
         max_vals = int(hj["lat_n"].max())
         if self.lat_prefix and max_vals <= self.lat_max_slots and \
@@ -1908,13 +2043,12 @@ class Engine:
         """Quantized labels scored on their candidates: fallback draws
         ("qfb", tpe_sample first) or injected candidates ("qinj")."""
         lib, hjp, nj, ks = st.lib, sl.hjp, sl.nj, sl.ks
-        d_rh = self._buf("reach_hi", 8 * lv.n_comp)
-        d_rl = self._buf("reach_lo", 8 * lv.n_comp)
+        d_rh, d_rl = lv.d_rh, lv.d_rl
         vals = st.d_cand
         if sl.kind == "qfb":
-            vals = self._buf("q_cand", 8 * max(lv.qfb_off, 1))
+            vals = self._buf("q_cand", 8 * max(lv.plan.qfb_off, 1))
             L.check(lib.tpe_sample(lv.base + lv.o_fb,
-                                   lv.fb_jobs.ctypes.data_as(ctypes.c_void_p), nj, lv.d_segs,
+                                   lv.plan.fb_jobs.ctypes.data_as(ctypes.c_void_p), nj, lv.d_segs,
                                    lv.d_mu, lv.d_sig, lv.d_cdf, 64, vals, ks), "tpe_sample")
         max_vals = int(sl.hj["n_cand"].max())
         npart = lib.tpe_quantized_partials(hjp, nj, max_vals)
@@ -1931,7 +2065,7 @@ class Engine:
         lib, hj, hjp, nj, ks = st.lib, sl.hj, sl.hjp, sl.nj, sl.ks
         npart = lib.tpe_categorical_partials(hjp, nj)
         d_part = self._buf(sl.pname, 32 * max(npart, 1))
-        if self.lat_prefix and not lv.inj(sl.ids[0]) and st.d_bl is None and st.d_x is None \
+        if self.lat_prefix and not lv.plan.inj(sl.ids[0]) and st.d_bl is None and st.d_x is None \
                 and int(hj["n_cand"].max()) > self.lat_prefix:
             # prefix first: the rest of a stream only where an unseen better
             # category could still be drawn (tpe_categorical_suggest)
@@ -1945,70 +2079,79 @@ class Engine:
                                               sl.db, ks), "tpe_score_categorical")
         return sl.e0
 
-    def _read_results(self, stream, sp, sync, after, pin, nbytes, n_jobs, fix, jobs, xbytes,
-                      groups, table_calls, outputs, table_scores, out_off, works, order, cont,
-                      modes, _hmark, xinfo=None):
-        """The level's synchronous readback: the result block (error bits, table
-        stats, one tpe_best per job, the exchange's label records) from the
-        pinned copy, the overflowed bands' exact re-score, per-candidate
-        outputs of the test hooks; one LabelResult per work."""
+    def _decode_results(self, rb):
+        """A level's result block, from its pinned copy (layout: RES_ERR ...
+        RES_BEST), for the synchronous readback and a _Pending alike: the
+        jobs' tpe_best records in launch order (returned), ``last_table_stats``,
+        ``last_pairs``, ``last_exchange``.  The order is fixed: the overflowed
+        bands' exact re-score, then the exchange's settle, and only then the
+        error bits -- a rank whose level set an error bit still takes part in
+        an owed second all-gather, so its peers are not left blocked in it."""
+        if rb.after is not None:
+            rb.after()
+            rb.after = None
         BS = L.BEST_DTYPE.itemsize
+        res_h = rb.pin[:rb.nbytes].numpy().copy()
+        end = RES_BEST + rb.n_jobs * BS
+        best_h = res_h[RES_BEST:end].view(L.BEST_DTYPE)
+        if rb.fix is not None:
+            rb.fix(best_h, rb.jobs)
+        xrec = None
+        if rb.xbytes:
+            xrec = self._exchange_fix(best_h, res_h[end:].view(L.BEST_DTYPE).copy(), rb.xinfo)
+        self.last_exchange = xrec
+        self.last_pairs = int(res_h[RES_PAIRS:RES_PAIRS + 8].view(np.int64)[0]) \
+            if rb.pairs else None
+        self.last_table_stats = None
+        if rb.table:
+            st = res_h[RES_STATS:RES_STATS + 24].view(np.int64).tolist()
+            self.last_table_stats = {"exact_candidates": st[0], "failed_cells": st[1],
+                                     "failed_score_cells": st[2]}
+        _raise_errors(int(res_h[RES_ERR:RES_ERR + 4].view(np.int32)[0]))
+        return best_h
+
+    def _read_results(self, lv, rb, sync):
+        """The level's synchronous readback: the result block (_decode_results),
+        per-candidate outputs of the test hooks; one LabelResult per work."""
+        plan, opts = lv.plan, lv.opts
         if sync:
-            L.hip_check(self._hip.hipStreamSynchronize(sp), "hipStreamSynchronize")
-        if after is not None:
-            after()
-        res_h = pin[:nbytes].numpy().copy()
-        best_h = res_h[64:64 + n_jobs * BS].view(L.BEST_DTYPE)
-        if fix is not None:
-            fix(best_h, jobs)
-        self.last_exchange = res_h[64 + n_jobs * BS:].view(L.BEST_DTYPE).copy() if xbytes \
-            else None
-        if xbytes:
-            self.last_exchange = self._exchange_fix(best_h, self.last_exchange, xinfo)
-        with self.torch.cuda.stream(stream):
-            err = int(res_h[:4].view(np.int32)[0])
-            self.last_pairs = None
-            if any(k == "sorted" and ids for k, ids in groups):
-                self.last_pairs = int(res_h[40:48].view(np.int64)[0])
-            self.last_table_stats = None
-            if table_calls:
-                st = res_h[16:40].view(np.int64).tolist()
-                self.last_table_stats = {"exact_candidates": st[0], "failed_cells": st[1],
-                                         "failed_score_cells": st[2]}
-            outs = None
-            if outputs:
-                outs = [self._bufs[k][:8 * max(out_off, 1)].to("cpu").numpy().view(np.float64)
-                        for k in ("out_bl", "out_al", "out_x")]
-            elif table_scores:
-                outs = [self._bufs[k][:8 * max(out_off, 1)].to("cpu").numpy().view(np.float64)
-                        for k in ("out_sc", "out_x", "out_eps")]
+            L.hip_check(self._hip.hipStreamSynchronize(lv.sp), "hipStreamSynchronize")
+        best_h = self._decode_results(rb)
+        jobs, out_off = plan.jobs, plan.out_off
+        names = ("out_bl", "out_al", "out_x") if opts.outputs else \
+            ("out_sc", "out_x", "out_eps") if opts.table_scores else ()
+        with self.torch.cuda.stream(lv.stream):
+            outs = [self._bufs[k][:8 * max(out_off, 1)].to("cpu").numpy().view(np.float64)
+                    for k in names]
+            if opts.table_scores:
                 ta, tb = self._tables_slice
                 tabs = self._bufs["tables"][:L.TABLE_DTYPE.itemsize * (tb - ta)].to("cpu") \
                     .numpy().view(L.TABLE_DTYPE)
-        _raise_errors(err)
-        _hmark('readback')
+        self._mark('readback')
+        works = plan.works
         results = [None] * len(works)
         b_idx, b_val = best_h["index"].tolist(), best_h["value"].tolist()
         b_sc, b_ns = best_h["score"].tolist(), best_h["n_scored"].tolist()
-        for pos, i in enumerate(order):
+        for pos, i in enumerate(plan.order):
             w = works[i]
             r = LabelResult(w.label, b_idx[pos], b_val[pos], b_sc[pos], b_ns[pos])
-            if outputs:
+            if opts.outputs:
                 o, n = int(jobs[pos]["out_off"]), int(jobs[pos]["n_cand"])
                 r.below_llik = outs[0][o:o + n].copy()
                 r.above_llik = outs[1][o:o + n].copy()
                 r.cand = outs[2][o:o + n].copy()
-            elif table_scores and i in cont and modes[i] == "table":
+            elif opts.table_scores and plan.modes.get(i) == "table":
                 o, n = int(jobs[pos]["out_off"]), int(jobs[pos]["n_cand"])
                 r.extra["score"] = outs[0][o:o + n].copy()
                 r.extra["eps"] = outs[2][o:o + n].copy()  # the band's bound per candidate
                 r.extra["table"] = tabs[pos - ta].copy()  # (slope, eps_cubic, eps_mix, ...)
                 r.cand = outs[1][o:o + n].copy()
             results[i] = r
-        _hmark("results")
+        self._mark("results")
         return results
 
-    def _band_fix(self, band_jobs, d_segs, max_comp, n_comp, stream, exchanged, best_h, jobs):
+
+    def _band_fix(self, band_jobs, d_segs, max_comp, n_comp, stream, best_h, jobs):
         """Jobs of the table path whose band overflowed (n_scored == -1: more
         than BAND_TILE_CAP candidates of one scorer tile within the fp32 error bound of the maximum --
         a plateau of equal scores) are re-scored exactly: their fp32 candidate
@@ -2039,7 +2182,7 @@ class Engine:
         res = out.cpu().numpy().view(L.BEST_DTYPE)
         for k, p in enumerate(pos):
             best_h[p] = res[k]
-        self.band_overflows = getattr(self, "band_overflows", 0) + len(pos)
+        self.band_overflows += len(pos)
         self.last_band_overflow = [(int(p), int(jobs[p]["family"]), int(jobs[p]["n_cand"]))
                                    for p in pos]  # (diagnostic: launch position, family, n)
 
@@ -2073,27 +2216,29 @@ class Engine:
             L.check(lib.tpe_maxloc_allreduce(d_xl.data_ptr(), d_xg.data_ptr(), d_out.data_ptr(),
                                              n_labels, comm, sp), "tpe_maxloc_allreduce (fix)")
             L.hip_check(self._hip.hipStreamSynchronize(sp), "hipStreamSynchronize")
-            self.exchange_fixes = getattr(self, "exchange_fixes", 0) + 1
+            self.exchange_fixes += 1
             return d_out.cpu().numpy().view(L.BEST_DTYPE).copy()
         return hdist.settle_exchange(xrec, lambda: best_h, exchange)
 
-    def _read_posteriors(self, works, fit_ids, cat, segs, csegs, n_comp, n_p, d_segs, stream,
-                         o_p):
-        torch = self.torch
-        with torch.cuda.stream(stream):
+    def _read_posteriors(self, lv):
+        """The ``posteriors`` hook's results: the fitted mixtures and the
+        categorical posteriors read back after the fit."""
+        torch, plan = self.torch, lv.plan
+        works, fit_ids, cat, segs, csegs = plan.works, plan.fit_ids, plan.cat, plan.segs, plan.csegs
+        with torch.cuda.stream(lv.stream):
             host = {}
             if fit_ids:
                 for k in ("w", "mu", "sigma"):
-                    host[k] = self._bufs[k][:8 * n_comp].to("cpu").numpy().view(np.float64)
+                    host[k] = self._bufs[k][:8 * plan.n_comp].to("cpu").numpy().view(np.float64)
                 seg_t = self._bufs["stage"]
                 # the fit writes prior_pos / p_accept back into the staged segment table
                 raw = torch.empty(segs.nbytes, dtype=torch.uint8)
-                off = d_segs - seg_t.data_ptr()
+                off = lv.d_segs - seg_t.data_ptr()
                 raw.copy_(seg_t[off:off + segs.nbytes])
                 dsegs = raw.numpy().view(L.SEG_DTYPE)
             if cat:
-                host["p"] = self._bufs["stage"][o_p:o_p + 8 * n_p].to("cpu").numpy() \
-                    .view(np.float64)
+                host["p"] = self._bufs["stage"][lv.o_p:lv.o_p + 8 * plan.p_pool.size].to("cpu") \
+                    .numpy().view(np.float64)
         results = [LabelResult(w.label, -1, 0.0, 0.0, 0) for w in works]
         for si, i in enumerate(fit_ids):
             post = {}
@@ -2116,49 +2261,23 @@ class Engine:
 
 class _Pending(object):
     """A WorkBatch run whose result block is being copied back (Engine.run
-    with defer=True).  ``result()`` waits for it once, checks the error bits
-    and returns the BatchResult (cached)."""
+    with defer=True).  ``result()`` waits for it once, decodes the block
+    (Engine._decode_results: ``rb``) and returns the BatchResult (cached)."""
+    __slots__ = ("eng", "event", "order", "rb", "_res")
 
-    def __init__(self, eng, event, pin, nbytes, order, xoff, table, after=None, fix=None,
-                 jobs=None, xinfo=None):
-        self.eng, self.event, self.pin, self.nbytes = eng, event, pin, nbytes
-        self.order, self.table, self.after = order, table, after
-        self.fix, self.jobs = fix, jobs  # band overflow re-score (Engine._band_fix)
-        self.xoff = xoff  # offset of the exchanged label records (Engine.run exchange=)
-        self.xinfo = xinfo  # what Engine._exchange_fix needs to redo an owed exchange
+    def __init__(self, eng, event, order, rb):
+        self.eng, self.event, self.order, self.rb = eng, event, order, rb
         self._res = None
 
     def result(self):
         if self._res is not None:
             return self._res
-        L.hip_check(self.eng._hip.hipEventSynchronize(self.event), "hipEventSynchronize")
-        if self.after is not None:
-            self.after()
-            self.after = None
         eng = self.eng
+        L.hip_check(eng._hip.hipEventSynchronize(self.event), "hipEventSynchronize")
         if eng._inflight is self:
             eng._inflight = None
-        res_h = self.pin[:self.nbytes].numpy().copy()
-        err = int(res_h[:4].view(np.int32)[0])
-        eng.last_pairs = None
-        eng.last_table_stats = None
-        if self.table:
-            st = res_h[16:40].view(np.int64).tolist()
-            eng.last_table_stats = {"exact_candidates": st[0], "failed_cells": st[1],
-                                    "failed_score_cells": st[2]}
+        best_h = eng._decode_results(self.rb)
         n = self.order.size
-        best_h = res_h[64:64 + n * L.BEST_DTYPE.itemsize].view(L.BEST_DTYPE)
-        # the same order as Engine._read_results: the band fix and the settle
-        # exchange first, the error bits after -- a rank whose level set an
-        # error bit still takes part in an owed second all-gather, so its
-        # peers are not left blocked in it (ADVICE r4)
-        if self.fix is not None:
-            self.fix(best_h, self.jobs)
-        eng.last_exchange = res_h[self.xoff:].view(L.BEST_DTYPE).copy() \
-            if self.xoff is not None else None
-        if self.xoff is not None:
-            eng.last_exchange = eng._exchange_fix(best_h, eng.last_exchange, self.xinfo)
-        _raise_errors(err)
         by = np.empty(n, L.BEST_DTYPE)
         by[self.order] = best_h[:n]
         self._res = BatchResult(by["index"].copy(), by["value"].copy(), by["score"].copy(),
@@ -2181,56 +2300,61 @@ class _Replay(object):
     input the pack and the records depend on; a workspace buffer that would
     have to grow (a new pointer) sends the call down the full path instead."""
 
-    def __init__(self, sig, gen, ops, pinned, pkey, pending, res_pin, offs, history, tjobs,
-                 fix_args):
-        self.sig, self.gen, self.ops, self.pkey = sig, gen, ops, pkey
-        self.pinned, self.host = pinned, pinned.numpy()
-        self.offs, self.history, self.tjobs, self.fix_args = offs, history, tjobs, fix_args
+    def __init__(self, eng, sig, lv, ops, pending):
+        """From the recorded level ``lv`` (its records ``ops``, its _Pending)."""
+        self.sig, self.gen, self.ops, self.pkey = sig, eng._gen, ops, lv.plan.pkey
+        self.pinned = eng._pinned[0]
+        self.host = self.pinned.numpy()
+        self.offs = dict(segs=lv.o_segs, csegs=lv.o_csegs, g=lv.o_g, jobs=lv.o_jobs, fb=lv.o_fb,
+                         isb=lv.o_isb)
+        self.history = lv.opts.history if lv.sorted_fit else None
+        self.tjobs = lv.tjobs
+        self.band_jobs, self.d_segs, self.stream = list(lv.band_jobs), lv.d_segs, lv.sp.value
         self.order = pending.order
-        self.nbytes, self.xoff, self.table = pending.nbytes, pending.xoff, pending.table
-        self.res_pin = res_pin
-        n = self.order.size
-        o = offs["jobs"]
-        self.jobs_view = self.host[o:o + n * L.JOB_DTYPE.itemsize].view(L.JOB_DTYPE)
+        # the readback of every re-issue (the recorded level's block; the job
+        # table, timer reader and band fix are set per call -- the previous
+        # call's _Pending has been collected by then, Engine._run_level)
+        rb = pending.rb
+        self.rb = _Readback(pin=rb.pin, nbytes=rb.nbytes, n_jobs=rb.n_jobs, table=rb.table,
+                            xbytes=rb.xbytes, xinfo=rb.xinfo)
+        o = self.offs["jobs"]
+        self.jobs_view = self.host[o:o + self.order.size * L.JOB_DTYPE.itemsize] \
+            .view(L.JOB_DTYPE)
         self.counts = None  # (n_below, n_above, rows) the staged pack holds
         self.hist_rows = None
         self.fix = None
-        self.xinfo = fix_args[4]
 
     @staticmethod
-    def signature(eng, works, prior_weight, lf, precision, outputs, stream, sample_only, pruned,
-                  scorer, posteriors, history, rows, is_below, histories, timers, timer_groups,
-                  table_scores, exchange):
-        if (history is None or rows is not None or histories is not None or outputs
-                or sample_only or posteriors or table_scores or stream is None
-                or not eng.native):
-            return None  # (stream: the caller's current stream handle; None: given explicitly)
+    def signature(eng, batch, opts, stream):
+        """``stream``: the caller's current stream handle (None: given explicitly)."""
+        history = opts.history
+        if (history is None or opts.rows is not None or opts.histories is not None or opts.hooks
+                or stream is None or not eng.native):
+            return None
+        scorer, exchange = opts.scorer, opts.exchange
         if scorer is None:
-            scorer = "auto" if pruned else "dense"
+            scorer = "auto" if opts.pruned else "dense"
         if exchange is not None:
             exchange = (int(exchange[0]), int(exchange[1]), int(exchange[2]),
                         np.asarray(exchange[3], np.int32).tobytes())
         # (the timer spec last: the rest is the staged pack's signature)
-        return (stream, works.key, float(prior_weight), int(lf), int(precision), scorer, pruned,
+        return (stream, batch.key, float(opts.prior_weight), int(opts.lf), int(opts.precision),
+                scorer, opts.pruned,
                 history.vals.data_ptr(), history.active.data_ptr(), history.ld,
                 exchange, eng.side_stream, eng.table_scorer, eng.exact64, eng.lat_prefix,
                 eng.cat_early, eng.cat_issue, eng.cat_hist, eng.lat_main, eng.lat_max_slots,
-                eng.device_events,
-                eng.sorted_fit, "off" if timers is None else
-                ("all" if timer_groups is None else frozenset(timer_groups)))
+                eng.device_events, eng.sorted_fit, opts.timer_spec())
 
     def _put(self, name, arr):
         off = self.offs[name]
         if off is not None and arr.size:
             self.host[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
 
-    def run(self, eng, batch, is_below, timers, defer):
+    def run(self, eng, batch, opts):
         """Re-issue the level for ``batch``; None when it cannot (the caller
         then runs the full path)."""
-        hm = eng.host_marks
-        if hm is not None:
-            hm.append(("start", time.perf_counter()))
-        isb = np.ascontiguousarray(is_below, dtype=np.uint8).reshape(-1)
+        eng._mark("start")
+        isb = np.ascontiguousarray(opts.is_below, dtype=np.uint8).reshape(-1)
         n_rows = isb.size
         counts = (batch.n_below.tobytes(), batch.n_above.tobytes(), n_rows)
         if counts == self.counts and (self.history is None or
@@ -2240,73 +2364,61 @@ class _Replay(object):
             self.jobs_view["key"] = batch.keys[oi]
             self.jobs_view["cand_base"] = batch.cand_base[oi]
             self._put("isb", isb)
-            return self._issue(eng, timers, defer, self.jobs_view, hm)
+            return self._issue(eng, opts, self.jobs_view)
         P = eng._plans.get(self.pkey)
         if P is None or self.pkey[-1] != eng._big64(self.pkey[4], batch.n_above):
             return None
-        (_, _, _, fit_ids, _, nf, segs, _, n_obs_total, n_comp, max_obs, csegs, _, _, _,
-         cobs_off, _, _, _, _, _, g_arr) = eng._plan_fast(P, batch.n_below, batch.n_above)
-        if hm is not None:
-            hm.append(("replay:plan_fast", time.perf_counter()))
-        jobs, _, fb_jobs = eng._jobs_fast(P, batch.keys, batch.cand_base)[:3]
-        if hm is not None:
-            hm.append(("replay:jobs", time.perf_counter()))
+        plan = eng._plan_fast(P, batch.n_below, batch.n_above)
+        eng._mark("replay:plan_fast")
+        eng._jobs_fast(P, plan, batch.keys, batch.cand_base)
+        segs, g_arr, jobs, max_obs = plan.segs, plan.g_arr, plan.jobs, plan.max_obs
+        eng._mark("replay:jobs")
         pack_size = self.offs["isb"] + max(n_rows, 1)
         gen0 = eng._gen
         if pack_size > self.pinned.numel():
             return None
         eng._buf("stage", pack_size)
-        eng._presize(n_comp, n_obs_total, max_obs, cobs_off, len(segs), self.tjobs,
-                     n_rows if self.history is not None else 0)
+        eng._presize(plan, self.tjobs, n_rows if self.history is not None else 0)
         if eng._gen != gen0:
             return None
-        if hm is not None:
-            hm.append(("replay:presize", time.perf_counter()))
+        eng._mark("replay:presize")
         if self.history is not None:  # rows appended since: merged into the sorted orders
-            nfs = 2 * nf
             self.history.ensure_order(eng, eng.torch.cuda.current_stream(eng.device),
-                                      g_arr["col"][:nfs:2], segs["transform"][::2],
+                                      g_arr["col"][:2 * plan.nf:2], segs["transform"][::2],
                                       segs["floor"][::2])
-        if hm is not None:
-            hm.append(("replay:order", time.perf_counter()))
-        for name, arr in (("segs", segs), ("csegs", csegs), ("g", g_arr), ("jobs", jobs),
-                          ("fb", fb_jobs), ("isb", isb)):
+        eng._mark("replay:order")
+        for name, arr in (("segs", segs), ("csegs", plan.csegs), ("g", g_arr), ("jobs", jobs),
+                          ("fb", plan.fb_jobs), ("isb", isb)):
             self._put(name, arr)
-        keep = self.ops.keep  # the host copies the entry points validate
-        keep[0][...] = jobs
-        keep[1][...] = fb_jobs
-        if keep[2] is not None:
-            keep[2][...] = g_arr
-        self.ops.set_sizes(dict(n_rows=n_rows, max_obs=max_obs, n_obs_total=n_obs_total,
-                                max_comp=max_obs + 1, pack_size=pack_size))
+        self.ops.refill(plan, dict(n_rows=n_rows, max_obs=max_obs, n_obs_total=plan.n_obs_total,
+                                   max_comp=max_obs + 1, pack_size=pack_size))
         self.counts = counts
         self.hist_rows = self.history.rows if self.history is not None else None
-        band_jobs, d_segs, stream, exchanged, self.xinfo = self.fix_args
         self.fix = None
-        if band_jobs:
-            self.fix = functools.partial(eng._band_fix, band_jobs, d_segs, max_obs + 1, n_comp,
-                                         stream, exchanged)
-        return self._issue(eng, timers, defer, jobs, hm)
+        if self.band_jobs:
+            self.fix = functools.partial(eng._band_fix, self.band_jobs, self.d_segs, max_obs + 1,
+                                         plan.n_comp, self.stream)
+        return self._issue(eng, opts, jobs)
 
-    def _issue(self, eng, timers, defer, jobs, hm):
-        if hm is not None:
-            hm.append(("plan", time.perf_counter()))
+    def _issue(self, eng, opts, jobs):
+        eng._mark("plan")
         try:
             self.ops.issue(eng)
         except L.TpeHipError:
             eng._replays.clear()
             raise
-        if hm is not None:
-            hm.append(("score launches", time.perf_counter()))
+        eng._mark("score launches")
         eng.graph_stats["native"] = eng.graph_stats.get("native", 0) + 1
         eng.graph_stats["replay"] = eng.graph_stats.get("replay", 0) + 1
         after = None
-        if self.ops.timed and timers is not None:
-            after = functools.partial(self.ops.read_timers, eng._hip, timers)
-        p = eng._inflight = _Pending(eng, eng._event("result"), self.res_pin, self.nbytes,
-                                     self.order, self.xoff, self.table, after, self.fix, jobs,
-                                     self.xinfo)
-        return p if defer else p.result()
+        if self.ops.timed and opts.timers is not None:
+            after = functools.partial(self.ops.read_timers, eng._hip, opts.timers)
+        rb = self.rb
+        rb.jobs, rb.after, rb.fix = jobs, after, self.fix
+        p = eng._inflight = _Pending(eng, eng._event("result"), self.order, rb)
+        return p if opts.defer else p.result()
+
+
 
 
 class _Timed(object):
@@ -2372,6 +2484,7 @@ class _OpList(_Timing):
         self.timed = []
         self.events = []
         self.table_calls = []
+        self.band_jobs = []
         self.keep = self.arr = None
         self.ptr = self.n = 0
         # the records as a hipGraph (Engine.graphs): the graph of records
@@ -2429,11 +2542,18 @@ class _OpList(_Timing):
         self.arr, self.keep, self.rows = arr, keep, None
         self.ptr, self.n = arr.ctypes.data, len(arr)
 
-    def set_sizes(self, values):
-        """Rewrite the size words of the records (names of _V arguments)."""
+    def refill(self, plan, values):
+        """This call's size words of the records (``values`` by the names of
+        their _V arguments) and host tables (the copies the entry points
+        validate: jobs, fallback jobs, the gather table)."""
         a = self.arr["a"]
         for i, j, name in self.sizes:
             a[i, j] = values[name]
+        keep = self.keep
+        keep[0][...] = plan.jobs
+        keep[1][...] = plan.fb_jobs
+        if keep[2] is not None:
+            keep[2][...] = plan.g_arr
 
     def issue(self, eng):
         """Issue the records (one tpe_run_ops call), or replay them as a

@@ -268,9 +268,9 @@ def test_plan_key_rules():
     hashable structure only; injected candidates, per-candidate outputs, the
     sampler hook and upload mode always plan from scratch; the key follows
     kinds, arguments, candidate counts and columns but not the Philox keys."""
-    from hyperopt_amd.engine import Engine, LabelWork
+    from hyperopt_amd.engine import Engine, LabelWork, _LevelOpts
     eng = Engine.__new__(Engine)  # key logic only: no device state
-    eng._plans = {}
+    eng._init_host_state()
 
     def work(**kw):
         base = dict(label="u", kind="uniform", args=(-5.0, 5.0), obs_below=np.zeros(3),
@@ -278,8 +278,10 @@ def test_plan_key_rules():
         base.update(kw)
         return LabelWork(**base)
 
-    k = lambda ws, **o: eng._plan_key(ws, 1.0, 25, 32, "auto", o.get("outputs", False),  # noqa
-                                      o.get("sample_only", False), o.get("hist", True), False)
+    k = lambda ws, **o: eng._plan_key(ws, _LevelOpts(  # noqa
+        1.0, 25, 32, scorer="auto", outputs=o.get("outputs", False),
+        sample_only=o.get("sample_only", False),
+        history=object() if o.get("hist", True) else None))
     assert k([work()]) is not None
     assert k([work()]) == k([work(key=99, cand_base=7, n_above=9, obs_below=np.ones(5))])
     assert k([work()]) != k([work(n_cand=48)])

@@ -5,7 +5,7 @@ launch entry points do nothing; size queries use the real library), so what
 is timed is exactly the Python / numpy / ctypes work of a step -- the part
 of a level during which the GPU waits.
 
-    python tools/host_cpu_profile.py [world=1] [rank=0] [--cprofile]
+    python tools/host_cpu_profile.py [world=1] [rank=0] [--cprofile] [--append] [--marks]
 """
 import cProfile
 import ctypes
@@ -86,35 +86,18 @@ class _Lib(object):
 
 
 def make_engine():
+    """An engine on the stand-ins: Engine._init_host_state gives it every
+    device-free attribute (switches follow the TPE_* variables only with
+    TPE_DIAG=1, as in the product); the shim torch, the stub runtime and
+    library, and the CPU device are put in here."""
     eng = E.Engine.__new__(E.Engine)
     shim = _torch_shim()
     eng.torch = shim
     eng.lib = _Lib(L.load())
     eng.device = torch.device("cpu")
-    eng._bufs, eng._plans, eng._retired, eng._pinned = {}, {}, [], {}
-    eng._res_pin = eng._inflight = None
-    eng._events = {}
     eng._hip = _Hip()
-    eng.host_marks = None
-    eng.side_stream = os.environ.get("TPE_SIDE_STREAM", "1")
-    eng._side = None
-    eng.table_scorer = "cubic"
-    eng.exact64 = "auto"
-    eng.cat_early = os.environ.get("TPE_CAT_EARLY", "1") == "1"
-    eng.cat_issue = os.environ.get("TPE_CAT_ISSUE", "post")
-    eng.cat_hist = os.environ.get("TPE_CAT_HIST", "1") == "1"
-    eng.cat_chunked = True
-    eng.lat_main = os.environ.get("TPE_LAT_MAIN", "1") == "1"
-    eng.lat_max_slots = E.LAT_SUGGEST_MAX_SLOTS
-    eng.lat_prefix = int(os.environ.get("TPE_LAT_PREFIX", str(E.LAT_PREFIX)))
-    eng.device_events = True
-    eng.sorted_fit = os.environ.get("TPE_SORTED_FIT", "1") == "1"
-    eng._last_gkey, eng._gen = None, 0
-    eng.graph_stats = {"eager": 0}
-    eng.native = os.environ.get("TPE_NATIVE_LAUNCH", "1") != "0"
-    eng.graphs = os.environ.get("TPE_GRAPHS", "0") == "1"
+    eng._init_host_state()
     eng._cap_stream = _Stream()
-    eng._oplists, eng._oplist_once, eng._replays, eng._staged_sig = {}, None, {}, None
     E.torch_shim = shim
     L.hip = lambda: eng._hip  # (DeviceHistory.append's event calls)
     return eng
