@@ -1,30 +1,64 @@
 // tpe_common.hpp -- device helpers shared by the TPE kernels (gfx950 / CDNA4).
 //
-// Wave64 everywhere: reductions use 64-lane butterflies, block sizes are
-// multiples of 64.  Nothing here is CUDA-shaped; there is one code path.
+// Wave64 everywhere: reductions use 64-lane butterflies (tpe_wave.hpp), block
+// sizes are multiples of 64.  Nothing here is CUDA-shaped; there is one code
+// path.  The host section holds what the C-ABI entry points share: error
+// reporting, job-list validation and launch-shape helpers (tpe_util.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/tpe_hip.h"
+#include "tpe_wave.hpp"
 
 namespace tpe {
 
 constexpr double kEps = 1e-12;  // hyperopt/tpe.py:32
-constexpr int kWave = 64;
 constexpr double kSqrt2 = 1.4142135623730951;
 constexpr double kTwoPi = 6.283185307179586;  // 2 * np.pi, as the reference forms it
 constexpr double kLog2e = 1.4426950408889634;
 constexpr double kLn2 = 0.6931471805599453;
 
 // ---------------------------------------------------------------------------
-// host-side error reporting
+// host side (tpe_util.hip): error reporting, then what the entry points share.
+// `fn` is the entry point's name, the prefix of its messages; the checks set
+// the error and return false.
 // ---------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 void defer_launch_checks(bool on);
+
+// n in [0, 65535], host_jobs given, no negative candidate count
+bool check_jobs(const char* fn, const tpe_job* hj, int n);
+// job i is an unquantized GMM1/LGMM1 job (kJobSampled: and not injected)
+enum { kJobTable = 1, kJobSampled = 2 };
+bool check_gmm_job(const char* fn, int i, const tpe_job& j, int want);
+// a list of at most max_jobs such jobs, all injected or all sampled (*inj);
+// kJobTable: each with a cell table
+bool check_gmm_jobs(const char* fn, const tpe_job* hj, int n, int max_jobs, int want, bool* inj);
+// the partial workspace holds `need` entries
+bool check_partials(const char* fn, int64_t n_partial, int64_t need);
+// blocks (tiles of per_block candidates) of the largest job, at least 1: the
+// x extent of a scorer's grid and of its partial layout
+int64_t tiles_per_job(const tpe_job* hj, int n, int64_t per_block);
+// 1-D grid of gx * n_jobs work items padded to a multiple of the 8 XCDs (the
+// kernels map blocks to work items XCD by XCD), with `extra` blocks after it;
+// -1 (error set) when it does not fit a launch
+int64_t xcd_grid(const char* fn, int64_t gx, int n_jobs, int64_t extra = 0);
+// one block per job: best[j] = np.argmax over its nper partials (k_reduce,
+// tpe_band.hip)
+void launch_reduce(const tpe_job* jobs, const tpe_best* partial, int64_t nper, tpe_best* best,
+                   int n_jobs, hipStream_t st);
+// f(std::bool_constant<b>): a launch's argument list written once for both
+// instantiations of a kernel's bool template parameter
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---------------------------------------------------------------------------
 // Philox4x32-10 (counter-based; one call = 4 independent 32-bit words)
@@ -33,7 +67,7 @@ struct U4 {
   uint32_t x, y, z, w;
 };
 
-#ifndef TPE_PHILOX_ROUNDS  // diagnostic builds only (tools/diag_variants.sh): 10 in the product
+#ifndef TPE_PHILOX_ROUNDS  // diagnostic builds only (tools/probes/diag_variants.sh): 10 in the product
 #define TPE_PHILOX_ROUNDS 10
 #endif
 __device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
@@ -157,34 +191,6 @@ __device__ __forceinline__ BestT block_best(BestT b, BestT* sh) {
   return r;
 }
 
-template <int BS, typename T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  T r = sh[0];
-#pragma unroll
-  for (int k = 1; k < BS / kWave; ++k) r += sh[k];
-  return r;
-}
-
-template <int BS, typename T>
-__device__ __forceinline__ T block_max(T v, T* sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  T r = sh[0];
-#pragma unroll
-  for (int k = 1; k < BS / kWave; ++k) r = fmax(r, sh[k]);
-  return r;
-}
-
 // ---------------------------------------------------------------------------
 // numpy-exact arithmetic helpers (no FMA contraction where numpy has none)
 // ---------------------------------------------------------------------------
@@ -232,9 +238,6 @@ __device__ __forceinline__ double obs_transform(double v, int transform, double 
   }
   return v;
 }
-
-// float -> ordered position inside a 64-lane wave's work split
-__device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
 // the fit's bandwidth / coefficient launches (tpe_parzen.hip), shared by
 // tpe_parzen_fit and tpe_fit_sorted

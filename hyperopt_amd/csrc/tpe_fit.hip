@@ -102,27 +102,6 @@ constexpr int kCatList = 1024;  // weights buffered per wave before a fold
 // on LF ramps, dyadic tie-heavy weights and 24-decade ranges:
 // tests/test_seq_fold.py restates it on the host; the GPU tests compare the
 // counts with np.bincount's.)
-// wave scans by DPP (row shifts, then the row broadcasts of 15 and 31):
-// lanes whose source is outside the wave keep `old`, the scan's identity
-template <int CTRL, int ROWM>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, ROWM, 0xF, false);
-}
-template <int CTRL, int ROWM>
-__device__ __forceinline__ void scan_step_u64(uint64_t& v) {
-  const uint32_t lo = dpp_u32<CTRL, ROWM>(0u, (uint32_t)v);
-  const uint32_t hi = dpp_u32<CTRL, ROWM>(0u, (uint32_t)(v >> 32));
-  v += ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_incl_sum_u64(uint64_t v) {
-  scan_step_u64<0x111, 0xF>(v);  // row_shr:1
-  scan_step_u64<0x112, 0xF>(v);  // row_shr:2
-  scan_step_u64<0x114, 0xF>(v);  // row_shr:4
-  scan_step_u64<0x118, 0xF>(v);  // row_shr:8
-  scan_step_u64<0x142, 0xA>(v);  // row_bcast:15 -> rows 1, 3
-  scan_step_u64<0x143, 0xC>(v);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
 // parity maps P -> a P ^ c packed as a | c << 1; y (earlier) then x
 __device__ __forceinline__ uint32_t map_then(uint32_t y, uint32_t x) {
   const uint32_t a2 = x & 1u, c2 = (x >> 1) & 1u;
@@ -237,7 +216,7 @@ __device__ double seq_fold(double S, const double* list, int n, int lane) {
       }
       tot += d[j];
     }
-    const uint64_t incl = wave_incl_sum_u64(tot);
+    const uint64_t incl = wave_prefix_sum_u64(tot);
     // the first step leaving the binade
     uint64_t cum = incl - tot;
     int jc = -1;
@@ -787,7 +766,7 @@ __device__ double block_seq_fold(double S, const double* list, int n, FoldX& X) 
       }
       tot += d[j];
     }
-    const uint64_t incl = wave_incl_sum_u64(tot);
+    const uint64_t incl = wave_prefix_sum_u64(tot);
     if (lane == kWave - 1) X.wsum[wid] = incl;
     __syncthreads();
     // the waves' increment totals: before this wave, and all of them

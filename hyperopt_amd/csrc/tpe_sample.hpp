@@ -148,7 +148,7 @@ __device__ __forceinline__ int comp_of(const Mix& M, uint32_t word) {
 // reads and costs ~35 VGPRs, which lost more (occupancy) than the branches.
 __device__ __forceinline__ void comp_res(const Mix& M, uint32_t word, float& mu, float& sg,
                                          float& res) {
-#ifdef TPE_DIAG_NO_COMP  // diagnostic builds only (tools/diag_variants.sh)
+#ifdef TPE_DIAG_NO_COMP  // diagnostic builds only (tools/probes/diag_variants.sh)
   const float4 c = M.cw ? M.cw[word & 7] : make_float4(0.0f, 1.0f, 0.0f, 0x1.0p-32f);
   mu = c.x;
   sg = c.y;
@@ -291,6 +291,10 @@ __device__ __forceinline__ float draw32(const Mix& M, uint64_t key, int64_t g, b
 // through `wstage`, the wave's R*64 floats of LDS (slot r of lane l at
 // r*64 + l).
 constexpr int kRetryList = 256;  // listed rejections per wave (uint16 entries)
+#ifndef TPE_LATR
+#define TPE_LATR 16
+#endif
+constexpr int kLatR = TPE_LATR;  // lattice sampler and tpe_sample: candidates per thread
 
 template <int R>
 __device__ __forceinline__ void draw32_pairs(const Mix& M, uint64_t key, int64_t g0, int n,

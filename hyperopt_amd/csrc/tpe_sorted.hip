@@ -250,31 +250,6 @@ __global__ __launch_bounds__(kCB) void k_fit_count(
   }
 }
 
-// exclusive block scan of one int per thread (sh: >= kCB / kWave ints,
-// reusable after the call); total: the block's sum
-__device__ __forceinline__ int block_excl_sum(int v, int* sh, int& total) {
-  constexpr int kNW = kCB / kWave;
-  const int lane = lane_id(), wid = threadIdx.x / kWave;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int x = __shfl_up(incl, o, kWave);
-    if (lane >= o) incl += x;
-  }
-  __syncthreads();
-  if (lane == kWave - 1) sh[wid] = incl;
-  __syncthreads();
-  int pos = incl - v;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kNW; ++w) {
-    pos += w < wid ? sh[w] : 0;
-    total += sh[w];
-  }
-  __syncthreads();
-  return pos;
-}
-
 // columns of up to kPreChunks chunks (4M rows) take the chunk bases from LDS
 // in K3; longer ones globalize the words first (K2)
 constexpr int kPreChunks = 4096;
@@ -340,7 +315,7 @@ __global__ __launch_bounds__(kCB) void k_fit_emit_sorted(
       const int q = q0 + (int)threadIdx.x;
       const int c = q < nch ? C[q * kCnt] : 0;
       int total;
-      const int ex = block_excl_sum(c, sh, total);
+      const int ex = block_excl_sum<kCB>(c, sh, total);
       if (q < nch) s_pre[q] = carry + ex;
       carry += total;
     }

@@ -1,4 +1,4 @@
-// tpe_util.hip -- error reporting shared by every C-ABI entry point.
+// tpe_util.hip -- error reporting, job checks and launch shapes of the C-ABI entry points.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -34,6 +34,78 @@ int check_launch(const char* what) {
     return TPE_E_LAUNCH;
   }
   return TPE_OK;
+}
+
+// ---- job-list validation and launch shapes shared by the entry points ------
+bool check_jobs(const char* fn, const tpe_job* hj, int n) {
+  if (n < 0 || n > 65535) {
+    set_error("%s: n_jobs=%d outside [0, 65535]", fn, n);
+    return false;
+  }
+  if (n > 0 && !hj) {
+    set_error("%s: host_jobs is NULL", fn);
+    return false;
+  }
+  for (int i = 0; i < n; ++i)
+    if (hj[i].n_cand < 0) {
+      set_error("%s: job %d has n_cand < 0", fn, i);
+      return false;
+    }
+  return true;
+}
+
+bool check_gmm_job(const char* fn, int i, const tpe_job& j, int want) {
+  const bool sampled = want & kJobSampled;
+  if (j.family == TPE_CAT || (j.flags & TPE_F_QUANT) || j.n_cand < 0 ||
+      (sampled && (j.flags & TPE_F_INJECTED))) {
+    set_error("%s: job %d is not %s unquantized GMM1/LGMM1 job", fn, i,
+              sampled ? "a sampled" : "an");
+    return false;
+  }
+  return true;
+}
+
+bool check_gmm_jobs(const char* fn, const tpe_job* hj, int n, int max_jobs, int want, bool* inj) {
+  if (n < 0 || n > max_jobs || (n > 0 && !hj)) {
+    set_error("%s: bad job list (n_jobs=%d)", fn, n);
+    return false;
+  }
+  for (int i = 0; i < n; ++i) {
+    const tpe_job& j = hj[i];
+    if (!check_gmm_job(fn, i, j, want)) return false;
+    if ((want & kJobTable) && (j.tbl_cap < 1 || j.tbl_off < 0)) {
+      set_error("%s: job %d has no cell table (tbl_cap=%lld)", fn, i, (long long)j.tbl_cap);
+      return false;
+    }
+    const bool ji = (j.flags & TPE_F_INJECTED) != 0;
+    if (i > 0 && ji != *inj) {
+      set_error("%s: mixed injected / sampled jobs in one call", fn);
+      return false;
+    }
+    *inj = ji;
+  }
+  return true;
+}
+
+bool check_partials(const char* fn, int64_t n_partial, int64_t need) {
+  if (need <= n_partial) return true;
+  set_error("%s: partial workspace %lld < %lld", fn, (long long)n_partial, (long long)need);
+  return false;
+}
+
+int64_t tiles_per_job(const tpe_job* hj, int n, int64_t per_block) {
+  int64_t g = 1;
+  for (int i = 0; i < n; ++i) g = std::max(g, (hj[i].n_cand + per_block - 1) / per_block);
+  return g;
+}
+
+int64_t xcd_grid(const char* fn, int64_t gx, int n_jobs, int64_t extra) {
+  const int64_t per = (gx * n_jobs + 7) / 8;
+  if (gx > INT32_MAX || 8 * per + extra > INT32_MAX) {
+    set_error("%s: %lld work items", fn, (long long)(gx * n_jobs));
+    return -1;
+  }
+  return 8 * per;
 }
 }  // namespace tpe
 

@@ -2,7 +2,7 @@
 (tools only: sizes the grid and the build's (component, cell) work under
 alternative rules before they are written as kernels).
 
-Replicates k_table_plan1/2 + grid_of (tpe_table.hip): the global floor T
+Replicates k_table_plan1/2 + grid_of (tpe_table.hip, tpe_table.hpp): the global floor T
 (prior's smallest term over the range - log M - tau), per-component
 admissible half-width (9|A| + 65|B| <= 5.8), uniform grid h = min over both
 mixtures; then the build's per-cell items (reach window + wide list) and the

@@ -1,4 +1,4 @@
-"""Worst-case error bounds of the cell-table expansion (tpe_table.hip header).
+"""Worst-case error bounds of the cell-table expansion (tpe_table.hpp header).
 
 For one component, exp(A u + B u^2) = sum_n c_n u^n with |c_n| <= c~_n, the
 coefficients of exp(|A| u + |B| u^2) (same recurrence, all terms positive).
