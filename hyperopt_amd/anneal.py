@@ -38,7 +38,9 @@ import ctypes
 import numpy as np
 
 from . import rand
-from .base import as_domain, doc_loss, foreign_columnar
+from .base import as_domain, doc_loss
+from .walk import (decode, docs_matrix, idxs_vals, next_level, trial_docs, trials_columnar,
+                   walk)
 
 _default_avg_best_idx = 2.0
 _default_shrink_coef = 0.1
@@ -52,13 +54,7 @@ _NORMAL_KINDS = ("normal", "qnormal", "lognormal", "qlognormal")
 # ---------------------------------------------------------------------------
 def _columnar(domain, trials):
     """(docs, columnar cache or None) of ``trials`` for the domain's labels."""
-    labels = tuple(domain.params)
-    docs = trials.trials
-    if hasattr(trials, "columnar"):
-        return docs, trials.columnar(labels)
-    if not isinstance(docs, list):
-        docs = list(docs)
-    return docs, foreign_columnar(trials, docs, labels)
+    return trials_columnar(trials, tuple(domain.params))
 
 
 def _cache_is_history(docs, col):
@@ -83,17 +79,9 @@ class _HostHistory(object):
             for doc in docs:
                 by_tid[doc["tid"]] = doc
             tids = sorted(by_tid)
-            index = {lab: j for j, lab in enumerate(self.labels)}
             self.tids = np.asarray(tids, dtype=np.int64)
             self.losses = np.array([doc_loss(by_tid[t]) for t in tids], dtype=np.float64)
-            self.vals = np.full((len(tids), len(self.labels)), np.nan)
-            self.active = np.zeros((len(tids), len(self.labels)), bool)
-            for r, t in enumerate(tids):
-                for lab, vv in by_tid[t]["misc"]["vals"].items():
-                    j = index.get(lab)
-                    if j is not None and len(vv):
-                        self.vals[r, j] = float(vv[0])
-                        self.active[r, j] = True
+            self.vals, self.active = docs_matrix([by_tid[t] for t in tids], self.labels)
         self._rows, self._order = {}, {}
 
     def rows(self, j):
@@ -161,28 +149,23 @@ def _host_config(domain, hist, new_id, seed, avg_best_idx, shrink_coef, trace=No
     rng = np.random.RandomState(seed + new_id)
     col = {lab: j for j, lab in enumerate(hist.labels)}
     best_rows = []
-    decided = {}
-    while True:
-        live = domain.reachable(decided)
-        todo = [lab for lab in live if lab not in decided]
-        if not todo:
-            break
-        for lab in todo:
-            spec, j = domain.specs[lab], col[lab]
-            T = hist.rows(j).size
-            if T == 0:
-                decided[lab] = spec.sample(rng)
-                continue
-            row = next((r for r in best_rows if hist.active[r, j]), None)
-            if row is None:
-                g = rng.geometric(1.0 / avg_best_idx) - 1
-                row = int(hist.ranked(j)[int(np.clip(g, 0, T - 1))])
-                best_rows.append(row)
-            shrink = 1.0 / (1.0 + T * shrink_coef)
-            decided[lab] = _host_draw(spec, hist.vals[row, j], shrink, rng)
+
+    def choose(lab):
+        spec, j = domain.specs[lab], col[lab]
+        T = hist.rows(j).size
+        if T == 0:
+            return spec.sample(rng)
+        row = next((r for r in best_rows if hist.active[r, j]), None)
+        if row is None:
+            g = rng.geometric(1.0 / avg_best_idx) - 1
+            row = int(hist.ranked(j)[int(np.clip(g, 0, T - 1))])
+            best_rows.append(row)
+        shrink = 1.0 / (1.0 + T * shrink_coef)
+        return _host_draw(spec, hist.vals[row, j], shrink, rng)
+    config = walk(domain, choose)
     if trace is not None:
         trace.append([int(hist.tids[r]) for r in best_rows])
-    return {lab: decided[lab] for lab in live}
+    return config
 
 
 def _host_configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef, trace=None):
@@ -190,24 +173,6 @@ def _host_configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef, trac
     hist = _HostHistory(domain, docs, col)
     return [_host_config(domain, hist, new_id, seed, avg_best_idx, shrink_coef, trace)
             for new_id in new_ids]
-
-
-def _docs(new_ids, domain, trials, configs):
-    rval = []
-    for new_id, config in zip(new_ids, configs):
-        rval.extend(trials.new_trial_docs([new_id], [None], [domain.new_result()],
-                                          [rand._misc(domain, new_id, config)]))
-    return rval
-
-
-def _idxs_vals(new_ids, domain, configs):
-    idxs = {lab: [] for lab in domain.params}
-    vals = {lab: [] for lab in domain.params}
-    for new_id, config in zip(new_ids, configs):
-        for lab, v in config.items():
-            idxs[lab].append(new_id)
-            vals[lab].append(v)
-    return idxs, vals
 
 
 def suggest_host(new_ids, domain, trials, seed, avg_best_idx=_default_avg_best_idx,
@@ -218,8 +183,8 @@ def suggest_host(new_ids, domain, trials, seed, avg_best_idx=_default_avg_best_i
     the value's sampler)."""
     domain = as_domain(domain)
     new_ids = list(new_ids)
-    return _docs(new_ids, domain, trials,
-                 _host_configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))
+    return trial_docs(new_ids, domain, trials,
+                      _host_configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))
 
 
 # ---------------------------------------------------------------------------
@@ -266,15 +231,6 @@ def _device_losses(col, dh):
     st["rows"], st["final"] = n, col.n_final
     st["uploaded"] = n - start
     return st["loss"]
-
-
-def _level_items(domain, decided_all):
-    """Per trial, the labels of its next level (live and not yet decided)."""
-    out = []
-    for decided in decided_all:
-        live = domain.reachable(decided)
-        out.append([lab for lab in live if lab not in decided])
-    return out
 
 
 def sample_level(eng, dh, loss, rec, pool, items, new_ids, avg_best_idx, state, debug=False):
@@ -342,11 +298,11 @@ def _device_configs(new_ids, domain, col, seed, avg_best_idx, shrink_coef, trace
     loss = _device_losses(col, dh)
     labels, rec, pool = _records(domain, col, seed, shrink_coef)
     index = {lab: j for j, lab in enumerate(labels)}
-    ints = {lab for lab in labels if domain.specs[lab].kind in ("randint", "categorical")}
     state = chain_state(eng, dh, rec, pool, new_ids)
     decided_all = [{} for _ in new_ids]
-    while True:
-        todo = _level_items(domain, decided_all)
+    while True:  # one launch per level covers every trial's next level
+        levels = [next_level(domain, decided) for decided in decided_all]
+        todo = [level for _, level in levels]
         if not any(todo):
             break
         res = sample_level(eng, dh, loss, rec, pool, [[index[lab] for lab in it] for it in todo],
@@ -357,10 +313,9 @@ def _device_configs(new_ids, domain, col, seed, avg_best_idx, shrink_coef, trace
         k = 0
         for decided, it in zip(decided_all, todo):
             for lab in it:
-                v = vals[k]
-                decided[lab] = int(round(v)) if lab in ints else float(v)
+                decided[lab] = decode(domain.specs[lab], vals[k], offset=False)[0]
                 k += 1
-    return [{lab: decided[lab] for lab in domain.reachable(decided)} for decided in decided_all]
+    return [{lab: decided[lab] for lab in live} for decided, (live, _) in zip(decided_all, levels)]
 
 
 def _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef):
@@ -368,9 +323,7 @@ def _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef):
         raise ValueError("avg_best_idx must be positive", avg_best_idx)
     docs, col = _columnar(domain, trials)
     if not _cache_is_history(docs, col):
-        hist = _HostHistory(domain, docs, col)
-        return [_host_config(domain, hist, new_id, seed, avg_best_idx, shrink_coef)
-                for new_id in new_ids]
+        return _host_configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef)
     return _device_configs(new_ids, domain, col, seed, avg_best_idx, shrink_coef)
 
 
@@ -385,8 +338,8 @@ def suggest(new_ids, domain, trials, seed, avg_best_idx=_default_avg_best_idx,
         number of observations."""
     domain = as_domain(domain)
     new_ids = list(new_ids)
-    return _docs(new_ids, domain, trials,
-                 _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))
+    return trial_docs(new_ids, domain, trials,
+                      _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))
 
 
 def suggest_batch(new_ids, domain, trials, seed, avg_best_idx=_default_avg_best_idx,
@@ -397,5 +350,5 @@ def suggest_batch(new_ids, domain, trials, seed, avg_best_idx=_default_avg_best_
     trials, is not reproduced: each trial of a batch is annealed on its own."""
     domain = as_domain(domain)
     new_ids = list(new_ids)
-    return _idxs_vals(new_ids, domain,
-                      _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))
+    return idxs_vals(new_ids, domain,
+                     _configs(new_ids, domain, trials, seed, avg_best_idx, shrink_coef))

@@ -19,47 +19,24 @@ import ctypes
 import numpy as np
 
 from .base import as_domain
+from .walk import decode, idxs_vals, trial_docs, walk
 
 
 def sample_config(domain, rng):
     """{label: value} for the labels live under the sampled choices."""
-    decided = {}
-    while True:
-        live = domain.reachable(decided)
-        todo = [lab for lab in live if lab not in decided]
-        if not todo:
-            return {lab: decided[lab] for lab in live}
-        for lab in todo:
-            decided[lab] = domain.specs[lab].sample(rng)
-
-
-def _misc(domain, new_id, config):
-    return dict(tid=new_id, cmd=domain.cmd, workdir=domain.workdir,
-                idxs={lab: ([new_id] if lab in config else []) for lab in domain.params},
-                vals={lab: ([config[lab]] if lab in config else []) for lab in domain.params})
+    return walk(domain, lambda lab: domain.specs[lab].sample(rng))
 
 
 def suggest(new_ids, domain, trials, seed):
     domain = as_domain(domain)
     rng = np.random.RandomState(seed)
-    rval = []
-    for new_id in new_ids:
-        config = sample_config(domain, rng)
-        rval.extend(trials.new_trial_docs([new_id], [None], [domain.new_result()],
-                                          [_misc(domain, new_id, config)]))
-    return rval
+    return trial_docs(new_ids, domain, trials, [sample_config(domain, rng) for _ in new_ids])
 
 
 def suggest_batch(new_ids, domain, trials, seed):
     domain = as_domain(domain)
     rng = np.random.RandomState(seed)
-    idxs = {lab: [] for lab in domain.params}
-    vals = {lab: [] for lab in domain.params}
-    for new_id in new_ids:
-        for lab, v in sample_config(domain, rng).items():
-            idxs[lab].append(new_id)
-            vals[lab].append(v)
-    return idxs, vals
+    return idxs_vals(new_ids, domain, [sample_config(domain, rng) for _ in new_ids])
 
 
 # ---------------------------------------------------------------------------
@@ -124,28 +101,13 @@ def draw_priors(domain, seed, n):
 def _configs(domain, labels, vals):
     """Per new trial, {label: value} of the labels its own choices make live."""
     col = {lab: j for j, lab in enumerate(labels)}
-    ints = {lab for lab in labels if domain.specs[lab].kind in ("randint", "categorical")}
-    out = []
-    for i in range(vals.shape[1]):
-        decided = {}
-        while True:
-            live = domain.reachable(decided)
-            todo = [lab for lab in live if lab not in decided]
-            if not todo:
-                break
-            for lab in todo:
-                v = vals[col[lab], i]
-                decided[lab] = int(round(v)) if lab in ints else float(v)
-        out.append({lab: decided[lab] for lab in live})
-    return out
+    specs = domain.specs
+    return [walk(domain, lambda lab: decode(specs[lab], vals[col[lab], i], offset=False)[0])
+            for i in range(vals.shape[1])]
 
 
 def suggest_device(new_ids, domain, trials, seed):
     """rand.suggest with the prior draws made on the GPU (see module doc)."""
     domain = as_domain(domain)
     labels, vals = draw_priors(domain, seed, len(new_ids))
-    rval = []
-    for new_id, config in zip(new_ids, _configs(domain, labels, vals)):
-        rval.extend(trials.new_trial_docs([new_id], [None], [domain.new_result()],
-                                          [_misc(domain, new_id, config)]))
-    return rval
+    return trial_docs(new_ids, domain, trials, _configs(domain, labels, vals))

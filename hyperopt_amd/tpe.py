@@ -38,9 +38,11 @@ import numpy as np
 from . import _lib as _L
 from . import dist as hdist
 from . import rand
-from .base import as_domain, doc_loss, foreign_columnar
-from .engine import (DEFAULT_LF, Engine, LabelResult, LabelWork, WorkBatch, _lattice_range,
-                     _params)
+from .base import as_domain, doc_loss
+from .engine import (DEFAULT_LF, TABLE_MIN_CAND, Engine, LabelResult, LabelWork, WorkBatch,
+                     _lattice_range, _params)
+from .walk import decode as _decode  # engine value -> (switch value, stored value)
+from .walk import decode_level, docs_matrix, int_offset, next_level, trial_docs, trials_columnar
 
 logger = logging.getLogger(__name__)
 
@@ -87,11 +89,15 @@ def _mix64(h):
     return h ^ (h >> 31)
 
 
+def _seed_word(seed):
+    """The suggest seed as the 64-bit word every label hash is mixed with."""
+    return _mix64((int(seed) * 0x9E3779B97F4A7C15 + 1) & 0xFFFFFFFFFFFFFFFF)
+
+
 def label_key(seed, label):
     """64-bit Philox key for (suggest seed, label): the label's FNV-1a hash
     xor the mixed seed, through a splitmix finaliser."""
-    return _mix64(_label_hash(label) ^ _mix64((int(seed) * 0x9E3779B97F4A7C15 + 1)
-                                             & 0xFFFFFFFFFFFFFFFF))
+    return _mix64(_label_hash(label) ^ _seed_word(seed))
 
 
 def _mix64_np(h):
@@ -113,7 +119,7 @@ def _label_hashes(labels):
 def label_keys_array(seed, labels):
     """label_key(seed, lab) for every label at once, as a uint64 array (uint64
     array arithmetic wraps like the masked Python integers)."""
-    s = np.uint64(_mix64((int(seed) * 0x9E3779B97F4A7C15 + 1) & 0xFFFFFFFFFFFFFFFF))
+    s = np.uint64(_seed_word(seed))
     try:
         h = _label_hashes(tuple(labels))
     except TypeError:  # unhashable labels
@@ -177,13 +183,7 @@ def collect_history(trials, labels):
     then ``if loss <= best_docs_loss[tid]`` -- so a tid whose first document
     has a NaN loss never gets a document and drops out of the history.
     """
-    docs = trials.trials
-    if hasattr(trials, "columnar"):
-        col = trials.columnar(labels)
-    else:  # the reference's Trials (fmin(algo=hyperopt_amd.tpe.suggest)): a cache beside it
-        if not isinstance(docs, list):
-            docs = list(docs)
-        col = foreign_columnar(trials, docs, labels)
+    docs, col = trials_columnar(trials, labels)
     n = len(docs)
     if col is not None and n == col.rows and col.keys_increasing:
         # trials.trials is every cached row (a filtered subsequence of
@@ -223,17 +223,7 @@ def walk_history(docs, labels, best=None):
     (tpe.py:874-896 + miscs_to_idxs_vals, base.py:200-214), no cache: the
     fallback of collect_history, and what its cached forms must equal."""
     tids, losses, obs_tids, bdocs = _best_docs(docs) if best is None else best
-    L = len(labels)
-    index = {lab: j for j, lab in enumerate(labels)}
-    vals = np.full((len(bdocs), L), np.nan)
-    active = np.zeros((len(bdocs), L), bool)
-    for r, d in enumerate(bdocs):
-        for lab, vv in d["misc"]["vals"].items():
-            j = index.get(lab)
-            if j is not None and len(vv):
-                vals[r, j] = float(vv[0])
-                active[r, j] = True
-    return History(tids, losses, obs_tids, vals, active)
+    return History(tids, losses, obs_tids, *docs_matrix(bdocs, labels))
 
 
 def split_masks(hist, gamma, gamma_cap=DEFAULT_LF):
@@ -273,7 +263,7 @@ def _smallest_rows(losses, n):
     return out
 
 
-FP32_MIN_CAND = 1 << 16  # engine.TABLE_MIN_CAND: the cell-table path's threshold
+FP32_MIN_CAND = TABLE_MIN_CAND  # the cell-table path's threshold
 
 
 def _precision(precision, n_ei, T):
@@ -289,18 +279,6 @@ def _precision(precision, n_ei, T):
     if precision not in (32, 64):
         raise ValueError("precision must be 32 or 64", precision)
     return precision
-
-
-def _decode(spec, value):
-    """Engine value -> (value used by switches, value stored in the trial)."""
-    if spec.kind == "randint":
-        k = int(round(value))
-        offset = int(spec.args[0]) if spec.args[1] is not None else 0
-        return k, k + offset  # tpe.py:945-948
-    if spec.kind == "categorical":
-        k = int(round(value))
-        return k, k
-    return float(value), float(value)
 
 
 def _addr(a):
@@ -394,46 +372,75 @@ class LevelInputs(object):
                          obs_below=v[act & self.isb], obs_above=v[act & self.isa], **kw)
 
 
-def suggest(new_ids, domain, trials, seed, prior_weight=_default_prior_weight,
-            n_startup_jobs=_default_n_startup_jobs, n_EI_candidates=_default_n_EI_candidates,
-            gamma=_default_gamma, verbose=True, linear_forgetting=_default_linear_forgetting,
-            precision=None):
-    """TPE suggest: one new trial document for new_ids[0] (tpe.py:837-964)."""
-    t0 = time.time()
-    domain = as_domain(domain)  # (hyperopt's own Domain too: fmin(algo=tpe.suggest))
-    labels = list(domain.params)
-    hist = collect_history(trials, labels)
+_DEFAULTS = dict(prior_weight=_default_prior_weight, n_startup_jobs=_default_n_startup_jobs,
+                 n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
+                 linear_forgetting=_default_linear_forgetting, precision=None)
+
+
+class _Study(object):
+    """One suggest call past its startup phase: the request (``qi``: its
+    position in a suggest_many), its options ``kw``, the history and the level
+    inputs, this rank's candidate range, and the walk so far."""
+    __slots__ = ("qi", "new_ids", "domain", "trials", "seed", "kw", "labels", "hist", "obs",
+                 "col", "walk", "stored", "live", "start", "count", "n_ei", "done", "prec")
+
+
+def _open_study(qi, new_ids, domain, trials, seed, kw, shard=None, verbose=False):
+    """(study, None) -- history collected, split and level inputs made -- or
+    (None, documents) while the history is shorter than ``n_startup_jobs``
+    (tpe.py:909-911, prior draws on the GPU).  ``shard``: (rank, world) when
+    the study's candidates are dealt over the ranks (dist.shard)."""
+    st = _Study()
+    st.qi, st.new_ids, st.trials, st.seed, st.kw = qi, new_ids, trials, seed, kw
+    st.domain = domain = as_domain(domain)  # (hyperopt's own Domain too: fmin(algo=tpe.suggest))
+    st.labels = labels = list(domain.params)
+    st.hist = hist = collect_history(trials, labels)
     if verbose:
         if hist.tids.size:
             logger.info("TPE using %i/%i trials with best loss %f" % (
                 hist.tids.size, len(trials), np.nanmin(hist.losses)))
         else:
             logger.info("TPE using 0 trials")
-    if hist.tids.size < n_startup_jobs:  # tpe.py:909-911, prior draws on the GPU
-        return rand.suggest_device(new_ids, domain, trials, seed)
-
-    first_new_id = new_ids[0]
-    prec = _precision(precision, n_EI_candidates, hist.tids.size)
-    rank, ws = hdist.world()
-    n_ei = max(int(n_EI_candidates), 0)
-    col = {lab: j for j, lab in enumerate(labels)}
-
-    walk, stored = {}, {}
-    live = []
+    if hist.tids.size < kw["n_startup_jobs"]:
+        return None, rand.suggest_device(new_ids, domain, trials, seed)
+    st.n_ei = n_ei = max(int(kw["n_EI_candidates"]), 0)
+    st.prec = _precision(kw["precision"], n_ei, hist.tids.size)
+    st.start, st.count = (0, n_ei) if shard is None else hdist.shard(n_ei, *shard)
+    st.col = {lab: j for j, lab in enumerate(labels)}
+    st.walk, st.stored, st.live, st.done, st.obs = {}, {}, [], n_ei == 0, None
     if n_ei > 0:
         eng = engine()
         hm = eng.host_marks  # (diagnostic phase marks, Engine.host_marks)
         if hm is not None:
             hm.append(("suggest:split", time.perf_counter()))
-        obs = LevelInputs.fast(hist, gamma, eng) if USE_DEVICE_HISTORY else None
-        if obs is None:
-            isb, isa = split_masks(hist, gamma)
-            obs = LevelInputs(hist, isb, isa, eng, device=USE_DEVICE_HISTORY)
+        st.obs = LevelInputs.fast(hist, kw["gamma"], eng) if USE_DEVICE_HISTORY else None
+        if st.obs is None:
+            isb, isa = split_masks(hist, kw["gamma"])
+            st.obs = LevelInputs(hist, isb, isa, eng, device=USE_DEVICE_HISTORY)
         if hm is not None:
             hm.append(("suggest:inputs", time.perf_counter()))
+    return st, None
+
+
+def suggest(new_ids, domain, trials, seed, prior_weight=_default_prior_weight,
+            n_startup_jobs=_default_n_startup_jobs, n_EI_candidates=_default_n_EI_candidates,
+            gamma=_default_gamma, verbose=True, linear_forgetting=_default_linear_forgetting,
+            precision=None):
+    """TPE suggest: one new trial document for new_ids[0] (tpe.py:837-964)."""
+    t0 = time.time()
+    st, docs = _open_study(0, new_ids, domain, trials, seed, dict(
+        prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
+        n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
+        precision=precision), verbose=verbose)
+    if st is None:
+        return docs
+    rank, ws = hdist.world()
+    domain, obs, n_ei = st.domain, st.obs, st.n_ei
+    if not st.done:
+        eng = engine()
+        hm = eng.host_marks
         while True:
-            live = domain.reachable(walk)
-            level = [lab for lab in live if lab not in walk]
+            st.live, level = next_level(domain, st.walk)
             if not level:
                 break
             # under torch.distributed this rank scores its units of the level
@@ -447,15 +454,10 @@ def suggest(new_ids, domain, trials, seed, prior_weight=_default_prior_weight,
             if not units:  # more ranks than shards of this level: nothing here, but
                 res = []   # the rank still joins the winners' all-gather below
             elif obs.device and _space_sig(domain) is not None:
-                res = _level_batch(eng, domain, obs, level, units, seed, n_ei, col,
-                                   prior_weight, linear_forgetting, prec, ws == 1)
+                res = _level_batch(eng, st, level, units, ws == 1)
             else:
-                keys = label_keys(seed, level)
-                works = [obs.work(level[i], domain.specs[level[i]], col[level[i]], n_cand=count,
-                                  key=keys[i], cand_base=start, n_total=n_ei)
-                         for i, start, count in units]
-                res = eng.run(works, prior_weight=prior_weight, lf=linear_forgetting,
-                              precision=prec, **obs.run_kwargs)
+                res = eng.run(_works(st, level, units), prior_weight=prior_weight,
+                              lf=linear_forgetting, precision=st.prec, **obs.run_kwargs)
             if ws > 1:
                 best = hdist.gather_best(len(level), [(u[0], r) for u, r in zip(units, res)])
                 values = [b[2] for b in best]
@@ -464,16 +466,13 @@ def suggest(new_ids, domain, trials, seed, prior_weight=_default_prior_weight,
             else:  # (_level_batch on one rank: the winners' values in level order)
                 values = res
             for lab, v in zip(level, values):
-                walk[lab], stored[lab] = _decode(domain.specs[lab], v)
+                st.walk[lab], st.stored[lab] = _decode(domain.specs[lab], v)
             if hm is not None:
                 hm.append(("suggest:decoded", time.perf_counter()))
-    live = set(live)
-    misc = {"tid": first_new_id, "cmd": domain.cmd, "workdir": domain.workdir,
-            "idxs": {lab: ([first_new_id] if lab in live else []) for lab in labels},
-            "vals": {lab: ([stored[lab]] if lab in live else []) for lab in labels}}
+    docs = trial_docs([new_ids[0]], domain, trials, [{lab: st.stored[lab] for lab in st.live}])
     if verbose:
         logger.info("tpe.suggest took %f seconds" % (time.time() - t0))
-    return trials.new_trial_docs([first_new_id], [None], [domain.new_result()], [misc])
+    return docs
 
 
 class SuggestRequest(object):
@@ -505,28 +504,25 @@ def _space_sig(domain):
     return d["_tpe_space_id"]
 
 
+def _decode_plan(domain, level):
+    """walk.decode_level's plan of a level: (label, walk.int_offset)."""
+    return [(lab, int_offset(domain.specs[lab])) for lab in level]
+
+
 class _Level(object):
     """What a level of a space needs per call, computed once: label columns,
-    FNV hashes (label_keys without the per-label Python), and the unbounded
-    quantized labels whose lattice range follows the below set."""
+    FNV hashes (label_keys without the per-label Python), the unbounded
+    quantized labels whose lattice range follows the below set, and the
+    decode plan."""
 
     def __init__(self, lid, domain, level):
         self.id = lid
         labels = list(domain.params)
         self.js = np.array([labels.index(lab) for lab in level], np.int64)
         self.h = np.fromiter((_label_hash(lab) for lab in level), np.uint64, len(level))
-        self.lat = []
-        for i, lab in enumerate(level):
-            spec = domain.specs[lab]
-            if spec.kind in ("qnormal", "qlognormal"):
-                self.lat.append((i, lab, spec))
-        # _decode as a plan: (label, 0 continuous / 1 integer, offset)
-        self.decode = []
-        for lab in level:
-            spec = domain.specs[lab]
-            off = int(spec.args[0]) if (spec.kind == "randint" and spec.args[1] is not None) \
-                else 0
-            self.decode.append((lab, 1 if spec.kind in ("randint", "categorical") else 0, off))
+        self.lat = [(i, lab, domain.specs[lab]) for i, lab in enumerate(level)
+                    if domain.specs[lab].kind in ("qnormal", "qlognormal")]
+        self.decode = _decode_plan(domain, level)
 
 
 def _level_info(domain, level):
@@ -552,14 +548,50 @@ def _zero_bases(n):
     return z
 
 
-def _level_batch(eng, domain, obs, level, units, seed, n_ei, col, pw, lf, prec, values=False):
+def _lat_ranges(lv, obs):
+    """The lattice ranges of a level's unbounded quantized labels under the
+    current below set (they are part of the WorkBatch key; callers skip the
+    call for a level without such labels)."""
+    return tuple(_lattice_range(obs.work(lab, spec, int(lv.js[i])), _params(spec.kind, spec.args))
+                 for i, lab, spec in lv.lat)
+
+
+def _works(st, level, units=None, hist=0):
+    """The LabelWork list of a study's level: one work per unit (label
+    position, candidate start, count), or with ``units`` None one per label
+    over the study's own candidate range; ``hist``: the study's place in
+    Engine.run's ``histories``."""
+    if units is None:
+        units = [(i, st.start, st.count) for i in range(len(level))]
+    keys = label_keys(st.seed, level)
+    specs, col, obs = st.domain.specs, st.col, st.obs
+    out = []
+    for i, start, count in units:
+        w = obs.work(level[i], specs[level[i]], col[level[i]], n_cand=count, key=keys[i],
+                     cand_base=start, n_total=st.n_ei)
+        w.hist = hist
+        out.append(w)
+    return out
+
+
+def _split_levels(values, items):
+    """A batch's flat value list as one list per (study, level) item."""
+    out, a = [], 0
+    for _, level in items:
+        out.append(values[a:a + len(level)])
+        a += len(level)
+    return out
+
+
+def _level_batch(eng, st, level, units, values=False):
     """One study's level (this rank's units of it) as a WorkBatch on the
     device history: counts from the split, keys from the cached label hashes,
     a structure key of a few small ints -- LabelWork objects only the first
     time the structure is seen.  Returns one LabelResult per unit, or with
     ``values`` (one rank: every unit a whole label, in level order) just the
     winners' values."""
-    lv = _level_info(domain, level)
+    obs, n_ei = st.obs, st.n_ei
+    lv = _level_info(st.domain, level)
     whole = isinstance(units, tuple) and units is _whole_units(len(level), n_ei)
     if whole:  # (one rank: every label, in level order)
         idx = None
@@ -567,31 +599,32 @@ def _level_batch(eng, domain, obs, level, units, seed, n_ei, col, pw, lf, prec, 
     else:
         idx = np.fromiter((u[0] for u in units), np.int64, len(units))
         js = lv.js[idx]
-    lat = ()
-    if lv.lat:
-        lat = tuple(_lattice_range(obs.work(lab, spec, int(lv.js[i])),
-                                   _params(spec.kind, spec.args)) for i, lab, spec in lv.lat)
-    s = np.uint64(_mix64((int(seed) * 0x9E3779B97F4A7C15 + 1) & 0xFFFFFFFFFFFFFFFF))
+    s = np.uint64(_seed_word(st.seed))
     with np.errstate(over="ignore"):
         keys = _mix64_np((lv.h if whole else lv.h[idx]) ^ s)
-
-    def materialize():
-        specs = domain.specs
-        return [obs.work(level[i], specs[level[i]], col[level[i]], n_cand=count,
-                         key=int(k), cand_base=start, n_total=n_ei)
-                for (i, start, count), k in zip(units, keys.tolist())]
     # (the key names the units: a token for the one-rank plan -- tuples do
     # not cache their hash, and this key is hashed a few times per call)
     batch = WorkBatch(("suggest", lv.id, ("whole", len(units)) if whole else tuple(units), n_ei,
-                       lat), obs.nb[js],
+                       _lat_ranges(lv, obs) if lv.lat else ()), obs.nb[js],
                       obs.n_above[js], keys,
-                      _zero_bases(len(units)) if whole else [u[1] for u in units], materialize)
-    r = eng.run(batch, prior_weight=pw, lf=lf, precision=prec, **obs.run_kwargs)
+                      _zero_bases(len(units)) if whole else [u[1] for u in units],
+                      lambda: _works(st, level, units))
+    r = eng.run(batch, prior_weight=st.kw["prior_weight"], lf=st.kw["linear_forgetting"],
+                precision=st.prec, **obs.run_kwargs)
     if values:
         return r.value.tolist()
     return [LabelResult(level[u[0]], ix, v, sc, ns) for u, ix, v, sc, ns in
             zip(units, r.index.tolist(), r.value.tolist(), r.score.tolist(),
                 r.n_scored.tolist())]
+
+
+def _histories(items):
+    """Engine.run's ``histories`` of a batch: one per study, in item order."""
+    out = []
+    for st, _ in items:
+        rk = st.obs.run_kwargs
+        out.append((rk["history"], rk["rows"], rk["is_below"]))
+    return out
 
 
 def _run_columnar(eng, items, pw, lf, prec, defer=False):
@@ -600,74 +633,41 @@ def _run_columnar(eng, items, pw, lf, prec, defer=False):
     LevelInputs, keys from cached hashes); LabelWork objects are only built
     the first time a batch structure is seen.  Returns the winners' values
     per item."""
-    hists, struct, nb, na, hh, ss, cb, sizes = [], [], [], [], [], [], [], []
+    struct, nb, na, hh, ss, cb, sizes = [], [], [], [], [], [], []
     for st, level in items:
-        obs = st["obs"]
-        rk = obs.run_kwargs
-        hists.append((rk["history"], rk["rows"], rk["is_below"]))
-        lv = _level_info(st["rq"].domain, level)
-        lat = ()
-        if lv.lat:
-            lat = tuple(_lattice_range(obs.work(lab, spec, int(lv.js[i])),
-                                       _params(spec.kind, spec.args)) for i, lab, spec in lv.lat)
-        struct.append((lv.id, st["count"], st["n_ei"], lat))
+        obs = st.obs
+        lv = _level_info(st.domain, level)
+        struct.append((lv.id, st.count, st.n_ei, _lat_ranges(lv, obs) if lv.lat else ()))
         nb.append(obs.nb[lv.js])
         na.append(obs.n_above[lv.js])
         hh.append(lv.h)
-        ss.append(_mix64((int(st["rq"].seed) * 0x9E3779B97F4A7C15 + 1) & 0xFFFFFFFFFFFFFFFF))
-        cb.append(st["start"])
+        ss.append(_seed_word(st.seed))
+        cb.append(st.start)
         sizes.append(len(level))
     sizes = np.asarray(sizes, np.int64)
     with np.errstate(over="ignore"):
         keys = _mix64_np(np.concatenate(hh) ^ np.repeat(np.asarray(ss, np.uint64), sizes))
 
     def materialize():
-        out = []
-        for h, (st, level) in enumerate(items):
-            specs, col = st["rq"].domain.specs, st["col"]
-            for lab, k in zip(level, label_keys(st["rq"].seed, level)):
-                w = st["obs"].work(lab, specs[lab], col[lab], n_cand=st["count"], key=k,
-                                   cand_base=st["start"], n_total=st["n_ei"])
-                w.hist = h
-                out.append(w)
-        return out
+        return [w for h, (st, level) in enumerate(items) for w in _works(st, level, hist=h)]
     batch = WorkBatch(tuple(struct), np.concatenate(nb), np.concatenate(na), keys,
                       np.repeat(np.asarray(cb, np.int64), sizes), materialize)
-    res = eng.run(batch, prior_weight=pw, lf=lf, precision=prec, histories=hists, defer=defer)
+    res = eng.run(batch, prior_weight=pw, lf=lf, precision=prec, histories=_histories(items),
+                  defer=defer)
     if defer:
         return res
-    vals = res.value.tolist()
-    out, a = [], 0
-    for n in sizes.tolist():
-        out.append(vals[a:a + n])
-        a += n
-    return out
+    return _split_levels(res.value.tolist(), items)
 
 
 def _run_works(eng, items, pw, lf, prec, dev, combine):
     """The general path: one LabelWork per label (host lists or histories),
     winners combined across ranks when the candidates are sharded."""
-    works, kw_run, hists = [], {}, []
-    for h, (st, level) in enumerate(items):
-        specs, col = st["rq"].domain.specs, st["col"]
-        for lab, k in zip(level, label_keys(st["rq"].seed, level)):
-            w = st["obs"].work(lab, specs[lab], col[lab], n_cand=st["count"], key=k,
-                               cand_base=st["start"], n_total=st["n_ei"])
-            w.hist = h
-            works.append(w)
-        if dev:  # one history per study of the batch
-            rk = st["obs"].run_kwargs
-            hists.append((rk["history"], rk["rows"], rk["is_below"]))
-    if dev:
-        kw_run["histories"] = hists
+    works = [w for h, (st, level) in enumerate(items) for w in _works(st, level, hist=h)]
+    kw_run = {"histories": _histories(items)} if dev else {}  # one history per study
     res = eng.run(works, prior_weight=pw, lf=lf, precision=prec, **kw_run)
     if combine:
         hdist.allreduce_best(res)
-    out, a = [], 0
-    for _, level in items:
-        out.append([r.value for r in res[a:a + len(level)]])
-        a += len(level)
-    return out
+    return _split_levels([r.value for r in res], items)
 
 
 def suggest_many(requests, shard_studies=False):
@@ -710,79 +710,51 @@ def _suggest_many(requests, shard_studies=False):
     pend = []  # launched batches not yet decoded: (items, values or _Pending)
     turn = itertools.count()
 
-    def make_state(qi, rq):
-        kw = dict(prior_weight=_default_prior_weight, n_startup_jobs=_default_n_startup_jobs,
-                  n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
-                  linear_forgetting=_default_linear_forgetting, precision=None)
-        kw.update({k: v for k, v in rq.kwargs.items() if k != "verbose"})
-        rq.domain = as_domain(rq.domain)
-        labels = list(rq.domain.params)
-        hist = collect_history(rq.trials, labels)
-        if hist.tids.size < kw["n_startup_jobs"]:
-            out[qi] = rand.suggest_device(rq.new_ids, rq.domain, rq.trials, rq.seed)
-            return None
-        n_ei = max(int(kw["n_EI_candidates"]), 0)
-        start, count = (0, n_ei) if (shard_studies or ws == 1) else hdist.shard(n_ei, rank, ws)
-        eng = engine() if n_ei > 0 else None
-        obs = LevelInputs.fast(hist, kw["gamma"], eng) if USE_DEVICE_HISTORY else None
-        if obs is None:
-            isb, isa = split_masks(hist, kw["gamma"])
-            obs = LevelInputs(hist, isb, isa, eng, device=USE_DEVICE_HISTORY)
-        return dict(qi=qi, rq=rq, kw=kw, labels=labels, hist=hist, obs=obs,
-                    col={lab: j for j, lab in enumerate(labels)}, walk={}, stored={},
-                    live=[], start=start, count=count, n_ei=n_ei, done=n_ei == 0,
-                    prec=_precision(kw["precision"], n_ei, hist.tids.size))
+    def open_chunk(reqs):
+        sts = []
+        for qi, rq in reqs:
+            kw = dict(_DEFAULTS)
+            kw.update({k: v for k, v in rq.kwargs.items() if k != "verbose"})
+            st, out[qi] = _open_study(qi, rq.new_ids, rq.domain, rq.trials, rq.seed, kw,
+                                      None if columnar else (rank, ws))
+            if st is not None:
+                sts.append(st)
+        return sts
 
     def finish(items, values):
         if not isinstance(values, list):
-            r = values.result().value.tolist()
-            values, a = [], 0
-            for _, level in items:
-                values.append(r[a:a + len(level)])
-                a += len(level)
+            values = _split_levels(values.result().value.tolist(), items)
         for (st, level), vals in zip(items, values):
-            walk, stored, dom = st["walk"], st["stored"], st["rq"].domain
-            if _space_sig(dom) is None:  # (no cached level plan for this space)
-                for lab, v in zip(level, vals):
-                    walk[lab], stored[lab] = _decode(dom.specs[lab], v)
-                continue
-            for (lab, mode, off), v in zip(_level_info(dom, level).decode, vals):
-                if mode == 0:  # a continuous label: the value itself
-                    walk[lab] = stored[lab] = float(v)
-                else:  # randint (offset re-applied, tpe.py:945-948) / categorical
-                    k = int(round(v))
-                    walk[lab], stored[lab] = k, k + off
+            plan = _level_info(st.domain, level).decode if _space_sig(st.domain) is not None \
+                else _decode_plan(st.domain, level)  # (no cached level plan for this space)
+            decode_level(plan, vals, st.walk, st.stored)
 
     # Level by level; within a level the studies go in chunks, each chunk's
     # batches launched without waiting (Engine.run defer=True, two engines
     # taking turns), so the host prepares chunk c+1 while chunk c runs.
     first = True
     while True:
-        src = todo if first else [st for st in states if not st["done"]]
+        src = todo if first else [st for st in states if not st.done]
         if not src:
             break
         for c0 in range(0, len(src), chunk):
             if first:
-                sts = [st for st in (make_state(qi, rq) for qi, rq in src[c0:c0 + chunk])
-                       if st is not None]
+                sts = open_chunk(src[c0:c0 + chunk])
                 states.extend(sts)
             else:
                 sts = src[c0:c0 + chunk]
-            batches = {}  # (prior_weight, lf, precision, device) -> [(state, level)]
+            batches = {}  # (prior_weight, lf, precision, device) -> [(study, level)]
             for st in sts:
-                if st["done"]:
+                if st.done:
                     continue
-                live = st["rq"].domain.reachable(st["walk"])
-                st["live"] = live
-                level = [lab for lab in live if lab not in st["walk"]]
+                st.live, level = next_level(st.domain, st.walk)
                 if not level:
-                    st["done"] = True
+                    st.done = True
                     continue
-                key = (st["kw"]["prior_weight"], st["kw"]["linear_forgetting"], st["prec"],
-                       st["obs"].device)
+                key = (st.kw["prior_weight"], st.kw["linear_forgetting"], st.prec, st.obs.device)
                 batches.setdefault(key, []).append((st, level))
             for (pw, lf, prec, dev), items in batches.items():
-                if dev and columnar and all(_space_sig(st["rq"].domain) is not None
+                if dev and columnar and all(_space_sig(st.domain) is not None
                                             for st, _ in items):
                     eng = engine(next(turn) % 2)
                     values = _run_columnar(eng, items, pw, lf, prec, defer=True)
@@ -796,12 +768,7 @@ def _suggest_many(requests, shard_studies=False):
             finish(*pend.pop(0))
         first = False
     for st in states:
-        rq, live = st["rq"], set(st["live"])
-        tid = rq.new_ids[0]
-        misc = {"tid": tid, "cmd": rq.domain.cmd, "workdir": rq.domain.workdir,
-                "idxs": {lab: ([tid] if lab in live else []) for lab in st["labels"]},
-                "vals": {lab: ([st["stored"][lab]] if lab in live else [])
-                         for lab in st["labels"]}}
-        out[st["qi"]] = rq.trials.new_trial_docs([tid], [None], [rq.domain.new_result()], [misc])
+        out[st.qi] = trial_docs([st.new_ids[0]], st.domain, st.trials,
+                                [{lab: st.stored[lab] for lab in st.live}])
     return out
 
