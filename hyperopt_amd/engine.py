@@ -81,6 +81,9 @@ class LabelWork:
     # scorer choice follows it, so every shard of a label runs the same
     # kernel and the winner does not depend on the number of ranks
     n_total: int = 0
+    # candidates already on the device (Engine.run(cand_ptr=...)): (first
+    # element, count, (min, max) of the finite values in the scoring coordinate)
+    cand_dev: Optional[tuple] = None
 
 
 class WorkBatch(object):
@@ -435,6 +438,8 @@ class _LevelOpts:
     table_scores: bool = False
     defer: bool = False
     exchange: Optional[tuple] = None
+    cand_ptr: int = 0
+    device_outputs: bool = False
 
     @property
     def hist_mode(self):
@@ -729,6 +734,11 @@ class Engine:
             self._gen += 1  # recorded levels hold the old pointers
         return t.data_ptr()
 
+    def device_output_ptrs(self):
+        """(out_bl, out_al): the per-candidate log-densities of the last
+        ``run(outputs=True, device_outputs=True)``, valid until the next run."""
+        return self._bufs["out_bl"].data_ptr(), self._bufs["out_al"].data_ptr()
+
     def _presize(self, plan, tjobs, n_rows):
         """Every workspace buffer whose size follows a level's per-call sizes
         (mixture pools, observation pools, fit / table scratch), grown here,
@@ -844,7 +854,8 @@ class Engine:
             return None
         parts = []
         for w in works:
-            if w.cand is not None or w.kind not in CONTINUOUS + CATEGORICAL:
+            if w.cand is not None or w.cand_dev is not None or \
+                    w.kind not in CONTINUOUS + CATEGORICAL:
                 return None
             lat = None
             if w.kind in CONTINUOUS and w.kind.startswith("q"):
@@ -1093,7 +1104,10 @@ class Engine:
         params, cat_meta = plan.params, plan.cat_meta
         precision, scorer, outputs = opts.precision, opts.scorer, opts.outputs
         # ---- jobs, ordered so every kernel call takes a contiguous slice -----------
-        inj = plan.inj = lambda i: works[i].cand is not None  # noqa: E731
+        inj = plan.inj = lambda i: (works[i].cand is not None or  # noqa: E731
+                                    works[i].cand_dev is not None)
+        n_inj = lambda w: (int(w.cand_dev[1]) if w.cand_dev is not None  # noqa: E731
+                           else int(np.asarray(w.cand).size))
         lat_ranges = plan.lat_ranges = {}
         fallback = plan.fallback = []
         for i in quant:
@@ -1111,8 +1125,7 @@ class Engine:
                 m = int(w.n_above) if w.obs_above is None else np.size(w.obs_above)
                 return "pruned64" if (self.exact64 == "pruned" or (
                     self.exact64 == "auto" and m >= PRUNED64_MIN_COMP)) else "cont"
-            n = int(np.asarray(works[i].cand).size) if inj(i) else \
-                int(works[i].n_total or works[i].n_cand)
+            n = n_inj(works[i]) if inj(i) else int(works[i].n_total or works[i].n_cand)
             mode = scorer
             if mode == "auto":
                 mode = "cont"
@@ -1154,12 +1167,19 @@ class Engine:
             w = works[i]
             J["key"][pos] = int(w.key) & 0xFFFFFFFFFFFFFFFF
             J["cand_base"][pos] = w.cand_base
-            n = int(np.asarray(w.cand).size) if inj(i) else int(w.n_cand)
+            n = n_inj(w) if inj(i) else int(w.n_cand)
             J["n_cand"][pos] = n
             J["out_off"][pos] = out_off
             out_off += n
             flags = 0
-            if inj(i):
+            if w.cand_dev is not None:  # an element range of the caller's device buffer
+                if not opts.cand_ptr or w.cand is not None:
+                    raise ValueError("cand_dev needs Engine.run(cand_ptr=...) and no cand")
+                J["cand_off"][pos] = int(w.cand_dev[0])
+                flags |= L.F_INJECTED
+            elif inj(i):
+                if opts.cand_ptr:
+                    raise ValueError("with cand_ptr every injected work names a cand_dev range")
                 # categorical candidates are category indices (0..K-1), as the
                 # reference's randint_via_categorical samples them (tpe.py:590)
                 c = np.asarray(w.cand, dtype=np.float64).reshape(-1)
@@ -1226,7 +1246,8 @@ class Engine:
             outputs=False, stream=None, timers=None, sample_only=False,
             pruned=True, scorer=None, posteriors=False, history=None, rows=None,
             is_below=None, histories=None, timer_groups=None,
-            table_scores=False, defer=False, exchange=None) -> List[LabelResult]:
+            table_scores=False, defer=False, exchange=None, cand_ptr=0,
+            device_outputs=False) -> List[LabelResult]:
         """Run one level (``_run_level``); at precision 32 the labels scored by
         an fp32 argmax -- injected candidates, or per-candidate ``outputs`` --
         get the exact decision afterwards (``_exact_decision``), so every
@@ -1270,10 +1291,19 @@ class Engine:
         and all-reduced over the RCCL communicator ``comm`` (an ncclComm_t
         address; tpe_maxloc_allreduce), on the level's stream; the combined
         records (BEST_DTYPE, the same on every rank) come back with the level's
-        one readback as ``self.last_exchange``."""
+        one readback as ``self.last_exchange``.
+        ``cand_ptr``: a device buffer of fp64 candidates; a work's ``cand_dev``
+        names its element range there instead of uploading ``cand`` (precision
+        64).  ``device_outputs`` (with ``outputs``): the per-candidate
+        log-densities stay in the workspace buffers ``out_bl`` / ``out_al``
+        (``device_output_ptrs``), each result's range in ``extra["out_off"]`` /
+        ``extra["n"]``; nothing per candidate is read back."""
+        if (cand_ptr or device_outputs) and (precision != 64 or sample_only or table_scores):
+            raise ValueError("cand_ptr / device_outputs: exact fp64 scoring only")
         opts = _LevelOpts(prior_weight, lf, precision, outputs, stream, timers, sample_only,
                           pruned, scorer, posteriors, history, rows, is_below, histories,
-                          timer_groups, table_scores, defer, exchange)
+                          timer_groups, table_scores, defer, exchange, int(cand_ptr or 0),
+                          bool(device_outputs and outputs))
         res = self._run_level(works, opts)
         if precision == 32 and isinstance(works, list) and res and not (
                 sample_only or posteriors or table_scores or exchange is not None) and \
@@ -1692,11 +1722,12 @@ class Engine:
         # from one event recorded on the main stream after the fit (the
         # categorical posterior could start at the gather, but the side
         # stream has the slack and the fork costs two more host calls)
-        st.d_cand = lv.base + lv.o_cand
+        st.d_cand = opts.cand_ptr or lv.base + lv.o_cand
         if opts.outputs:
             st.d_bl = self._buf("out_bl", 8 * max(plan.out_off, 1))
             st.d_al = self._buf("out_al", 8 * max(plan.out_off, 1))
-            st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
+            if not opts.device_outputs:  # (nullable in every scorer)
+                st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
         elif opts.table_scores:
             st.d_sc = self._buf("out_sc", 8 * max(plan.out_off, 1))
             st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
@@ -2120,6 +2151,8 @@ class Engine:
         jobs, out_off = plan.jobs, plan.out_off
         names = ("out_bl", "out_al", "out_x") if opts.outputs else \
             ("out_sc", "out_x", "out_eps") if opts.table_scores else ()
+        if opts.device_outputs:  # the log-densities stay where the scorers wrote them
+            names = ()
         with self.torch.cuda.stream(lv.stream):
             outs = [self._bufs[k][:8 * max(out_off, 1)].to("cpu").numpy().view(np.float64)
                     for k in names]
@@ -2135,7 +2168,10 @@ class Engine:
         for pos, i in enumerate(plan.order):
             w = works[i]
             r = LabelResult(w.label, b_idx[pos], b_val[pos], b_sc[pos], b_ns[pos])
-            if opts.outputs:
+            if opts.device_outputs:
+                r.extra["out_off"], r.extra["n"] = (int(jobs[pos]["out_off"]),
+                                                    int(jobs[pos]["n_cand"]))
+            elif opts.outputs:
                 o, n = int(jobs[pos]["out_off"]), int(jobs[pos]["n_cand"])
                 r.below_llik = outs[0][o:o + n].copy()
                 r.above_llik = outs[1][o:o + n].copy()
@@ -2662,6 +2698,9 @@ def _injected_range(w: LabelWork, P, fp32=True):
     """Scoring-coordinate range of injected candidates (finite ones; the table
     grid covers it, anything outside is scored exactly).  fp32: the log of an
     LGMM1 candidate as the fp32 scorer forms it."""
+    if w.cand_dev is not None:  # (the caller's range of its device candidates)
+        lo, hi = w.cand_dev[2]
+        return float(lo), float(hi)
     c = np.asarray(w.cand, dtype=np.float64).reshape(-1)
     if P["family"] == L.LGMM1:
         with np.errstate(all="ignore"):

@@ -23,6 +23,10 @@ auto: float64 when n_EI_candidates x history is small, float32 otherwise;
 or 32 / 64; env HYPEROPT_AMD_PRECISION).  Under torch.distributed each rank
 scores its share of the candidates and the winners are combined with an
 all-gather + device max-loc (hyperopt_amd/dist.py).
+
+``Pool`` / ``score_configs`` / ``suggest_from_pool`` (hyperopt_amd/pool.py)
+rank a fixed set of configurations with the same posteriors and return
+several distinct documents per call.
 """
 from __future__ import annotations
 
@@ -772,3 +776,6 @@ def _suggest_many(requests, shard_studies=False):
                                 [{lab: st.stored[lab] for lab in st.live}])
     return out
 
+
+# a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
+from .pool import Pool, score_configs, suggest_from_pool  # noqa: E402,F401

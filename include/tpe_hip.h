@@ -638,6 +638,39 @@ int tpe_anneal_sample(const double* vals, const uint8_t* active, int64_t ld, int
 /* host: writes sizeof(tpe_anneal, tpe_anneal_dbg) to out[0..n); returns 2 */
 int tpe_anneal_struct_sizes(int32_t* out, int n);
 
+/* ---- a fixed pool of configurations (tpe.suggest_from_pool) ----------------
+ * A pool is n_rows configurations in HBM, label-major like a history: label
+ * j's values are one contiguous fp64 column (handed to the exact scorers above
+ * as their `cand`, TPE_F_INJECTED) and its activity one byte per row at
+ * active + j * ld.  The criterion of a whole configuration is broadcast_best's
+ * (tpe.py:649-658) summed over its live labels (build_posterior factorises
+ * over labels, tpe.py:697-746):
+ *   S[r] = sum_{j active in row r} (below_llik_j[r] - above_llik_j[r]).
+ *
+ * tpe_pool_fold adds n_labels labels to S, in list order: label i's
+ * log-densities are the n_rows elements at bl + host_off[i] / al + host_off[i]
+ * (the scorers' out_bl / out_al), its column host_col[i].  init != 0: S starts
+ * at 0.0, otherwise at its content (a pool scored in label chunks).  An
+ * inactive label is skipped, not added as zero; the sum is sequential fp64 in
+ * list order.  terms (nullable): label i's term (NaN where inactive) is also
+ * written to terms + host_col[i] * terms_ld.  host_off / host_col: host
+ * arrays, read before the call returns. */
+int tpe_pool_fold(const double* bl, const double* al, const int64_t* host_off,
+                  const int64_t* host_col, int n_labels, const uint8_t* active, int64_t ld,
+                  int64_t n_rows, int init, double* S, double* terms, int64_t terms_ld,
+                  void* stream);
+/* tpe_pool_topk: the first min(k, untaken rows) rows r with taken[r] == 0 in
+ * np.argmax order -- larger score first, NaN before everything, equal scores
+ * (-0.0 == +0.0) to the smaller row -- written to out_rows in rank order, their
+ * number to *out_count (entries of out_rows past it are left alone).  Exact
+ * (a multi-block radix select over the score bits, then a ranking of the
+ * selected rows); no floating-point atomics, the result does not depend on
+ * block scheduling.  scratch: tpe_pool_topk_scratch_bytes(n_rows, k) bytes
+ * (-1: bad arguments). */
+int64_t tpe_pool_topk_scratch_bytes(int64_t n_rows, int64_t k);
+int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t n_rows, int64_t k,
+                  int64_t* out_rows, int64_t* out_count, void* scratch, void* stream);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
