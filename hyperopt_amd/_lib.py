@@ -148,6 +148,7 @@ _SIGNATURES = {
     "tpe_pool_fold": (_I, [_P, _P, _P, _P, _I, _P, _I64, _I64, _I, _P, _P, _I64, _P]),
     "tpe_pool_topk_scratch_bytes": (_I64, [_I64, _I64]),
     "tpe_pool_topk": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "tpe_grid_fold": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),

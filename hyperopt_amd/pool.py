@@ -25,6 +25,11 @@ column is scored in place by the exact fp64 scorers (as injected candidates,
 selects the first k untaken rows (csrc/tpe_pool.hip).  Conditional labels are
 scored for every row (an inactive entry holds a copy of one of the column's
 live values) and masked in the fold.  Only the k row indices come back.
+
+``GridPool`` is the pool of a Cartesian product of per-label axes.  S is
+separable over the axes, so the scorers see every axis value once and
+``tpe_grid_fold`` (csrc/tpe_grid.hip) decodes the rows and sums the per-value
+terms; the device holds the axes, S and the taken mask, 9 bytes per row.
 """
 from __future__ import annotations
 
@@ -72,27 +77,36 @@ def _switch_value(spec, v):
     return int(round(v)) if spec.kind in INT_KINDS else float(v)
 
 
+def _first_invalid(spec, v, a):
+    """(position, what is wrong) of the first entry of ``v`` live under ``a``
+    that is not a stored value of the label -- finite, inside ``_bounds``, whole
+    for the integer kinds -- or None."""
+    lo, hi, hi_open, whole = _bounds(spec)
+    with np.errstate(invalid="ignore"):
+        bad = a & ~np.isfinite(v)
+        what = "is not finite"
+        if not bad.any():
+            bad = a & ((v < lo) | ((v >= hi) if hi_open else (v > hi)))
+            what = "is outside %s%g, %g%s of %s" % ("[", lo, hi, ")" if hi_open else "]",
+                                                    spec.kind)
+        if not bad.any() and whole:
+            bad = a & (v != np.round(v))
+            what = "is not a whole number (%s)" % spec.kind
+    if bad.any():
+        return int(np.flatnonzero(bad)[0]), what
+    return None
+
+
 def _validate(domain, labels, vals, active):
     """Raise ValueError naming the row and the label of the first invalid entry:
     every live value finite and inside its prior's support, and every row's
     label set the one its own choices make live (``domain.reachable``)."""
     P = vals.shape[0]
     for j, lab in enumerate(labels):
-        spec = domain.specs[lab]
         a, v = active[:, j], vals[:, j]
-        lo, hi, hi_open, whole = _bounds(spec)
-        with np.errstate(invalid="ignore"):
-            bad = a & ~np.isfinite(v)
-            what = "is not finite"
-            if not bad.any():
-                bad = a & ((v < lo) | ((v >= hi) if hi_open else (v > hi)))
-                what = "is outside %s%g, %g%s of %s" % ("[", lo, hi, ")" if hi_open else "]",
-                                                        spec.kind)
-            if not bad.any() and whole:
-                bad = a & (v != np.round(v))
-                what = "is not a whole number (%s)" % spec.kind
-        if bad.any():
-            r = int(np.flatnonzero(bad)[0])
+        bad = _first_invalid(domain.specs[lab], v, a)
+        if bad is not None:
+            r, what = bad
             raise ValueError("pool row %d, label %r: value %r %s" % (r, lab, float(v[r]), what))
     if P == 0:
         return
@@ -121,6 +135,20 @@ def _validate(domain, labels, vals, active):
                 int(rows[i]), labels[j],
                 "missing, but live under the row's choices" if want[j]
                 else "given, but not live under the row's choices"))
+
+
+def _scoring_range(spec, live):
+    """(min, max) of a label's live values in the scoring coordinate (log x for
+    the log-domain priors), the range a ``cand_dev`` work names."""
+    if spec.kind not in CONTINUOUS or not live.size:
+        return 0.0, 0.0
+    P = _params(spec.kind, spec.args)
+    if P["family"] == _L.LGMM1:
+        with np.errstate(all="ignore"):
+            live = np.log(live)
+    live = live[np.isfinite(live)]
+    mu = P["prior_mu"]
+    return (float(live.min()), float(live.max())) if live.size else (mu, mu)
 
 
 class _DevicePool(object):
@@ -246,15 +274,7 @@ class Pool(object):
                 # (an inactive entry is scored too and masked in the fold: it
                 # holds a value the scorer accepts)
                 cols[j, :P] = np.where(a, c, live[0] if live.size else 0.0)
-                rng = (0.0, 0.0)
-                if spec.kind in CONTINUOUS and live.size:
-                    if _params(spec.kind, spec.args)["family"] == _L.LGMM1:
-                        with np.errstate(all="ignore"):
-                            live = np.log(live)
-                    live = live[np.isfinite(live)]
-                    mu = _params(spec.kind, spec.args)["prior_mu"]
-                    rng = (float(live.min()), float(live.max())) if live.size else (mu, mu)
-                ranges.append(rng)
+                ranges.append(_scoring_range(spec, live))
             d = _DevicePool()
             d.vals = t.from_numpy(cols).to(eng.device)
             d.active = t.from_numpy(np.ascontiguousarray(self.active.T).view(np.uint8)
@@ -270,6 +290,305 @@ class Pool(object):
             d.taken[:len(self)].copy_(t.from_numpy(self.taken))
             d.taken_current = True
         return d
+
+
+class _GridBlock(object):
+    """One block of a grid pool: the rows [offset, offset + rows) share the
+    selector assignment that makes ``cols`` (label indices in ``domain.params``
+    order) live.  Label i of the block takes the ``radix[i]`` axis positions
+    from ``pos[i]`` on -- a fixed selector has radix 1 and ``pos`` at its
+    value -- and is digit i of the row index, the last label fastest."""
+    __slots__ = ("offset", "rows", "cols", "pos", "radix")
+
+
+class _DeviceGrid(object):
+    """A grid pool's mirror on one device: the concatenated axes (fp64,
+    randint(low, high) values offset-free), the (min, max) of every axis in the
+    scoring coordinate, S (8 bytes per row) and the mask ``tpe_pool_topk``
+    reads (taken or excluded, one byte per row)."""
+    __slots__ = ("axes", "taken", "taken_current", "ranges", "S", "rows_out", "count", "scratch")
+
+
+KEEP_CHUNK = 1 << 20   # rows per call of a grid pool's ``keep``
+MAX_BLOCKS = 4096      # the size of Domain.reachable's memo
+
+
+class GridPool(object):
+    """The Cartesian product of per-label axes as a pool, without its rows.
+
+        pool = tpe.GridPool(domain, {"tile_m": [16, 32, 64], "unroll": range(1, 9), ...})
+
+    ``axes`` maps every label of ``domain.params`` to its stored values (as in
+    a trial's ``misc["vals"]``), pairwise distinct and valid under ``Pool``'s
+    rules (ValueError names the label and the position on the axis).  The
+    score of a row is separable, S(row) = sum_l T_l[digit_l(row)] with
+    T_l = log l - log g of label l's axis values: the exact scorers see the
+    sum of the axis lengths, and ``tpe_grid_fold`` (csrc/tpe_grid.hip) decodes
+    the rows.  Nothing of size rows x labels is built except by ``to_pool``.
+
+    Rows.  The pool is a sequence of blocks, one per complete assignment of the
+    live selector labels, enumerated depth first: the first undecided live
+    selector in ``domain.params`` order takes its axis values in axis order,
+    until ``domain.reachable`` adds no label.  A block's rows are the product
+    of the axes of its live non-selector labels in ``itertools.product`` order
+    (``domain.params`` order, last label fastest); a row's number is its
+    block's offset plus its index in the block.  A flat space is one block.
+
+    ``keep(cols)``, optional: called once over all rows in chunks of at most
+    ``KEEP_CHUNK``, ``cols`` the {label: float64 array} of the chunk's rows
+    (NaN where the label is not live); rows whose entry of the returned mask
+    is false are excluded -- never suggested, not counted by ``n_untaken``,
+    not drawn in the startup phase.  ``exclude(rows)`` does the same for rows
+    given by number.  The rest of the surface is ``Pool``'s.
+    """
+
+    def __init__(self, domain, axes, keep=None):
+        domain = as_domain(domain)
+        labels = list(domain.params)
+        for lab in axes:
+            if lab not in domain.params:
+                raise ValueError("grid axis %r: not a label of the space" % (lab,))
+        self.axes, self.axis_off = [], np.zeros(len(labels) + 1, np.int64)
+        for j, lab in enumerate(labels):
+            if lab not in axes:
+                raise ValueError("grid axis %r: missing (every label of the space needs an axis)"
+                                 % (lab,))
+            try:
+                v = np.array(axes[lab], dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("grid axis %r: its values are not numbers" % (lab,)) from None
+            if v.ndim != 1 or v.size == 0:
+                raise ValueError("grid axis %r: %s" % (
+                    lab, "empty" if v.size == 0 else "not one-dimensional"))
+            bad = _first_invalid(domain.specs[lab], v, np.ones(v.size, bool))
+            if bad is not None:
+                raise ValueError("grid axis %r, position %d: value %r %s"
+                                 % (lab, bad[0], float(v[bad[0]]), bad[1]))
+            order = np.argsort(v, kind="stable")
+            same = np.flatnonzero(v[order][1:] == v[order][:-1])
+            if same.size:
+                i = int(order[same + 1].min())
+                raise ValueError("grid axis %r, position %d: value %r is repeated"
+                                 % (lab, i, float(v[i])))
+            self.axes.append(v)
+            self.axis_off[j + 1] = self.axis_off[j] + v.size
+        self.domain, self.labels = domain, labels
+        self._enumerate()
+        P = len(self)
+        self.taken = np.zeros(P, np.uint8)
+        self.excluded = None
+        self.row_of = {}
+        self._device = {}
+        if keep is not None:
+            for lo in range(0, P, KEEP_CHUNK):
+                hi = min(P, lo + KEEP_CHUNK)
+                mask = np.asarray(keep(self._columns(lo, hi)))
+                if mask.shape != (hi - lo,):
+                    raise ValueError("keep returned shape %s for %d rows" % (mask.shape, hi - lo))
+                self.exclude(lo + np.flatnonzero(~mask.astype(bool)))
+
+    def _enumerate(self):
+        domain, labels = self.domain, self.labels
+        index = {lab: j for j, lab in enumerate(labels)}
+        domain.reachable({})
+        selectors = set(domain._selector_labels)
+        blocks = []
+
+        def expand(decided, where):
+            live = domain.reachable(decided)
+            for lab in live:  # (domain.params order)
+                if lab in selectors and lab not in decided:
+                    spec = domain.specs[lab]
+                    for i, v in enumerate(self.axes[index[lab]]):
+                        expand(dict(decided, **{lab: _switch_value(spec, v)}),
+                               dict(where, **{lab: i}))
+                    return
+            if len(blocks) == MAX_BLOCKS:
+                raise ValueError("the selector axes make more than %d blocks" % MAX_BLOCKS)
+            b = _GridBlock()
+            b.cols = np.asarray([index[lab] for lab in live], np.int64)
+            b.pos = np.asarray([where.get(lab, 0) for lab in live], np.int64)
+            b.radix = np.asarray([1 if lab in where else self.axes[index[lab]].size
+                                  for lab in live], np.int64)
+            b.rows = int(np.prod([int(r) for r in b.radix], dtype=object)) if live else 1
+            blocks.append(b)
+
+        expand({}, {})
+        self.blocks = blocks
+        self.block_off = np.zeros(len(blocks) + 1, np.int64)
+        total = 0
+        for i, b in enumerate(blocks):
+            b.offset = total
+            total += b.rows
+            if total >= 1 << 62:
+                raise ValueError("the grid has more than 2^62 rows")
+            self.block_off[i + 1] = total
+        live_cols = np.zeros(len(labels), bool)
+        for b in blocks:
+            live_cols[b.cols] = True
+        self.scored = np.flatnonzero(live_cols)  # labels live in some block
+
+    def __len__(self):
+        return int(self.block_off[-1])
+
+    @property
+    def n_untaken(self):
+        gone = self.taken if self.excluded is None else self.taken | self.excluded
+        return int(len(self) - np.count_nonzero(gone))
+
+    _rows = Pool._rows
+
+    def _stale(self):
+        for d in self._device.values():
+            d.taken_current = False
+
+    def mark_taken(self, rows):
+        """Rows that are no longer to be suggested (e.g. evaluated elsewhere)."""
+        self.taken[self._rows(rows)] = 1
+        self._stale()
+
+    def release(self, rows):
+        """Rows that may be suggested again; their ``row_of`` entries go.  An
+        excluded row cannot be released (ValueError)."""
+        rows = self._rows(rows)
+        if self.excluded is not None and self.excluded[rows].any():
+            raise ValueError("grid row %d is excluded: it cannot be released"
+                             % int(rows[np.flatnonzero(self.excluded[rows])[0]]))
+        self.taken[rows] = 0
+        gone = set(rows.tolist())
+        for tid in [t for t, r in self.row_of.items() if r in gone]:
+            del self.row_of[tid]
+        self._stale()
+
+    def exclude(self, rows):
+        """Rows that are not part of the search (module doc: ``keep``)."""
+        rows = self._rows(rows)
+        if rows.size:
+            if self.excluded is None:
+                self.excluded = np.zeros(len(self), np.uint8)
+            self.excluded[rows] = 1
+            self._stale()
+
+    def _block_of(self, row):
+        return int(np.searchsorted(self.block_off, row, side="right")) - 1
+
+    def config(self, row):
+        """Row ``row`` as the {live label: stored value} dict of a trial."""
+        row = int(row)
+        if not 0 <= row < len(self):
+            raise IndexError("pool rows outside [0, %d)" % len(self))
+        b = self.blocks[self._block_of(row)]
+        idx = row - b.offset
+        specs, out = self.domain.specs, {}
+        for i in range(len(b.cols) - 1, -1, -1):
+            idx, digit = divmod(idx, int(b.radix[i]))
+            j = int(b.cols[i])
+            v = self.axes[j][int(b.pos[i]) + digit]
+            lab = self.labels[j]
+            out[lab] = int(round(v)) if specs[lab].kind in INT_KINDS else float(v)
+        return {self.labels[j]: out[self.labels[j]] for j in b.cols}
+
+    def _columns(self, lo, hi):
+        """{label: float64 (hi - lo,)} of the rows [lo, hi), NaN where dead."""
+        cols = {lab: np.full(hi - lo, np.nan) for lab in self.labels}
+        for k in range(self._block_of(lo), len(self.blocks)):
+            b = self.blocks[k]
+            a, z = max(lo, b.offset), min(hi, b.offset + b.rows)
+            if a >= z:
+                if b.offset >= hi:
+                    break
+                continue
+            idx = np.arange(a - b.offset, z - b.offset, dtype=np.int64)
+            for i in range(len(b.cols) - 1, -1, -1):
+                idx, digit = np.divmod(idx, b.radix[i])
+                j = int(b.cols[i])
+                cols[self.labels[j]][a - lo:z - lo] = self.axes[j][b.pos[i] + digit]
+        return cols
+
+    def to_pool(self):
+        """The same rows in the same order as a plain ``Pool`` (the (P, L)
+        matrix this class avoids: for tests and small grids)."""
+        P = len(self)
+        vals = np.full((P, len(self.labels)), np.nan)
+        for lo in range(0, P, KEEP_CHUNK):
+            hi = min(P, lo + KEEP_CHUNK)
+            cols = self._columns(lo, hi)
+            for j, lab in enumerate(self.labels):
+                vals[lo:hi, j] = cols[lab]
+        return Pool.from_arrays(self.domain, vals, ~np.isnan(vals))
+
+    # -- device mirror ---------------------------------------------------------
+    def device(self, eng):
+        """The pool's mirror on ``eng``'s device, uploaded once."""
+        d = self._device.get(eng.device)
+        t = eng.torch
+        P = len(self)
+        if d is None:
+            flat, ranges = [], []
+            for lab, v in zip(self.labels, self.axes):
+                spec = self.domain.specs[lab]
+                c = v - (int_offset(spec) or 0)
+                flat.append(c)
+                ranges.append(_scoring_range(spec, c))
+            d = _DeviceGrid()
+            d.axes = t.from_numpy(np.concatenate(flat)).to(eng.device)
+            d.ranges = ranges
+            d.taken = t.zeros(max(P, 1), dtype=t.uint8, device=eng.device)
+            d.taken_current = False
+            d.S = t.empty(max(P, 1), dtype=t.float64, device=eng.device)
+            d.rows_out = d.count = d.scratch = None
+            self._device[eng.device] = d
+        if not d.taken_current:
+            gone = self.taken if self.excluded is None else self.taken | self.excluded
+            d.taken[:P].copy_(t.from_numpy(gone))
+            d.taken_current = True
+        return d
+
+
+def _score_grid(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None):
+    """S of every row of a grid pool into its device buffer ``S``: one engine
+    run over the axes of the scored labels, one ``tpe_grid_fold`` per block.
+    Returns (engine, device grid, {label index: T_l} or None)."""
+    if list(domain.params) != pool.labels:
+        raise ValueError("the pool was built for another space (labels differ)")
+    eng, obs = _history_inputs(domain, trials, gamma, hist)
+    d = pool.device(eng)
+    t, lib = eng.torch, eng.lib
+    works = []
+    for j in pool.scored:
+        lab = pool.labels[j]
+        n = pool.axes[j].size
+        w = obs.work(lab, domain.specs[lab], int(j), n_cand=n, n_total=n)
+        w.cand_dev = (int(pool.axis_off[j]), n, d.ranges[j])
+        works.append(w)
+    out_off = np.zeros(len(pool.labels), np.int64)
+    d_bl = d_al = None
+    if works:
+        res = eng.run(works, prior_weight=prior_weight, lf=lf, precision=64, outputs=True,
+                      cand_ptr=d.axes.data_ptr(), device_outputs=True, **obs.run_kwargs)
+        out_off[pool.scored] = [r.extra["out_off"] for r in res]
+        d_bl, d_al = eng.device_output_ptrs()
+    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    for b in pool.blocks:
+        off = np.ascontiguousarray(out_off[b.cols] + b.pos)
+        _L.check(lib.tpe_grid_fold(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data, len(b.cols),
+                                   0, b.rows, d.S.data_ptr() + 8 * b.offset, sp),
+                 "tpe_grid_fold")
+    terms = None
+    if want_terms:
+        terms = {}
+        n = int(sum(pool.axes[j].size for j in pool.scored))
+        if works:
+            bl, al = (eng._bufs[k][:8 * n].cpu().numpy().view(np.float64)
+                      for k in ("out_bl", "out_al"))
+        for j, lab in enumerate(pool.labels):
+            if j in pool.scored:
+                o = int(out_off[j])
+                with np.errstate(invalid="ignore"):
+                    terms[lab] = bl[o:o + pool.axes[j].size] - al[o:o + pool.axes[j].size]
+            else:  # live in no block: never scored
+                terms[lab] = np.full(pool.axes[j].size, np.nan)
+    return eng, d, terms
 
 
 def _history_inputs(domain, trials, gamma, hist=None):
@@ -290,6 +609,8 @@ def _history_inputs(domain, trials, gamma, hist=None):
 def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None):
     """S of every pool row into the pool's device buffer ``S`` (and the
     per-label terms into ``terms``); returns (engine, device pool)."""
+    if isinstance(pool, GridPool):
+        return _score_grid(domain, trials, pool, prior_weight, gamma, lf, False, hist)[:2]
     if list(domain.params) != pool.labels:
         raise ValueError("the pool was built for another space (labels differ)")
     eng, obs = _history_inputs(domain, trials, gamma, hist)
@@ -357,8 +678,17 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     ``return_terms`` also the (P, L) matrix of per-label terms log l - log g,
     NaN where the label is inactive.  Exact fp64 scoring, whatever the pool
     size.  S[r] is the sequential fp64 sum of row r's terms over its live
-    labels in ``domain.params`` order, starting from 0.0."""
+    labels in ``domain.params`` order, starting from 0.0.
+
+    For a ``GridPool`` the terms are per axis value, not per row:
+    ``return_terms`` gives {label: (V_l,) array of T_l}, all NaN for a label
+    live in no block."""
     domain = as_domain(domain)
+    if isinstance(pool, GridPool):
+        eng, d, terms = _score_grid(domain, trials, pool, prior_weight, gamma,
+                                    linear_forgetting, return_terms)
+        S = d.S[:len(pool)].cpu().numpy()
+        return (S, terms) if return_terms else S
     eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
                            return_terms)
     P = len(pool)
@@ -369,10 +699,14 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
 
 
 def startup_rows(pool, seed, k):
-    """The startup phase's rows: k of the untaken rows, uniformly without
+    """The startup phase's rows: k of the untaken rows (of a grid pool: that are
+    not excluded either), uniformly without
     replacement, a function of (seed, taken set) alone:
     ``untaken[np.random.RandomState(seed).choice(untaken.size, k, replace=False)]``."""
-    untaken = np.flatnonzero(pool.taken == 0)
+    free = pool.taken == 0
+    if getattr(pool, "excluded", None) is not None:  # (a GridPool's keep / exclude)
+        free &= pool.excluded == 0
+    untaken = np.flatnonzero(free)
     k = min(int(k), untaken.size)
     if k == 0:
         return np.zeros(0, np.int64)

@@ -671,6 +671,27 @@ int64_t tpe_pool_topk_scratch_bytes(int64_t n_rows, int64_t k);
 int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t n_rows, int64_t k,
                   int64_t* out_rows, int64_t* out_count, void* scratch, void* stream);
 
+/* ---- a grid pool: the product of per-label axes (tpe.GridPool) ---------------
+ * The criterion above is separable: once the scorers have left log l / log g
+ * of every axis value in bl / al, the score of a row of the product is a sum
+ * of per-value terms.  tpe_grid_fold writes it for one block of a grid -- the
+ * product of n_labels axes, row r holding the mixed-radix digits of r, last
+ * label fastest (itertools.product order) -- and a window of its rows:
+ *   S_out[i] = sum_j (bl[host_off[j] + d_j] - al[host_off[j] + d_j]),
+ *   d_j = digit j of row row_begin + i,   i in [0, n_rows),
+ * a sequential fp64 sum from 0.0 in list order: the bits tpe_pool_fold gives
+ * for the materialised row.  host_off[j]: the element of label j's digit 0;
+ * host_radix[j] >= 1 its number of digits (a label fixed in the block: radix 1
+ * and an offset that points at its value).  The block has prod host_radix
+ * rows, which must fit int64 and hold the window.  Only entries of digits that
+ * rows of the window take are read, so an offset may be negative where the
+ * caller keeps a slice of an axis's terms.  n_labels <= 128.  host_off /
+ * host_radix: host arrays, read before the call returns.  One launch, no
+ * atomics; the result does not depend on block scheduling. */
+int tpe_grid_fold(const double* bl, const double* al, const int64_t* host_off,
+                  const int64_t* host_radix, int n_labels, int64_t row_begin, int64_t n_rows,
+                  double* S_out, void* stream);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
