@@ -116,6 +116,7 @@ _SIGNATURES = {
                                   _P, _I64, _I, _P, _P]),
     "tpe_band_rescore": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "tpe_band_bytes": (_I64, [_P, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "tpe_band_layout": (_I, [_P, _I]),
     "tpe_categorical_suggest": (_I, [_P, _P, _I, _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "tpe_history_order_scratch_bytes": (_I64, [_I, _I64]),
     "tpe_history_order": (_I, [_P, _I64, _P, _P, _I, _I64, _I64, _P, _P, _P]),

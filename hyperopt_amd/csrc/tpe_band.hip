@@ -4,8 +4,10 @@
 // GMM1_lpdf / LGMM1_lpdf's sums (hyperopt/tpe.py:117-180, 265-307), and
 // broadcast_best's argmax (tpe.py:649-658) is taken over them.
 //
-// Exports: tpe_band_bytes, tpe_band_rescore; launch_reduce (k_reduce) for
-// every scorer.
+// Exports: tpe_band_bytes, tpe_band_rescore, tpe_band_layout; launch_reduce
+// (k_reduce) for every scorer.
+#include <cstddef>
+
 #include "tpe_table.hpp"
 
 namespace tpe {
@@ -789,6 +791,10 @@ __global__ __launch_bounds__(kFX) void k_band_final(const tpe_job* __restrict__ 
           const int ndt = s_nd[k][mix];
           if (ndt < 0) return band_direct(S, coef64, y);
           const double m = s_P[k][mix][kBandD + 1];
+          // every component of the cell slow (a cell budget that forces wide
+          // cells: in a tail cell the prior component itself): nothing was
+          // expanded, so there is no scale m to sum the listed ones at
+          if (m == -INFINITY) return band_direct(S, coef64, y);
           if (ndt > 0) {
             for (int cc = 0; cc < nch; ++cc) {
               const int un = k * nch + cc, nd = s_ndu[un][mix];
@@ -862,6 +868,22 @@ extern "C" int64_t tpe_band_bytes(const tpe_job* host_jobs, int n_jobs, int64_t*
   if (ctl_bytes) *ctl_bytes = tiles * kHdrWords * (int64_t)sizeof(uint32_t);
   if (work_bytes) *work_bytes = (int64_t)sizeof(BandWork) * std::max(n_jobs, 1);
   return tiles * kTileSlots * (int64_t)sizeof(tpe_band);
+}
+
+// The band work's layout and the two stages' constants, for tests that read
+// a job's route (BandWork.{ns, ncell, over, direct}) back: host only.
+extern "C" int tpe_band_layout(int64_t* out, int n) {
+  const int64_t v[] = {
+      (int64_t)sizeof(BandWork),         (int64_t)offsetof(BandWork, ns),
+      (int64_t)offsetof(BandWork, ncell), (int64_t)offsetof(BandWork, over),
+      (int64_t)offsetof(BandWork, direct), (int64_t)offsetof(BandWork, sy),
+      (int64_t)offsetof(BandWork, sidx),  (int64_t)offsetof(BandWork, cells),
+      kBandBlocks, kBandDirect, kBandSurv, kBandCells, kBandSurvMax, kBandTiles, kChunkDir,
+      kTileSlots, kTileF, kHdrWords, (int64_t)kTileFull};
+  const int m = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < m && i < n; ++i)
+    if (out) out[i] = v[i];
+  return m;
 }
 
 extern "C" int tpe_band_rescore(const tpe_job* jobs, const tpe_job* host_jobs, int n_jobs,

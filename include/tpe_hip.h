@@ -467,6 +467,14 @@ int tpe_band_rescore(const tpe_job* jobs, const tpe_job* host_jobs, int n_jobs,
                      const tpe_seg* segs, const double* coef64, const tpe_table* tables,
                      const tpe_band* band, const uint32_t* band_ctl, const tpe_best* partial,
                      int64_t n_partial, tpe_best* best, void* work, void* stream);
+/* tpe_band_layout (host only, tests): the first n of the band work's layout
+ * and the two stages' constants to out; returns how many there are (19):
+ * bytes of one job's work; byte offsets in it of ns, ncell, over, direct
+ * (int32), sy (float[]), sidx (int64[]), cells (int32[]); then blocks per
+ * job, direct survivors (always / at most), listed cells, survivors, tiles,
+ * slow components per list, entries per tile, candidates per tile, header
+ * words per tile, and the "tile full" count. */
+int tpe_band_layout(int64_t* out, int n);
 
 /* ---- continuous candidates, exact fp64 with pruning (parity mode) ----------
  * Same results as tpe_score_continuous(precision=64) up to fp64 rounding (a
