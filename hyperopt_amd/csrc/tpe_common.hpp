@@ -195,15 +195,26 @@ __device__ __forceinline__ BestT block_best(BestT b, BestT* sh) {
 // numpy-exact arithmetic helpers (no FMA contraction where numpy has none)
 // ---------------------------------------------------------------------------
 // np.linspace(1/N, 1, N-LF) element i, then ones(LF): tpe.py:380-392
+// (the ramp of a set of n observations: built once per kernel, at() per entry)
+struct LfRamp {
+  bool ramp;  // lf > 0 && lf < n: otherwise every weight is 1
+  int64_t num;
+  double start, step;
+  template <typename I>  // (n's own width: an int count keeps num's arithmetic in 32 bits)
+  __device__ __forceinline__ LfRamp(I n, int32_t lf)
+      : ramp(lf > 0 && lf < n),
+        num(n - lf),
+        start(1.0 / (double)n),
+        step((1.0 - start) / (double)(num - 1)) {}  // (read only when ramp && num > 1)
+  __device__ __forceinline__ double at(int64_t pos) const {
+    if (!ramp || pos >= num) return 1.0;
+    if (num == 1) return start;
+    if (pos == num - 1) return 1.0;
+    return __dadd_rn(__dmul_rn((double)pos, step), start);
+  }
+};
 __device__ __forceinline__ double lf_weight(int64_t i, int64_t n, int32_t lf) {
-  if (!(lf > 0 && lf < n)) return 1.0;
-  const int64_t num = n - lf;
-  if (i >= num) return 1.0;
-  const double start = 1.0 / (double)n;
-  if (num == 1) return start;
-  if (i == num - 1) return 1.0;
-  const double step = (1.0 - start) / (double)(num - 1);
-  return __dadd_rn(__dmul_rn((double)i, step), start);
+  return LfRamp(n, lf).at(i);
 }
 
 // normal_cdf: 0.5 * (1 + erf((x - mu) / max(sqrt(2) * sigma, EPS)))  tpe.py:109-114

@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "tpe_common.hpp"
+#include "tpe_fold.hpp"
 
 namespace tpe {
 
@@ -81,183 +82,22 @@ constexpr int kCatWaves = kCatBS / kWave;
 // result must be that chain's bits.  The wave scans 64 observations per
 // step, ballots the matches, and every matching lane writes its weight
 // (computed in parallel) into the wave's LDS list at its rank; a full list
-// is folded into the running count by seq_fold below -- the same bits as the
-// serial chain, in a few wave-wide passes instead of one fp64 add latency
-// per match (a 60 000-match category: ~0.45 ms serially).
+// is folded into the running count by fold_list (tpe_fold.hpp) -- the same
+// bits as the serial chain, in a few wave-wide passes instead of one fp64 add
+// latency per match (a 60 000-match category: ~0.45 ms serially).
 constexpr int kCatList = 1024;  // weights buffered per wave before a fold
 
-// The sequential fp64 sum S_{k+1} = fl(S_k + w_k) over list[0, n), wave-
-// parallel and bit-exact (every lane returns it).  While S stays in one
-// binade [2^e, 2^(e+1)) its values are A * u (u = 2^(e-52), A < 2^53 an
-// integer) and each step adds d_k * u with d_k = w_k / u rounded to an
-// integer -- nearest, ties to the even A_{k+1} (IEEE round-to-nearest-even
-// on the binade's grid).  d_k is a shift of w_k's mantissa except at a tie
-// (remainder exactly u/2), where it depends on the parity of A_k; parities
-// compose as maps P -> a P ^ c (a tie: P -> 0, else P -> P ^ (d_k & 1)), so
-// one wave scan of those maps and one of the d_k give every A_k.  The first
-// step whose A would reach 2^53 (the next binade, where the grid is 2u), or
-// whose w_k is at least 2^(e+1), is taken by the hardware add from its exact
-// predecessor, and the pass repeats from the step after it.  Passes: one
-// per list plus one per binade crossed.  (Checked against the serial chain
-// on LF ramps, dyadic tie-heavy weights and 24-decade ranges:
-// tests/test_seq_fold.py restates it on the host; the GPU tests compare the
-// counts with np.bincount's.)
-// parity maps P -> a P ^ c packed as a | c << 1; y (earlier) then x
-__device__ __forceinline__ uint32_t map_then(uint32_t y, uint32_t x) {
-  const uint32_t a2 = x & 1u, c2 = (x >> 1) & 1u;
-  return (a2 & y & 1u) | ((((a2 & (y >> 1)) ^ c2) & 1u) << 1);
-}
-template <int CTRL, int ROWM>
-__device__ __forceinline__ void scan_step_map(uint32_t& x) {
-  x = map_then(dpp_u32<CTRL, ROWM>(1u, x), x);  // (1: the identity map)
-}
-
-// The same sum by lane 0 alone (list reads batched; every lane returns it):
-// one dependent fp64 add per entry, cheaper than seq_fold's passes while the
-// sum is small and crosses a binade every few entries (the first ~4k of a
-// chain: a pass per crossing)
-constexpr int kSerialHits = 4096;
-__device__ double serial_fold(double S, const double* list, int n, int lane) {
-  if (lane == 0) {
-    constexpr int kB = 8;
-    int j = 0;
-    for (; j + kB <= n; j += kB) {
-      double v[kB];
-#pragma unroll
-      for (int i = 0; i < kB; ++i) v[i] = list[j + i];
-#pragma unroll
-      for (int i = 0; i < kB; ++i) S = __dadd_rn(S, v[i]);
-    }
-    for (; j < n; ++j) S = __dadd_rn(S, list[j]);
+// a category's count into its pseudocount (lane 0 / thread 0 of its owner)
+__device__ __forceinline__ void cat_pseudocount(const tpe_cat_seg& S, double* __restrict__ p,
+                                                int k, double cnt) {
+  double pseudo;
+  if (S.mode == 0) {
+    pseudo = cnt + S.prior_weight;  // tpe.py:589
+  } else {
+    const double pk = p[S.prior_p_off + k];
+    pseudo = cnt + (double)S.n_cat * (S.prior_weight * pk);  // tpe.py:603
   }
-  return __shfl(S, 0, kWave);
-}
-// list[0, n) into S, the first entries of a chain (done < kSerialHits)
-// serially, the rest by seq_fold
-template <int kSE>
-__device__ double fold_list(double S, const double* list, int n, int64_t& done, int lane);
-
-// one entry's d (w / u rounded on the binade of biased exponent es, ties
-// left for the parity scan: bit j of tie), or bit j of huge (w >= 2^(e+1))
-__device__ __forceinline__ uint64_t fold_step(double w, int es, bool on, uint32_t& tie,
-                                              uint32_t& huge, int j) {
-  if (!on) return 0;
-  constexpr uint64_t kFrac = (1ull << 52) - 1;
-  const uint64_t wb = (uint64_t)__double_as_longlong(w);
-  const int ew = (int)((wb >> 52) & 0x7ff);
-  const uint64_t M = (wb & kFrac) | (ew ? (1ull << 52) : 0ull);
-  const int sh = es - max(ew, 1);
-  if (sh < 0) {
-    huge |= 1u << j;
-    return 0;
-  }
-  if (sh == 0) return M;
-  if (sh >= 64) return 0;
-  const uint64_t rem = M & ((1ull << sh) - 1), half = 1ull << (sh - 1);
-  if (rem == half) tie |= 1u << j;
-  return (M >> sh) + (rem > half ? 1ull : 0ull);
-}
-
-template <int kSE>
-__device__ double seq_fold(double S, const double* list, int n, int lane) {
-  double v[kSE];
-#pragma unroll
-  for (int j = 0; j < kSE; ++j) {
-    const int i = lane * kSE + j;
-    v[j] = i < n ? list[i] : 0.0;
-  }
-  constexpr uint64_t kFrac = (1ull << 52) - 1, kTop = 1ull << 53;
-  int r0 = 0;
-  while (r0 < n) {  // (wave-uniform)
-    const uint64_t sb = (uint64_t)__double_as_longlong(S);
-    const int es = (int)((sb >> 52) & 0x7ff);
-    if (S == 0.0 || es == 0) {  // 0 + w = w; a subnormal sum (never on the LF ramp): one add
-      S = __dadd_rn(S, list[r0]);
-      ++r0;
-      continue;
-    }
-    const uint64_t A = (sb & kFrac) | (1ull << 52);
-    uint64_t d[kSE];
-    uint32_t tie = 0, huge = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      const int i = lane * kSE + j;
-      d[j] = fold_step(v[j], es, i >= r0 && i < n, tie, huge, j);
-    }
-    // parity maps (bit 0: a, bit 1: c), composed over the lane, then an
-    // inclusive wave scan (later o earlier: a = a2 a1, c = a2 c1 ^ c2)
-    uint32_t a = 1, c = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if ((tie >> j) & 1u) {
-        a = 0;
-        c = 0;
-      } else {
-        c ^= (uint32_t)(d[j] & 1ull);
-      }
-    }
-    uint32_t x = a | (c << 1);
-    scan_step_map<0x111, 0xF>(x);
-    scan_step_map<0x112, 0xF>(x);
-    scan_step_map<0x114, 0xF>(x);
-    scan_step_map<0x118, 0xF>(x);
-    scan_step_map<0x142, 0xA>(x);
-    scan_step_map<0x143, 0xC>(x);
-    const uint32_t ex = dpp_u32<0x138, 0xF>(1u, x);  // wave_shr:1 (lane 0: the identity)
-    uint32_t P = ((ex & 1u) & (uint32_t)(A & 1ull)) ^ (ex >> 1);
-    uint64_t tot = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if ((tie >> j) & 1u) {
-        d[j] += (P + d[j]) & 1ull;  // ties to the even A_{k+1}
-        P = 0;
-      } else {
-        P ^= (uint32_t)(d[j] & 1ull);
-      }
-      tot += d[j];
-    }
-    const uint64_t incl = wave_prefix_sum_u64(tot);
-    // the first step leaving the binade
-    uint64_t cum = incl - tot;
-    int jc = -1;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if (jc < 0) {
-        if (((huge >> j) & 1u) || A + cum + d[j] >= kTop) jc = j;
-        else cum += d[j];
-      }
-    }
-    const uint64_t bal = __ballot(jc >= 0);
-    auto lane_u64 = [](uint64_t v, int l) {
-      return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
-             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    };
-    if (bal == 0) {
-      const uint64_t Dt = lane_u64(incl, kWave - 1);
-      S = ldexp((double)(A + Dt), es - 1075);
-      r0 = n;
-    } else {
-      const int L = __ffsll((unsigned long long)bal) - 1;
-      const int g = L * kSE + __builtin_amdgcn_readlane(jc, L);
-      const uint64_t Dx = lane_u64(cum, L);
-      S = __dadd_rn(ldexp((double)(A + Dx), es - 1075), list[g]);
-      r0 = g + 1;
-    }
-  }
-  return S;
-}
-
-template <int kSE>
-__device__ double fold_list(double S, const double* list, int n, int64_t& done, int lane) {
-  int f = 0;
-  if (done < kSerialHits) {
-    f = (int)std::min<int64_t>(n, kSerialHits - done);
-    S = serial_fold(S, list, f, lane);
-  }
-  constexpr int kN = kSE * kWave;
-  for (; f < n; f += kN) S = seq_fold<kSE>(S, list + f, min(kN, n - f), lane);
-  done += n;
-  return S;
+  p[S.p_off + k] = pseudo;
 }
 
 __global__ __launch_bounds__(kCatBS) void k_cat_counts(const int64_t* __restrict__ obs,
@@ -269,11 +109,7 @@ __global__ __launch_bounds__(kCatBS) void k_cat_counts(const int64_t* __restrict
   if (k >= S.n_cat) return;  // wave-uniform
   double* list = s_list[threadIdx.x / kWave];
   const int n = S.n_obs, lane = lane_id();
-  // linear-forgetting ramp (np.linspace(1/N, 1, N-LF), tpe.py:380-392)
-  const bool ramp = S.lf > 0 && S.lf < n;
-  const int64_t num = n - S.lf;
-  const double start = 1.0 / (double)n;
-  const double step = (ramp && num > 1) ? (1.0 - start) / (double)(num - 1) : 0.0;
+  const LfRamp lfw(n, S.lf);
   const uint64_t lt = (1ull << lane) - 1ull;
   double cnt = 0.0;
   int filled = 0;
@@ -310,30 +146,12 @@ __global__ __launch_bounds__(kCatBS) void k_cat_counts(const int64_t* __restrict
       const bool hit = cur[b] == (int64_t)k;
       const uint64_t m = __ballot(hit);
       if (m == 0) continue;  // wave-uniform
-      if (hit) {
-        const int64_t i = t0 + b * kWave + lane;
-        double wt = 1.0;
-        if (ramp && i < num) {
-          if (num == 1) wt = start;
-          else if (i == num - 1) wt = 1.0;
-          else wt = __dadd_rn(__dmul_rn((double)i, step), start);
-        }
-        list[filled + __popcll(m & lt)] = wt;
-      }
+      if (hit) list[filled + __popcll(m & lt)] = lfw.at(t0 + b * kWave + lane);
       filled += __popcll(m);
     }
   }
   fold();
-  if (lane == 0) {
-    double pseudo;
-    if (S.mode == 0) {
-      pseudo = cnt + S.prior_weight;  // tpe.py:589
-    } else {
-      const double pk = p[S.prior_p_off + k];
-      pseudo = cnt + (double)S.n_cat * (S.prior_weight * pk);  // tpe.py:603
-    }
-    p[S.p_off + k] = pseudo;
-  }
+  if (lane == 0) cat_pseudocount(S, p, k, cnt);
 }
 
 // The same counts read straight from the HBM history (the gathered lists'
@@ -344,17 +162,38 @@ __global__ __launch_bounds__(kCatBS) void k_cat_counts(const int64_t* __restrict
 // one scan of the packed (observations << 16 | matches) counts per (tile,
 // wave) gives every observation its position in the segment -- its LF
 // weight -- and every match its rank in the window, the window's match
-// weights going to LDS in order; wave 0 folds (seq_fold) the previous
+// weights going to LDS in order; wave 0 folds (fold_list) the previous
 // window's weights meanwhile, from the other of two LDS buffers (the fold of
 // a long chain is a serial-latency walk; the scan is load latency: they
 // overlap).  A segment whose observation count differs from S.n_obs sets
 // bit 4 of *err (tpe_gather_obs' rule).
+
+// row i of a history walk: a member of the segment (active label, the
+// segment's side of the split) and its category (-1: none of 0..n_cat-1)
+__device__ __forceinline__ void cath_row(const double* __restrict__ V,
+                                         const uint8_t* __restrict__ Ac,
+                                         const int32_t* __restrict__ rows,
+                                         const uint8_t* __restrict__ is_below, int64_t i,
+                                         int64_t n_rows, uint8_t side, int64_t offset, int n_cat,
+                                         bool& mem, int& cat) {
+  mem = false;
+  cat = -1;
+  if (i < n_rows) {
+    const int64_t r = rows ? (int64_t)rows[i] : i;
+    const bool a = Ac[r] != 0;
+    const double v = V[r];  // (read unconditionally: one latency, not two)
+    mem = a && is_below[i] == side;
+    const int64_t cv = (int64_t)v - offset;
+    if (mem && cv >= 0 && cv < (int64_t)n_cat) cat = (int)cv;
+  }
+}
+
 constexpr int kCHB = 1024;             // block
 constexpr int kCHScan = kCHB / kWave - 1;  // scanning waves (wave 0 folds)
 constexpr int kCHT = 8;                // rows per scanning thread per window
 constexpr int kCHW = kCHScan * kWave * kCHT;  // rows per window (7 680)
 constexpr int kCHSlots = kCHT * kCHScan;      // (tile, wave) counts per window
-constexpr int kCHSE = 8;               // seq_fold entries per lane (512 per pass; wider
+constexpr int kCHSE = 8;               // fold entries per lane (512 per pass; wider
                                        // passes measured slower: 16 +25 %, 32 +65 %)
 static_assert(kCHSlots <= 2 * kWave, "the slot scan: two slots per lane of one wave");
 static_assert(kCHW < (1 << 16), "packed 16-bit counts");
@@ -379,10 +218,7 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
   const int st = threadIdx.x - kWave;       // scanning thread index
   const uint64_t lt = (1ull << lane) - 1ull;
   const int n = S.n_obs;
-  const bool ramp = S.lf > 0 && S.lf < n;
-  const int64_t num = n - S.lf;
-  const double start = 1.0 / (double)n;
-  const double step = (ramp && num > 1) ? (1.0 - start) / (double)(num - 1) : 0.0;
+  const LfRamp lfw(n, S.lf);
   double cnt = 0.0;     // (wave 0)
   int64_t folded = 0;  // (wave 0) matches folded so far
   int64_t carry = 0;   // (scanners) observations before the window
@@ -397,15 +233,10 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
       const int64_t p0 = it * kCHW;
 #pragma unroll
       for (int t = 0; t < kCHT; ++t) {
-        const int64_t i = p0 + (int64_t)t * (kCHScan * kWave) + st;
-        mem[t] = hit[t] = false;
-        if (i < n_rows) {
-          const int64_t r = rows ? (int64_t)rows[i] : i;
-          const bool a = Ac[r] != 0;
-          const double v = V[r];  // (read unconditionally: one latency, not two)
-          mem[t] = a && is_below[i] == side;
-          hit[t] = mem[t] && (int64_t)v - G.offset == (int64_t)k;
-        }
+        int cat;
+        cath_row(V, Ac, rows, is_below, p0 + (int64_t)t * (kCHScan * kWave) + st, n_rows, side,
+                 G.offset, S.n_cat, mem[t], cat);
+        hit[t] = cat == k;  // (0 <= k < n_cat)
       }
 #pragma unroll
       for (int t = 0; t < kCHT; ++t) {
@@ -417,11 +248,7 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
     }
     if (wid == 0 && it > 0) {
       const int nh = (int)(s_tot[buf ^ 1] & 0xffffu);
-#ifdef TPE_DIAG_CAT_NOFOLD  // (diagnostic builds: the scan alone)
-      if (nh > 0) cnt += s_w[buf ^ 1][nh - 1];
-#else
       cnt = fold_list<kCHSE>(cnt, s_w[buf ^ 1], nh, folded, lane);
-#endif
     }
     __syncthreads();
     if (!scan) break;
@@ -448,14 +275,7 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
       for (int t = 0; t < kCHT; ++t) {
         if (hit[t]) {
           const uint32_t ex = s_slot[t * kCHScan + sw] + pre[t];
-          const int64_t pos = carry + (int64_t)(ex >> 16);
-          double wt = 1.0;
-          if (ramp && pos < num) {
-            if (num == 1) wt = start;
-            else if (pos == num - 1) wt = 1.0;
-            else wt = __dadd_rn(__dmul_rn((double)pos, step), start);
-          }
-          s_w[buf][ex & 0xffffu] = wt;
+          s_w[buf][ex & 0xffffu] = lfw.at(carry + (int64_t)(ex >> 16));
         }
       }
       carry += (int64_t)(s_tot[buf] >> 16);
@@ -465,16 +285,7 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
   if (threadIdx.x == kWave) {  // (a scanner holds the observation count)
     if (carry != (int64_t)n && err) atomicOr(err, 4);
   }
-  if (threadIdx.x == 0) {
-    double pseudo;
-    if (S.mode == 0) {
-      pseudo = cnt + S.prior_weight;  // tpe.py:589
-    } else {
-      const double pk = p[S.prior_p_off + k];
-      pseudo = cnt + (double)S.n_cat * (S.prior_weight * pk);  // tpe.py:603
-    }
-    p[S.p_off + k] = pseudo;
-  }
+  if (threadIdx.x == 0) cat_pseudocount(S, p, k, cnt);
 }
 
 // Long histories (n_rows >= kCathMinRows, at most kCathMaxCat categories):
@@ -487,8 +298,9 @@ __global__ __launch_bounds__(kCHB) void k_cat_counts_hist(
 //                 the segment (chunk base + wave base + rank in the tile) gives
 //                 its LF weight, every match its place in its category's list,
 //                 in row order -- the lists the single-block kernel folds;
-//   k_cath_fold   one wave per (segment, category): the list folded in order
-//                 (fold_list: the serial chain's bits), staged through LDS.
+//   k_cath_fold   one block of 8 waves per (segment, category): the list folded
+//                 in order (block_fold_list: the serial chain's bits), staged
+//                 through LDS 4 096 entries at a time.
 constexpr int kCathMinRows = 32768;
 constexpr int kCathMaxCat = 32;
 constexpr int kCC = 4096;                 // rows per chunk
@@ -503,47 +315,24 @@ __host__ __device__ inline int64_t cath_count_bytes(int n_seg, int64_t n_rows) {
   return ((int64_t)4 * n_seg * cath_chunks(n_rows) * kCathStride + 255) & ~(int64_t)255;
 }
 
-// row i of the walk: a member of the segment (active label, the segment's
-// side of the split) and its category (-1: none of 0..n_cat-1)
-__device__ __forceinline__ void cath_row(const double* __restrict__ V,
-                                         const uint8_t* __restrict__ Ac,
-                                         const int32_t* __restrict__ rows,
-                                         const uint8_t* __restrict__ is_below, int64_t i,
-                                         int64_t n_rows, uint8_t side, int64_t offset, int n_cat,
-                                         bool& mem, int& cat) {
-  mem = false;
-  cat = -1;
-  if (i < n_rows) {
-    const int64_t r = rows ? (int64_t)rows[i] : i;
-    const bool a = Ac[r] != 0;
-    const double v = V[r];
-    mem = a && is_below[i] == side;
-    const int64_t cv = (int64_t)v - offset;  // (k_cat_counts_hist's test)
-    if (mem && cv >= 0 && cv < (int64_t)n_cat) cat = (int)cv;
-  }
-}
-
-__global__ __launch_bounds__(kCathBS) void k_cath_count(
-    const double* __restrict__ vals, const uint8_t* __restrict__ active, int64_t ld,
-    const int32_t* __restrict__ rows, int64_t n_rows, const uint8_t* __restrict__ is_below,
-    const tpe_gather* __restrict__ gathers, const tpe_cat_seg* __restrict__ segs,
-    uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t s_c[kCathW][kCathStride];
-  const int seg = blockIdx.y, c = blockIdx.x;
-  const tpe_cat_seg S = segs[seg];
-  const tpe_gather G = gathers[seg];
-  const double* __restrict__ V = vals + (int64_t)G.col * ld;
-  const uint8_t* __restrict__ Ac = active + (int64_t)G.col * ld;
-  const uint8_t side = G.below ? 1 : 0;
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  const int K = S.n_cat;
-  bool mem[kCathT];
-  int cat[kCathT];
-  const int64_t r0 = (int64_t)c * kCC + (int64_t)w * kCathRPW;
+// A chunk block's prologue, in two steps (as one helper k_cath_emit took 72
+// VGPRs instead of 56): this wave's rows of the chunk loaded (cath_row's
+// arguments; i0: this lane's first row, the others every 64) ...
+__device__ __forceinline__ void cath_load(
+    const double* __restrict__ V, const uint8_t* __restrict__ Ac,
+    const int32_t* __restrict__ rows, const uint8_t* __restrict__ is_below, int64_t i0,
+    int64_t n_rows, uint8_t side, int64_t offset, int K, bool (&mem)[kCathT],
+    int (&cat)[kCathT]) {
 #pragma unroll
   for (int t = 0; t < kCathT; ++t)
-    cath_row(V, Ac, rows, is_below, r0 + t * kWave + lane, n_rows, side, G.offset, K, mem[t],
-             cat[t]);
+    cath_row(V, Ac, rows, is_below, i0 + t * kWave, n_rows, side, offset, K, mem[t], cat[t]);
+}
+// ... and counted by ballots: the wave's members in s_c[wave][0], its matches
+// of category k in s_c[wave][1 + k]
+__device__ __forceinline__ void cath_count(int K, const bool (&mem)[kCathT],
+                                           const int (&cat)[kCathT],
+                                           uint32_t (*s_c)[kCathStride]) {
+  const int lane = lane_id(), w = threadIdx.x / kWave;
   uint32_t nm = 0;
 #pragma unroll
   for (int t = 0; t < kCathT; ++t) nm += (uint32_t)__popcll(__ballot(mem[t]));
@@ -554,6 +343,23 @@ __global__ __launch_bounds__(kCathBS) void k_cath_count(
     for (int t = 0; t < kCathT; ++t) nk += (uint32_t)__popcll(__ballot(cat[t] == k));
     if (lane == 0) s_c[w][1 + k] = nk;
   }
+}
+
+__global__ __launch_bounds__(kCathBS) void k_cath_count(
+    const double* __restrict__ vals, const uint8_t* __restrict__ active, int64_t ld,
+    const int32_t* __restrict__ rows, int64_t n_rows, const uint8_t* __restrict__ is_below,
+    const tpe_gather* __restrict__ gathers, const tpe_cat_seg* __restrict__ segs,
+    uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_c[kCathW][kCathStride];
+  const int seg = blockIdx.y, c = blockIdx.x;
+  const int K = segs[seg].n_cat;
+  const tpe_gather G = gathers[seg];
+  bool mem[kCathT];
+  int cat[kCathT];
+  const int64_t r0 = (int64_t)c * kCC + (int64_t)(threadIdx.x / kWave) * kCathRPW;
+  cath_load(vals + (int64_t)G.col * ld, active + (int64_t)G.col * ld, rows, is_below,
+            r0 + lane_id(), n_rows, G.below ? 1 : 0, G.offset, K, mem, cat);
+  cath_count(K, mem, cat, s_c);
   __syncthreads();
   uint32_t* out = cnt + ((int64_t)seg * gridDim.x + c) * kCathStride;
   for (int j = threadIdx.x; j < 1 + K; j += kCathBS) {
@@ -576,30 +382,15 @@ __global__ __launch_bounds__(kCathBS) void k_cath_emit(
   const int seg = blockIdx.y, c = blockIdx.x, nch = gridDim.x;
   const tpe_cat_seg S = segs[seg];
   const tpe_gather G = gathers[seg];
-  const double* __restrict__ V = vals + (int64_t)G.col * ld;
-  const uint8_t* __restrict__ Ac = active + (int64_t)G.col * ld;
-  const uint8_t side = G.below ? 1 : 0;
   const int lane = lane_id(), w = threadIdx.x / kWave;
   const uint64_t lt = (1ull << lane) - 1ull;
   const int K = S.n_cat;
   bool mem[kCathT];
   int cat[kCathT];
   const int64_t r0 = (int64_t)c * kCC + (int64_t)w * kCathRPW;
-#pragma unroll
-  for (int t = 0; t < kCathT; ++t)
-    cath_row(V, Ac, rows, is_below, r0 + t * kWave + lane, n_rows, side, G.offset, K, mem[t],
-             cat[t]);
-  // this wave's members and matches
-  uint32_t nm = 0;
-#pragma unroll
-  for (int t = 0; t < kCathT; ++t) nm += (uint32_t)__popcll(__ballot(mem[t]));
-  if (lane == 0) s_w[w][0] = nm;
-  for (int k = 0; k < K; ++k) {
-    uint32_t nk = 0;
-#pragma unroll
-    for (int t = 0; t < kCathT; ++t) nk += (uint32_t)__popcll(__ballot(cat[t] == k));
-    if (lane == 0) s_w[w][1 + k] = nk;
-  }
+  cath_load(vals + (int64_t)G.col * ld, active + (int64_t)G.col * ld, rows, is_below, r0 + lane,
+            n_rows, G.below ? 1 : 0, G.offset, K, mem, cat);
+  cath_count(K, mem, cat, s_w);
   // the chunks before this one, and the segment's totals per category
   const uint32_t* C = cnt + (int64_t)seg * nch * kCathStride;
   for (int j = threadIdx.x; j < 1 + K; j += kCathBS) {
@@ -633,11 +424,7 @@ __global__ __launch_bounds__(kCathBS) void k_cath_emit(
   }
   __syncthreads();
   // the wave's tiles in row order: member positions -> LF weights -> list slots
-  const int n = S.n_obs;
-  const bool ramp = S.lf > 0 && S.lf < n;
-  const int64_t num = n - S.lf;
-  const double start = 1.0 / (double)n;
-  const double step = (ramp && num > 1) ? (1.0 - start) / (double)(num - 1) : 0.0;
+  const LfRamp lfw(S.n_obs, S.lf);
   int64_t mpos = s_cur[w][0];
 #pragma unroll
   for (int t = 0; t < kCathT; ++t) {
@@ -653,167 +440,8 @@ __global__ __launch_bounds__(kCathBS) void k_cath_emit(
       if (lane == 0) s_cur[w][1 + k] = base + __popcll(kb);
       __builtin_amdgcn_wave_barrier();
     }
-    if (slot >= 0) {
-      double wt = 1.0;
-      if (ramp && pos < num) {
-        if (num == 1) wt = start;
-        else if (pos == num - 1) wt = 1.0;
-        else wt = __dadd_rn(__dmul_rn((double)pos, step), start);
-      }
-      lists[slot] = wt;
-    }
+    if (slot >= 0) lists[slot] = lfw.at(pos);
   }
-}
-
-// seq_fold across a whole block (kFW waves): the same binade-grid steps, the
-// parity maps and the integer increments scanned over the block (wave scans,
-// then the waves' totals through LDS), so one pass covers kSE * 64 * kFW
-// entries -- a long chain's ~50k weights take ~15 passes instead of ~100
-// (a pass is a latency-bound chain of dependent steps, not throughput).
-// Every thread returns the same S (block-uniform control).
-#ifndef TPE_FOLD_WAVES  // diagnostic builds: k_cath_fold's waves and entries per lane
-#define TPE_FOLD_WAVES 8
-#endif
-#ifndef TPE_FOLD_SE
-#define TPE_FOLD_SE 8
-#endif
-constexpr int kFW = TPE_FOLD_WAVES;   // waves of k_cath_fold
-constexpr int kFB = kFW * kWave;      // its block
-constexpr int kFSE = TPE_FOLD_SE;     // entries per lane per pass
-constexpr int kFoldN = kFSE * kFB;    // entries per pass / per staged chunk (4 096)
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, kWave);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, kWave);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
-         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-}
-struct FoldX {
-  uint32_t wmap[kFW];        // each wave's composed parity map (inclusive)
-  uint64_t wsum[kFW];        // each wave's increment total
-  int64_t wcross[kFW];       // each wave's first leaving entry (-1: none) ...
-  uint64_t wcum[kFW];        // ... and the increments before it
-  double S;                  // (the serial prefix's result, broadcast)
-};
-__device__ double block_seq_fold(double S, const double* list, int n, FoldX& X) {
-  constexpr int kSE = kFSE;
-  const int lane = lane_id(), wid = threadIdx.x / kWave;
-  double v[kSE];
-#pragma unroll
-  for (int j = 0; j < kSE; ++j) {
-    const int i = threadIdx.x * kSE + j;
-    v[j] = i < n ? list[i] : 0.0;
-  }
-  constexpr uint64_t kFrac = (1ull << 52) - 1, kTop = 1ull << 53;
-  int r0 = 0;
-  while (r0 < n) {  // (block-uniform)
-    const uint64_t sb = (uint64_t)__double_as_longlong(S);
-    const int es = (int)((sb >> 52) & 0x7ff);
-    if (S == 0.0 || es == 0) {
-      S = __dadd_rn(S, list[r0]);
-      ++r0;
-      continue;
-    }
-    const uint64_t A = (sb & kFrac) | (1ull << 52);
-    uint64_t d[kSE];
-    uint32_t tie = 0, huge = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      const int i = threadIdx.x * kSE + j;
-      d[j] = fold_step(v[j], es, i >= r0 && i < n, tie, huge, j);
-    }
-    uint32_t a = 1, c = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if ((tie >> j) & 1u) {
-        a = 0;
-        c = 0;
-      } else {
-        c ^= (uint32_t)(d[j] & 1ull);
-      }
-    }
-    uint32_t x = a | (c << 1);
-    scan_step_map<0x111, 0xF>(x);
-    scan_step_map<0x112, 0xF>(x);
-    scan_step_map<0x114, 0xF>(x);
-    scan_step_map<0x118, 0xF>(x);
-    scan_step_map<0x142, 0xA>(x);
-    scan_step_map<0x143, 0xC>(x);
-    const uint32_t ex = dpp_u32<0x138, 0xF>(1u, x);  // the wave's lanes before this one
-    if (lane == kWave - 1) X.wmap[wid] = x;
-    __syncthreads();
-    // the waves before this one, composed in order: lane q < wid holds wave
-    // q's map (the others the identity), an ordered scan over 16 lanes
-    uint32_t pre = (lane < kFW && lane < wid) ? X.wmap[lane] : 1u;
-#pragma unroll
-    for (int o = 1; o < kFW; o <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)pre, o, kWave);
-      pre = lane >= o ? map_then(y, pre) : pre;
-    }
-    pre = (uint32_t)__builtin_amdgcn_readlane((int)pre, kFW - 1);
-    const uint32_t in = map_then(pre, ex);
-    uint32_t P = ((in & 1u) & (uint32_t)(A & 1ull)) ^ (in >> 1);
-    uint64_t tot = 0;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if ((tie >> j) & 1u) {
-        d[j] += (P + d[j]) & 1ull;  // ties to the even A_{k+1}
-        P = 0;
-      } else {
-        P ^= (uint32_t)(d[j] & 1ull);
-      }
-      tot += d[j];
-    }
-    const uint64_t incl = wave_prefix_sum_u64(tot);
-    if (lane == kWave - 1) X.wsum[wid] = incl;
-    __syncthreads();
-    // the waves' increment totals: before this wave, and all of them
-    const uint64_t wsl = lane < kFW ? X.wsum[lane] : 0ull;
-    uint64_t base = lane < wid ? wsl : 0ull, all = wsl;
-#pragma unroll
-    for (int o = 1; o < kFW; o <<= 1) {  // (lanes 0..15 reduce; lane 0's sums broadcast)
-      base += shfl_xor_u64(base, o);
-      all += shfl_xor_u64(all, o);
-    }
-    base = readlane_u64(base, 0);
-    all = readlane_u64(all, 0);
-    uint64_t cum = base + incl - tot;
-    int jc = -1;
-#pragma unroll
-    for (int j = 0; j < kSE; ++j) {
-      if (jc < 0) {
-        if (((huge >> j) & 1u) || A + cum + d[j] >= kTop) jc = j;
-        else cum += d[j];
-      }
-    }
-    const uint64_t bal = __ballot(jc >= 0);
-    if (lane == 0) {
-      if (bal == 0) {
-        X.wcross[wid] = -1;
-      } else {
-        const int L = __ffsll((unsigned long long)bal) - 1;
-        X.wcross[wid] = (int64_t)(wid * kWave + L) * kSE + __builtin_amdgcn_readlane(jc, L);
-        X.wcum[wid] =
-            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cum >> 32), L) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cum, L);
-      }
-    }
-    __syncthreads();
-    const uint64_t cb = __ballot(lane < kFW && X.wcross[lane < kFW ? lane : 0] >= 0);
-    const int qc = cb ? __ffsll((unsigned long long)cb) - 1 : -1;  // the first wave leaving
-    if (qc < 0) {
-      S = ldexp((double)(A + all), es - 1075);
-      r0 = n;
-    } else {
-      const int g = (int)X.wcross[qc];
-      S = __dadd_rn(ldexp((double)(A + X.wcum[qc]), es - 1075), list[g]);
-      r0 = g + 1;
-    }
-    __syncthreads();  // (X is rewritten by the next pass)
-  }
-  return S;
 }
 
 __global__ __launch_bounds__(kFB) void k_cath_fold(const tpe_cat_seg* __restrict__ segs,
@@ -823,7 +451,7 @@ __global__ __launch_bounds__(kFB) void k_cath_fold(const tpe_cat_seg* __restrict
                                                    double* __restrict__ p,
                                                    int32_t* __restrict__ err) {
   __shared__ double s_l[kFoldN];
-  __shared__ FoldX X;
+  __shared__ FoldX<kFW> X;
   __shared__ int64_t s_meta[3];
   const int seg = blockIdx.y, k = blockIdx.x;
   const tpe_cat_seg S = segs[seg];
@@ -852,46 +480,8 @@ __global__ __launch_bounds__(kFB) void k_cath_fold(const tpe_cat_seg* __restrict
   __syncthreads();
   const int64_t n_k = s_meta[1];
   const double* L = lists + (int64_t)seg * n_rows + s_meta[0];
-  double cntv = 0.0;
-  int64_t done = 0;
-  for (int64_t f0 = 0; f0 < n_k; f0 += kFoldN) {
-    const int m = (int)min((int64_t)kFoldN, n_k - f0);
-    double t[kFSE];
-#pragma unroll
-    for (int u = 0; u < kFSE; ++u) {  // (all loads in flight, then the stores)
-      const int i = u * kFB + (int)threadIdx.x;
-      t[u] = i < m ? L[f0 + i] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kFSE; ++u) {
-      const int i = u * kFB + (int)threadIdx.x;
-      if (i < m) s_l[i] = t[u];
-    }
-    __syncthreads();
-    int f = 0;
-    if (done < kSerialHits) {  // the chain's first entries: one thread, one add each
-      f = (int)min((int64_t)m, kSerialHits - done);
-      if (threadIdx.x < kWave) {
-        const double sv = serial_fold(cntv, s_l, f, lane);
-        if (threadIdx.x == 0) X.S = sv;
-      }
-      __syncthreads();
-      cntv = X.S;
-    }
-    if (f < m) cntv = block_seq_fold(cntv, s_l + f, m - f, X);
-    done += m;
-    __syncthreads();  // (s_l is restaged next)
-  }
-  if (threadIdx.x == 0) {
-    double pseudo;
-    if (S.mode == 0) {
-      pseudo = cntv + S.prior_weight;  // tpe.py:589
-    } else {
-      const double pk = p[S.prior_p_off + k];
-      pseudo = cntv + (double)S.n_cat * (S.prior_weight * pk);  // tpe.py:603
-    }
-    p[S.p_off + k] = pseudo;
-  }
+  const double cntv = block_fold_list<kFSE, kFW>(0.0, L, n_k, 0, s_l, X);
+  if (threadIdx.x == 0) cat_pseudocount(S, p, k, cntv);
 }
 
 // normalise (numpy pairwise sum), log p (categorical_lpdf, tpe.py:60-73) and

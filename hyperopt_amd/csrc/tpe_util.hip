@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "tpe_common.hpp"
+#include "tpe_fold.hpp"
 
 namespace tpe {
 namespace {
@@ -277,4 +278,50 @@ extern "C" int tpe_check_transcendentals(double* out, void* stream) {
   hipLaunchKernelGGL(tpe::k_ulp_check, dim3(8192), dim3(256), 0, st,
                      reinterpret_cast<unsigned long long*>(out));
   return tpe::check_launch("tpe_check_transcendentals");
+}
+
+// ---------------------------------------------------------------------------
+// The categorical counts' exact fold (tpe_fold.hpp) on a caller's list, so a
+// test can feed it what the LF ramp never does (ties, wide ranges, sums
+// started near 2^53): one wave (scope 0: fold_list<8>, k_cat_counts' and
+// k_cat_counts_hist's driver) or one block (scope 1: block_fold_list,
+// k_cath_fold's) folds list[0, n) into s0 as if `done` entries of the chain
+// had been folded before.  (Here and not in tpe_fit.hip: DESIGN.md 3, the
+// note after the source map.)
+// ---------------------------------------------------------------------------
+namespace tpe {
+namespace {
+__global__ __launch_bounds__(kWave) void k_fold_check_wave(const double* __restrict__ list, int n,
+                                                           double s0, int64_t done,
+                                                           double* __restrict__ out) {
+  const double s = fold_list<8>(s0, list, n, done, lane_id());
+  if (threadIdx.x == 0) out[0] = s;
+}
+__global__ __launch_bounds__(kFB) void k_fold_check_block(const double* __restrict__ list,
+                                                          int64_t n, double s0, int64_t done,
+                                                          double* __restrict__ out) {
+  __shared__ double s_l[kFoldN];
+  __shared__ FoldX<kFW> X;
+  const double s = block_fold_list<kFSE, kFW>(s0, list, n, done, s_l, X);
+  if (threadIdx.x == 0) out[0] = s;
+}
+}  // namespace
+}  // namespace tpe
+
+extern "C" int tpe_fold_check(const double* list, int64_t n, double s0, int64_t done, int scope,
+                              double* out, void* stream) {
+  if (n < 0 || n > INT32_MAX || done < 0 || (n > 0 && !list) || !out ||
+      (scope != 0 && scope != 1)) {
+    tpe::set_error("tpe_fold_check: bad arguments (n=%lld done=%lld scope=%d)", (long long)n,
+                   (long long)done, scope);
+    return TPE_E_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (scope == 0)
+    hipLaunchKernelGGL(tpe::k_fold_check_wave, dim3(1), dim3(tpe::kWave), 0, st, list, (int)n, s0,
+                       done, out);
+  else
+    hipLaunchKernelGGL(tpe::k_fold_check_block, dim3(1), dim3(tpe::kFB), 0, st, list, n, s0, done,
+                       out);
+  return tpe::check_launch("tpe_fold_check");
 }

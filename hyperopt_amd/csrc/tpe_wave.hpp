@@ -75,6 +75,18 @@ __device__ __forceinline__ uint64_t wave_prefix_sum_u64(uint64_t v) {
   return v;
 }
 
+// 64-bit lane exchanges as two 32-bit ones: lane l's value in every lane
+// (l wave-uniform), and the butterfly partner's
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, kWave);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, kWave);
+  return ((uint64_t)hi << 32) | lo;
+}
+
 // block reductions; result valid in every thread.  `sh` holds >= BS / 64 T.
 template <int BS, typename T>
 __device__ __forceinline__ T block_sum(T v, T* sh) {

@@ -823,6 +823,18 @@ int tpe_abi_version(void);
  * |v_log_f32(p) - log2 p| / max(1, |log2 p|).  Exhaustive (2^32 inputs, a
  * few ms); out: 2 doubles (device), asynchronous on `stream`. */
 int tpe_check_transcendentals(double* out, void* stream);
+/* Self-check of the categorical counts' exact fold (np.bincount's sequential
+ * fp64 sum): one launch folds list[0, n) (device) into s0 in
+ * order and writes the sum to out[0] (device), asynchronous on `stream`.
+ * scope 0: one wave (the driver of tpe_cat_posterior and of the single-block
+ * history count); scope 1: one block (the driver of the chunked history
+ * count).  The chain is treated as if `done` entries had been folded before:
+ * the first 4096 entries of a chain are added serially, so done >= 4096 skips
+ * that prefix and done = 4000 ends it 96 entries into the list.
+ * Precondition: every entry and s0 finite and >= 0.  The result must equal
+ * the serial chain s = s + w bit for bit. */
+int tpe_fold_check(const double* list, int64_t n, double s0, int64_t done, int scope, double* out,
+                   void* stream);
 
 /* host: writes sizeof(tpe_seg, tpe_cat_seg, tpe_job, tpe_best, tpe_table, tpe_gather,
  * tpe_history, tpe_prior, tpe_op, tpe_band, tpe_colspec) to out[0..n); returns 11 */

@@ -42,6 +42,18 @@ def test_struct_sizes_and_abi():
     assert L.OP_DTYPE.itemsize == 192
 
 
+def test_fold_check_argument_errors():
+    """tpe_fold_check rejects a negative n or done, a missing list or output
+    and an unknown scope before it launches anything."""
+    lib = L.load()
+    buf = (ctypes.c_double * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for args in ((p, -1, 0.0, 0, 0, p), (p, 4, 0.0, -1, 0, p), (None, 4, 0.0, 0, 0, p),
+                 (p, 4, 0.0, 0, 2, p), (p, 4, 0.0, 0, 1, None)):
+        assert lib.tpe_fold_check(*args, None) == -1, args
+        assert b"tpe_fold_check" in lib.tpe_last_error()
+
+
 def _ops(*records):
     ops = np.zeros(len(records), L.OP_DTYPE)
     for i, (code, args) in enumerate(records):

@@ -146,6 +146,41 @@ def test_history_categorical_counts_long(engine, T, K):
         np.testing.assert_array_equal(res[j].extra["p_above"], want, err_msg=lab)
 
 
+@pytest.mark.parametrize("T", [7680, 7681])
+@pytest.mark.parametrize("m", [4095, 4096, 4097, 4096 + 512, 4096 + 513])
+def test_history_categorical_counts_serial_to_pass_handover(engine, T, m):
+    """The single block per (set, category) (k_cat_counts_hist: fewer than
+    32 768 rows) where a chain leaves its serial prefix inside the kernel: a
+    two-category label whose dominant category has exactly m observations on
+    the above side, 15 % of the rows inactive, the history one window of
+    7 680 rows long and one row longer.  Bit-exact against the oracle."""
+    from hyperopt_amd.engine import DeviceHistory, LabelWork
+    from tests.fold_cases import two_category_column
+    rows = np.arange(T)
+    act = ~np.isin(rows % 20, (3, 10, 17))
+    losses = np.cos(0.37 * rows)  # (deterministic, no ties among the best)
+    n_below = min(int(np.ceil(0.25 * np.sqrt(T))), 25)
+    isb = np.zeros(T, np.uint8)
+    isb[np.argsort(losses, kind="stable")[:n_below]] = 1
+    above = act & (isb == 0)
+    col = (rows % 2).astype(np.int64)  # (below and inactive rows: either category)
+    col[above] = two_category_column(int(above.sum()), m)
+    mat = np.stack([col.astype(float), (col + 2).astype(float)], axis=1)
+    active = np.stack([act, act], axis=1)
+    hist = DeviceHistory(engine, 2)
+    hist.append(mat, active)
+    p = np.array([0.6, 0.4])
+    specs = [("c", "categorical", (tuple(p.tolist()),)), ("r", "randint", (2, 4))]
+    works = [LabelWork(lab, kind, a, mat[act & (isb == 1), j], None, col=j,
+                       n_above=int(above.sum()))
+             for j, (lab, kind, a) in enumerate(specs)]
+    res = engine.run(works, posteriors=True, history=hist, is_below=isb)
+    np.testing.assert_array_equal(res[0].extra["p_above"],
+                                  O.categorical_posterior(col[above], 1.0, p))
+    np.testing.assert_array_equal(res[1].extra["p_above"],
+                                  O.randint_posterior(col[above] + 2, 1.0, 2, 4))
+
+
 def _suggest_both(monkeypatch, trials, domain, n_ei, seed=7):
     from hyperopt_amd import tpe
     out = []

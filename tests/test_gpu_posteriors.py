@@ -103,10 +103,30 @@ def test_p_accept_bounded(engine):
         np.testing.assert_allclose(r.extra["p_accept"][k], ref, rtol=1e-12)
 
 
+@pytest.mark.parametrize("m", [4095, 4096, 4097, 4096 + 512, 4096 + 513])
+def test_categorical_counts_serial_to_pass_handover(engine, m):
+    """Uploaded lists (k_cat_counts) at the smallest sizes where a chain leaves
+    its serial prefix inside the kernel: the dominant category of a
+    two-category label has exactly m observations on the above side -- the
+    prefix alone (4095, 4096), one entry for the passes (4097), one full pass
+    (4096 + 512) and one more entry (4096 + 513)."""
+    from hyperopt_amd.engine import LabelWork
+    from tests.fold_cases import two_category_column
+    above = two_category_column(m + 600, m)
+    below = above[:25]
+    p = np.array([0.7, 0.3])
+    works = [LabelWork("c", "categorical", (tuple(p.tolist()),), below, above),
+             LabelWork("r", "randint", (3, 5), below + 3, above + 3)]
+    rc, rr = engine.run(works, prior_weight=1.0, posteriors=True)
+    np.testing.assert_array_equal(rc.extra["p_above"], O.categorical_posterior(above, 1.0, p))
+    np.testing.assert_array_equal(rc.extra["p_below"], O.categorical_posterior(below, 1.0, p))
+    np.testing.assert_array_equal(rr.extra["p_above"], O.randint_posterior(above + 3, 1.0, 3, 5))
+
+
 @pytest.mark.parametrize("n,k", [(3000, 3), (60000, 3), (150000, 7), (40000, 40)])
 def test_categorical_counts_long_histories(engine, n, k):
     """Categorical / randint pseudocounts over long LF-ramped histories (the
-    wave-parallel exact fold, tpe_fit.hip seq_fold, crossing many binades):
+    wave-parallel exact fold, tpe_fold.hpp fold_pass, crossing many binades):
     bit-exact against np.bincount's sequential sums."""
     from hyperopt_amd.engine import LabelWork
     rng = np.random.RandomState(n + k)
