@@ -507,7 +507,8 @@ __host__ __device__ inline double mix_eps(int items, bool coop, double ab) {
   const int K = (items + stride - 1) / stride + 5 + (coop ? 5 : 0);  // fp64 adds into one P_n
   const double E1 = exp(ab), E2 = E1 * E1;
   return 4.4e-7                         // series truncation (tools/table_bounds.py)
-         + 1.0e-10                      // components below the exclusion floor
+         + exp(-kTauExtra) * 1.0001     // components below the exclusion floor: at most M, each
+                                        // < e^-tau / M of S (4.2e-8 at tau = 17)
          + 0.6932 * u + 1e-13           // each term's exponent: its fraction rounded to fp32
          + 0x1.0p-22                    // v_exp_f32 (checked exhaustively, tpe_check_transcendentals)
          + 5.5 * u * ab                 // A, B rounded to fp32
@@ -729,7 +730,9 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(TPE_BUILD_W
     float* __restrict__ cells, unsigned long long* __restrict__ stats) {
   const tpe_job J = jobs[blockIdx.y];
   const tpe_table Tb = tables[blockIdx.y];
-  const Grid g = grid_of(Tb, J.tbl_cap);
+  const tpe_seg SB = segs[J.below], SA = segs[J.above];
+  static_assert(kRefineCells <= kCoopCells, "a refined grid builds cooperatively");
+  const Grid g = grid_of(Tb, J.tbl_cap, SB.n_obs + SA.n_obs + 2);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     tpe_table* W = tables + blockIdx.y;
     W->origin = g.origin;
@@ -739,7 +742,6 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(TPE_BUILD_W
     W->nb = g.nb;
     W->slope = 0.0f;  // raised by k_table_score (the next launch)
   }
-  const tpe_seg SB = segs[J.below], SA = segs[J.above];
   const int wid = threadIdx.x / kWave, row = lane_id() >> 4;
   float* region = cells + J.tbl_off * (kSlotB / 4);
   __shared__ BuildLds X;

@@ -31,9 +31,11 @@
 // most 1.4e-7; the scorer evaluates that fp16 tail in fp16 arithmetic, which
 // adds at most 4.4e-7 (tools/table_bounds.py 9 evaluates the three maxima).
 // Components whose largest term anywhere in the candidate range is below
-// exp(-25)/M of the prior component's smallest term there (a lower bound of S
-// everywhere) are left out (together < 1.4e-11 of S); the rest are found per
-// cell through reach windows over the sorted means.
+// exp(-tau)/M of the prior component's smallest term there (a lower bound of S
+// everywhere) are left out: at most M of them, so together < exp(-tau) of S --
+// 4.2e-8 at the table's tau = 17 (TPE_TAU_TABLE, tpe_table.hip), which mix_eps
+// charges; the rest are found per cell through reach windows over the sorted
+// means.
 // The plan step chooses h so that every component that can be included in
 // any cell satisfies the bound; if the cell budget (job.tbl_cap) forces a
 // larger h, failing cells are flagged and their candidates take the exact
@@ -96,7 +98,19 @@ struct Grid {
 __device__ __forceinline__ float cell_centre(float origin, float h, int c) {
   return fmaf((float)(2 * c + 1), h, origin);
 }
-__device__ __forceinline__ Grid grid_of(const tpe_table& Tb, int64_t cap) {
+// A small job's grid is refined: the score cubic's error falls with h^4, and
+// on the cells that the series bound alone admits a below mixture of a few
+// components against a few hundred leaves 5-17 % of the sampler's mass (44 %
+// for a 3-trial history) on cells whose cubic misses kFitTol -- those
+// candidates then take the two-polynomial cell.  The build costs cells x
+// components, so a job of at most kRefineComps components (both mixtures)
+// gets up to kRefine times the cells the series bound asks for, never past
+// kRefineCells (it stays a cooperative build) nor the job's budget.  Larger
+// jobs (C3: 10^4 components) keep their grid.
+constexpr int kRefine = 4;
+constexpr int kRefineComps = 1024;
+constexpr int kRefineCells = 4096;
+__device__ __forceinline__ Grid grid_of(const tpe_table& Tb, int64_t cap, int n_comp) {
   const double span = Tb.hi - Tb.lo;
   double hn = fmin(Tb.h_below, Tb.h_above);
   if (!(hn > 0.0) || !isfinite(hn)) hn = fmax(span, 1.0);
@@ -108,6 +122,8 @@ __device__ __forceinline__ Grid grid_of(const tpe_table& Tb, int64_t cap) {
     return g;
   }
   double n = ceil(span / (2.0 * hn));
+  if (n_comp <= kRefineComps && n < (double)kRefineCells)
+    n = fmin(n * (double)kRefine, (double)kRefineCells);
   if (!(n <= (double)cap)) n = (double)cap;
   g.nb = (int)fmax(1.0, n);
   g.h = span / (2.0 * g.nb);

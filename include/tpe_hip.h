@@ -349,8 +349,8 @@ int tpe_score_sorted(const tpe_job* jobs, const tpe_job* host_jobs, int n_jobs,
  * mixture -- truncation, the build's fp32 terms, series, sums and merges,
  * fp32/fp16 storage -- is bounded per job from the build's worst case
  * (tpe_table.eps_mix); components whose largest term
- * on the whole range is below e^-25 / M of the prior component's smallest
- * term are left out (< 1.4e-11 of the sum).
+ * on the whole range is below e^-17 / M of the prior component's smallest
+ * term are left out (together < 4.2e-8 of the sum, a term of eps_mix).
  * From those two polynomials the build also fits, per cell, a cubic of the
  * score f(u) = (m_b - m_a) + log P_b(u) - log P_a(u) at four Chebyshev nodes
  * of [-1.05, 1.05], rounds it to fp32 and BOUNDS its error against f on

@@ -25,6 +25,7 @@ import pytest
 from hyperopt_amd import _lib as L
 from tests import band_util as B
 from tests.band_util import CONT
+from tests.table_util import band_cell
 
 pytestmark = pytest.mark.gpu
 
@@ -144,22 +145,6 @@ def eng64():
 # ---------------------------------------------------------------------------
 # the table's cells, as the kernels form them
 # ---------------------------------------------------------------------------
-def band_cell(tab, y):
-    """band_cell (tpe_band.hip) in numpy: the fp32 cell of y, -2 off the grid."""
-    y = np.asarray(y, np.float32)
-    g0, h32, inv_w = np.float32(tab["origin"]), np.float32(tab["h"]), np.float32(tab["inv_w"])
-    nb = int(tab["nb"])
-    with np.errstate(all="ignore"):
-        t = (y - g0) * inv_w
-        c = np.where(t >= 0, np.minimum(t, np.float32(nb)), np.float32(0)).astype(np.int64)
-        c = np.minimum(c, nb - 1)
-        centre = ((2 * c + 1).astype(np.float64) * np.float64(h32) + np.float64(g0)) \
-            .astype(np.float32)
-        u = (y.astype(np.float64) - centre.astype(np.float64)) / float(tab["h"])
-        ok = (np.abs(u) <= np.float64(np.float32(1.05))) & (y == y)
-    return np.where(ok, c, -2)
-
-
 def y_in_cells(tab, cells, rng):
     """One fp32 y per entry of ``cells``, well inside its cell (|u| <= 0.9)."""
     cells = np.asarray(cells, np.int64)

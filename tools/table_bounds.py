@@ -12,9 +12,13 @@ On |u| <= 1.05 and over the admissible set 9|A| + 65|B| <= 5.8 this prints
     in fp16 (u rounded to fp16, one rounding per packed FMA): a relative error
     of (k + n - 6) 2^-11 on term n for k = P-6 FMAs, i.e.
     2^-11 e^{a+b} sum_n (n - 6 + P - 6) c~_n 1.05^n
-all relative to the mixture density (every term positive, P_0 >= 1).
+all relative to the mixture density (every term positive, P_0 >= 1), and
+  * the exclusion term: a component whose largest term on the range is below
+    e^-tau / M of the prior's smallest term there (a lower bound of S) is left
+    out; at most M are, so together < e^-tau of S (mix_eps charges
+    e^-tau 1.0001; tau = TPE_TAU_TABLE of tpe_table.hip)
 
-    python tools/table_bounds.py [P] [n_fp32]
+    python tools/table_bounds.py [P] [n_fp32] [tau]
 """
 import sys
 
@@ -51,9 +55,19 @@ def bounds(P=10, n32=6, lim=5.8 * (1 + 2e-5), ulim=1.0501, steps=4001):
     return trunc, fp16, horner, tail4
 
 
+TAU_TABLE = 17.0  # TPE_TAU_TABLE (tpe_table.hip)
+
+
+def excluded(tau=TAU_TABLE):
+    """mix_eps' term for the components left out below the floor."""
+    return float(np.exp(-tau) * 1.0001)
+
+
 if __name__ == "__main__":
     P = int(sys.argv[1]) if len(sys.argv) > 1 else 9
     n32 = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+    tau = float(sys.argv[3]) if len(sys.argv) > 3 else TAU_TABLE
+    print("tau=%g: components below the exclusion floor <= %.3e of S" % (tau, excluded(tau)))
     tr, h, hh, t4 = bounds(P, n32)
     print("P=%d (fp32 terms %d): truncation <= %.2e, fp16 storage <= %.2e, fp16 Horner <= %.2e, "
           "total <= %.2e; share of P_4.. (fp32 build sums) <= %.4f" % (P, n32, tr, h, hh,
