@@ -61,6 +61,10 @@ ANNEAL_DTYPE = np.dtype([("kind", "<i4"), ("n_cat", "<i4"), ("a", "<f8"), ("b", 
                          ("n_active", "<i4"), ("shrink", "<f8")], align=True)
 ANNEAL_DBG_DTYPE = np.dtype([("row", "<i4"), ("reused", "<i4"), ("g", "<i4"), ("pad_", "<i4"),
                              ("p0", "<f8"), ("p1", "<f8"), ("variate", "<f8")], align=True)
+COND_TERM_DTYPE = np.dtype([("col", "<i4"), ("value", "<i4")], align=True)
+# tpe_rows_active's program limits (tpe_hip.h TPE_COND_MAX_*)
+COND_MAX_LABELS, COND_MAX_CLAUSES, COND_MAX_TERMS = 128, 256, 256
+E_UNSUPPORTED = -3
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
 # tpe_run_ops record codes (tpe_hip.h TPE_OP_*): entry point -> code
@@ -149,6 +153,10 @@ _SIGNATURES = {
     "tpe_pool_fold": (_I, [_P, _P, _P, _P, _I, _P, _I64, _I64, _I, _P, _P, _I64, _P]),
     "tpe_pool_topk_scratch_bytes": (_I64, [_I64, _I64]),
     "tpe_pool_topk": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "tpe_rows_active": (_I, [_P, _I64, _I64, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "tpe_pool_ranges": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P]),
+    "tpe_pool_take": (_I, [_P, _P, _I64, _I, _P, _I64, _P, _P, _P]),
+    "tpe_sampled_struct_sizes": (_I, [_P, _I]),
     "tpe_grid_fold": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
@@ -235,6 +243,10 @@ def load():
     lib.tpe_anneal_struct_sizes(ctypes.cast(asz, _P), 2)
     if tuple(asz) != (ANNEAL_DTYPE.itemsize, ANNEAL_DBG_DTYPE.itemsize):
         raise ImportError("hyperopt_amd: tpe_anneal struct size mismatch %s" % (tuple(asz),))
+    ssz = (ctypes.c_int32 * 1)()
+    lib.tpe_sampled_struct_sizes(ctypes.cast(ssz, _P), 1)
+    if tuple(ssz) != (COND_TERM_DTYPE.itemsize,):
+        raise ImportError("hyperopt_amd: tpe_cond_term size mismatch %s" % (tuple(ssz),))
     _lib = lib
     return lib
 

@@ -776,6 +776,61 @@ class Domain(object):
         live.sort(key=lambda lab: order[lab])
         return live
 
+    def live_program(self):
+        """The space's liveness as a program: {label: tuple of clauses}, a
+        clause a tuple of (selector label, branch index) pairs.  A label is
+        live under a complete assignment of the selectors iff all pairs of one
+        of its clauses hold (the empty clause: always) -- the set ``reachable``
+        gives for that assignment.  None when a ``switch`` is selected by
+        anything but a bare randint(n) / categorical parameter (hp.choice,
+        hp.pchoice): an expression of labels, a randint(low, high).  Cached."""
+        cached = self.__dict__.get("_live_program", False)
+        if cached is False:
+            cached = self._live_program = self._live_program_walk()
+        return cached
+
+    def _live_program_walk(self):
+        # the walk of _reachable_walk with the path condition carried along:
+        # a node reached under several conditions is walked once per condition
+        order = {lab: i for i, lab in enumerate(self.params)}
+        clauses = {lab: set() for lab in self.params}
+        visited = set()
+        stack = [(self.expr, frozenset())]
+        while stack:
+            node, cond = stack.pop()
+            if (id(node), cond) in visited:
+                continue
+            visited.add((id(node), cond))
+            if node.name == "hyperopt_param":
+                clauses[node.pos_args[0].obj].add(cond)
+                continue
+            if node.name == "switch":
+                sel = node.pos_args[0]
+                if sel.name != "hyperopt_param":
+                    return None
+                lab = sel.pos_args[0].obj
+                spec = self.specs[lab]
+                if not (spec.kind == "categorical" or
+                        (spec.kind == "randint" and spec.args[1] is None)):
+                    return None
+                clauses[lab].add(cond)
+                held = dict(cond)
+                for b, branch in enumerate(node.pos_args[1:]):
+                    if held.get(lab, b) != b:
+                        continue  # the path already holds another branch of this selector
+                    stack.append((branch, cond | {(lab, b)}))
+                continue
+            stack.extend((n, cond) for n in node.inputs())
+        prog = {}
+        for lab in self.params:
+            cs = clauses[lab]
+            if frozenset() in cs:
+                cs = {frozenset()}
+            prog[lab] = tuple(sorted(
+                (tuple(sorted(c, key=lambda t: (order[t[0]], t[1]))) for c in cs),
+                key=lambda c: [(order[s], b) for s, b in c]))
+        return prog
+
     def memo_from_config(self, config):
         memo = {}
         for lab, node in self.hp_nodes.items():

@@ -440,6 +440,7 @@ class _LevelOpts:
     exchange: Optional[tuple] = None
     cand_ptr: int = 0
     device_outputs: bool = False
+    x_ptr: int = 0
 
     @property
     def hist_mode(self):
@@ -1113,7 +1114,7 @@ class Engine:
         for i in quant:
             if not inj(i):
                 kmin, kmax = _lattice_range(works[i], params[i])
-                if kmax - kmin + 1 > LATTICE_CAP:
+                if kmax - kmin + 1 > LATTICE_CAP or opts.x_ptr:  # (x_ptr: a value per candidate)
                     fallback.append(i)
                 else:
                     lat_ranges[i] = (kmin, kmax - kmin + 1)
@@ -1209,6 +1210,8 @@ class Engine:
                         flags |= L.F_DRAW32
                     flags |= L.F_LATTICE_READY  # cleared below for a large level
                     lat_off += nk
+                elif i in fallback and opts.x_ptr:  # drawn into the caller's buffer
+                    J["cand_off"][pos] = J["out_off"][pos]
                 elif i in fallback:
                     J["cand_off"][pos] = qfb_off
                     qfb_off += n
@@ -1247,7 +1250,7 @@ class Engine:
             pruned=True, scorer=None, posteriors=False, history=None, rows=None,
             is_below=None, histories=None, timer_groups=None,
             table_scores=False, defer=False, exchange=None, cand_ptr=0,
-            device_outputs=False) -> List[LabelResult]:
+            device_outputs=False, x_ptr=0) -> List[LabelResult]:
         """Run one level (``_run_level``); at precision 32 the labels scored by
         an fp32 argmax -- injected candidates, or per-candidate ``outputs`` --
         get the exact decision afterwards (``_exact_decision``), so every
@@ -1297,13 +1300,22 @@ class Engine:
         64).  ``device_outputs`` (with ``outputs``): the per-candidate
         log-densities stay in the workspace buffers ``out_bl`` / ``out_al``
         (``device_output_ptrs``), each result's range in ``extra["out_off"]`` /
-        ``extra["n"]``; nothing per candidate is read back."""
+        ``extra["n"]``; nothing per candidate is read back.  ``x_ptr`` (with
+        ``device_outputs``, drawn works only): a device buffer of fp64 that
+        takes the drawn values too, work i's candidates at element
+        ``extra["out_off"]`` beside its log-densities -- stored values,
+        randint(low, high) offset-free.  Quantized labels then take the dense
+        route (tpe_sample + tpe_score_quantized on the draws) instead of the
+        lattice, which keeps no value per candidate."""
         if (cand_ptr or device_outputs) and (precision != 64 or sample_only or table_scores):
             raise ValueError("cand_ptr / device_outputs: exact fp64 scoring only")
+        if x_ptr and (not (device_outputs and outputs) or cand_ptr or not isinstance(works, list)
+                      or any(w.cand is not None or w.cand_dev is not None for w in works)):
+            raise ValueError("x_ptr: drawn works with outputs=True, device_outputs=True only")
         opts = _LevelOpts(prior_weight, lf, precision, outputs, stream, timers, sample_only,
                           pruned, scorer, posteriors, history, rows, is_below, histories,
                           timer_groups, table_scores, defer, exchange, int(cand_ptr or 0),
-                          bool(device_outputs and outputs))
+                          bool(device_outputs and outputs), int(x_ptr or 0))
         res = self._run_level(works, opts)
         if precision == 32 and isinstance(works, list) and res and not (
                 sample_only or posteriors or table_scores or exchange is not None) and \
@@ -1728,6 +1740,8 @@ class Engine:
             st.d_al = self._buf("out_al", 8 * max(plan.out_off, 1))
             if not opts.device_outputs:  # (nullable in every scorer)
                 st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
+            elif opts.x_ptr:
+                st.d_x = opts.x_ptr
         elif opts.table_scores:
             st.d_sc = self._buf("out_sc", 8 * max(plan.out_off, 1))
             st.d_x = self._buf("out_x", 8 * max(plan.out_off, 1))
@@ -2077,7 +2091,7 @@ class Engine:
         d_rh, d_rl = lv.d_rh, lv.d_rl
         vals = st.d_cand
         if sl.kind == "qfb":
-            vals = self._buf("q_cand", 8 * max(lv.plan.qfb_off, 1))
+            vals = lv.opts.x_ptr or self._buf("q_cand", 8 * max(lv.plan.qfb_off, 1))
             L.check(lib.tpe_sample(lv.base + lv.o_fb,
                                    lv.plan.fb_jobs.ctypes.data_as(ctypes.c_void_p), nj, lv.d_segs,
                                    lv.d_mu, lv.d_sig, lv.d_cdf, 64, vals, ks), "tpe_sample")

@@ -26,6 +26,14 @@ selects the first k untaken rows (csrc/tpe_pool.hip).  Conditional labels are
 scored for every row (an inactive entry holds a copy of one of the column's
 live values) and masked in the fold.  Only the k row indices come back.
 
+``Pool.sample`` is the pool of a free space: row r holds candidate r of every
+label's posterior stream, the draws the exact scorers make anyway.  The rows
+never leave the device: ``tpe_rows_active`` decides each row's live labels
+from its own choices (``Domain.live_program``), the fold and the top-k are the
+ones above, and ``tpe_pool_take`` brings back the winners only
+(csrc/tpe_sampled.hip).  ``suggest_sampled`` is the ``algo`` around it: k
+distinct documents per call on any space.
+
 ``GridPool`` is the pool of a Cartesian product of per-label axes.  S is
 separable over the axes, so the scorers see every axis value once and
 ``tpe_grid_fold`` (csrc/tpe_grid.hip) decodes the rows and sums the per-value
@@ -110,14 +118,33 @@ def _validate(domain, labels, vals, active):
             raise ValueError("pool row %d, label %r: value %r %s" % (r, lab, float(v[r]), what))
     if P == 0:
         return
-    # the live set depends on the values of the switch selectors only: one
-    # reachable() per distinct selector assignment, compared with its rows
+    sel = _selectors(domain, labels)
+    js = [labels.index(lab) for lab in sel]
+    keys = np.where(active[:, js], vals[:, js], -np.inf)
+    for want, rows in _live_sets(domain, labels, sel, keys):
+        diff = active[rows] != want
+        if diff.any():
+            i, j = np.argwhere(diff)[0]
+            raise ValueError("pool row %d, label %r: %s" % (
+                int(rows[i]), labels[j],
+                "missing, but live under the row's choices" if want[j]
+                else "given, but not live under the row's choices"))
+
+
+def _selectors(domain, labels):
+    """The labels that select a ``switch`` branch, of ``labels``."""
     domain.reachable({})
     sel = getattr(domain, "_selector_labels", None)
-    sel = list(labels) if sel is None else [lab for lab in sel if lab in labels]
-    js = [labels.index(lab) for lab in sel]
-    if js:
-        keys = np.where(active[:, js], vals[:, js], -np.inf)
+    return list(labels) if sel is None else [lab for lab in sel if lab in labels]
+
+
+def _live_sets(domain, labels, sel, keys):
+    """(live mask over ``labels``, its rows) per distinct row of ``keys``, the
+    (P, len(sel)) stored values of the selectors (-inf: not decided).  The live
+    set depends on the values of the switch selectors only: one ``reachable``
+    per distinct assignment."""
+    P = keys.shape[0]
+    if len(sel):
         uniq, inverse = np.unique(keys, axis=0, return_inverse=True)
         inverse = np.asarray(inverse).reshape(-1)
     else:
@@ -127,14 +154,51 @@ def _validate(domain, labels, vals, active):
                    for i, lab in enumerate(sel) if uniq[u, i] != -np.inf}
         live = set(domain.reachable(decided))
         want = np.fromiter((lab in live for lab in labels), bool, len(labels))
-        rows = np.flatnonzero(inverse == u)
-        diff = active[rows] != want
-        if diff.any():
-            i, j = np.argwhere(diff)[0]
-            raise ValueError("pool row %d, label %r: %s" % (
-                int(rows[i]), labels[j],
-                "missing, but live under the row's choices" if want[j]
-                else "given, but not live under the row's choices"))
+        yield want, np.flatnonzero(inverse == u)
+
+
+def _host_active(domain, labels, sel, sel_vals):
+    """(P, L) activity of rows whose selectors ``sel`` hold the stored values
+    ``sel_vals`` (P, len(sel)): each row's ``reachable`` set, every selector
+    decided."""
+    active = np.zeros((sel_vals.shape[0], len(labels)), bool)
+    for want, rows in _live_sets(domain, labels, sel, np.asarray(sel_vals, np.float64)):
+        active[rows] = want
+    return active
+
+
+def program_csr(domain):
+    """``domain.live_program()`` as tpe_rows_active takes it: (label_off int32
+    (L + 1,), clause_off int32 (C + 1,), terms COND_TERM_DTYPE (T,)) in
+    ``domain.params`` order, or None without a program."""
+    prog = domain.live_program()
+    if prog is None:
+        return None
+    index = {lab: j for j, lab in enumerate(domain.params)}
+    label_off, clause_off, terms = [0], [0], []
+    for lab in domain.params:
+        for clause in prog[lab]:
+            terms.extend((index[s], int(b)) for s, b in clause)
+            clause_off.append(len(terms))
+        label_off.append(len(clause_off) - 1)
+    t = np.zeros(len(terms), _L.COND_TERM_DTYPE)
+    if terms:
+        t["col"], t["value"] = np.asarray(terms, np.int64).T
+    return np.asarray(label_off, np.int32), np.asarray(clause_off, np.int32), t
+
+
+def _range_from_extrema(spec, lo, hi, n_live):
+    """``_scoring_range`` from tpe_pool_ranges' (min, max) of the live finite
+    values (for the log-domain priors: of those > 0; the log is monotone) and
+    the number of live rows."""
+    if spec.kind not in CONTINUOUS or not n_live:
+        return 0.0, 0.0
+    P = _params(spec.kind, spec.args)
+    if lo > hi:  # no such value
+        return P["prior_mu"], P["prior_mu"]
+    if P["family"] == _L.LGMM1:
+        return float(np.log(lo)), float(np.log(hi))
+    return float(lo), float(hi)
 
 
 def _scoring_range(spec, live):
@@ -208,6 +272,26 @@ class Pool(object):
         self = cls.__new__(cls)
         self._setup(domain, labels, vals, active)
         return self
+
+    @classmethod
+    def sample(cls, domain, trials, seed, n_rows, prior_weight=1.0, gamma=0.25,
+               linear_forgetting=25, keep_terms=False):
+        """``tpe.Pool.sample(domain, trials, seed, n_rows, ...)``: the pool whose
+        row r holds candidate r of every label's posterior stream (below
+        posterior l; key ``label_key(seed, label)``, candidates [0, n_rows)), every
+        label drawn for every row.  A row's live labels are those its own choices
+        make live, and the pool is born scored: S(r) (module doc) is the fold of
+        the draws' own log l - log g, as the exact fp64 scorers leave them.
+        Nothing of size rows x labels crosses to the host.  With no observation
+        the posterior is the prior mixture; a startup rule is the caller's.
+
+        Rows are distinct as rows: on a purely discrete space two rows can hold
+        the same configuration (``Pool`` / ``GridPool`` are for enumerable
+        spaces).  A born S and a later ``score_configs`` of the same rows under the
+        same history may differ in their last bits: a log-domain label is scored
+        at its drawn log coordinate when born, at log(exp(z)) when injected."""
+        return _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting,
+                       keep_terms)
 
     def _setup(self, domain, labels, vals, active):
         _validate(domain, labels, vals, active)
@@ -290,6 +374,186 @@ class Pool(object):
             d.taken[:len(self)].copy_(t.from_numpy(self.taken))
             d.taken_current = True
         return d
+
+
+class SampledPool(Pool):
+    """The pool ``Pool.sample`` gives: born on the device, scored there
+    (``scores()``: the born S, until the pool is scored again), and an
+    ordinary ``Pool`` afterwards.  ``vals`` / ``active`` / ``n_active`` are
+    read back on first access -- ``config``, ``keep`` and a ``score_configs``
+    on another device do that; ``suggest_sampled`` without ``keep`` does not."""
+
+    def __len__(self):
+        return self._n_rows
+
+    def _born(self):
+        return self._device[self._born_on]
+
+    def _read_back(self):
+        if self._host is None:
+            d, P = self._born(), self._n_rows
+            active = np.ascontiguousarray(d.active[:, :P].cpu().numpy().T).astype(bool)
+            vals = np.ascontiguousarray(d.vals[:, :P].cpu().numpy().T)
+            for j, lab in enumerate(self.labels):
+                off = int_offset(self.domain.specs[lab])
+                if off:
+                    vals[:, j] += off
+            vals[~active] = np.nan
+            self._host = (vals, active)
+        return self._host
+
+    @property
+    def vals(self):
+        return self._read_back()[0]
+
+    @property
+    def active(self):
+        return self._read_back()[1]
+
+    @property
+    def n_active(self):
+        if self._n_active is None:
+            self._n_active = self._d_n_active.cpu().numpy()
+        return self._n_active
+
+    def scores(self):
+        """S of every row as the device last computed it (fp64 (P,))."""
+        return self._born().S[:self._n_rows].cpu().numpy()
+
+    def terms(self):
+        """The born per-label terms, (P, L), NaN where the label is not live
+        (``Pool.sample(..., keep_terms=True)``)."""
+        d = self._born()
+        if d.terms is None:
+            raise ValueError("the pool was sampled without keep_terms=True")
+        return np.ascontiguousarray(d.terms[:, :self._n_rows].cpu().numpy().T)
+
+    def device(self, eng):
+        if eng.device != self._born_on:  # another device: the host copy's mirror
+            return Pool.device(self, eng)
+        d = self._born()
+        if d.ranges is None:  # first use as injected candidates: the columns' ranges
+            t, L = eng.torch, len(self.labels)
+            specs = [self.domain.specs[lab] for lab in self.labels]
+            positive = np.asarray([s.kind in CONTINUOUS and
+                                   _params(s.kind, s.args)["family"] == _L.LGMM1
+                                   for s in specs], np.uint8)
+            out = t.empty(2 * max(L, 1), dtype=t.float64, device=eng.device)
+            sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+            P = self._n_rows
+            _L.check(eng.lib.tpe_pool_ranges(d.vals.data_ptr(), d.active.data_ptr(), P, P, L,
+                                             positive.ctypes.data, out.data_ptr(), sp),
+                     "tpe_pool_ranges")
+            ext = out.cpu().numpy()
+            with np.errstate(all="ignore"):
+                d.ranges = [_range_from_extrema(s, ext[2 * j], ext[2 * j + 1], self.n_active[j])
+                            for j, s in enumerate(specs)]
+        if not d.taken_current:
+            d.taken[:len(self)].copy_(eng.torch.from_numpy(self.taken))
+            d.taken_current = True
+        return d
+
+
+def _rows_active(eng, domain, labels, d, P, sp):
+    """The born pool's activity and per-label live counts from its own
+    selector columns: on the device by the space's program (tpe_rows_active),
+    else -- no program, or one over the kernel's limits -- one ``reachable``
+    per distinct selector assignment on the host (only the selector columns
+    come back, and the mask goes up).  Returns the counts (device int64)."""
+    t, L = eng.torch, len(labels)
+    n_active = t.zeros(max(L, 1), dtype=t.int64, device=eng.device)
+    csr = program_csr(domain)
+    if csr is not None:
+        label_off, clause_off, terms = csr
+        rc = eng.lib.tpe_rows_active(d.vals.data_ptr(), P, P, L, label_off.ctypes.data,
+                                     clause_off.ctypes.data, terms.ctypes.data, len(terms),
+                                     d.active.data_ptr(), n_active.data_ptr(), sp)
+        if rc == 0:
+            return n_active
+        if rc != _L.E_UNSUPPORTED:
+            _L.check(rc, "tpe_rows_active")
+    sel = _selectors(domain, labels)
+    js = [labels.index(lab) for lab in sel]
+    sv = d.vals[js, :P].cpu().numpy().T if js else np.zeros((P, 0))
+    for i, lab in enumerate(sel):
+        sv[:, i] += int_offset(domain.specs[lab]) or 0
+    active = _host_active(domain, labels, sel, sv)
+    d.active[:, :P].copy_(t.from_numpy(np.ascontiguousarray(active.T).view(np.uint8)))
+    n_active[:L].copy_(t.from_numpy(active.sum(0).astype(np.int64)))
+    return n_active
+
+
+def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting, keep_terms,
+            hist=None):
+    """``Pool.sample``."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    labels = list(domain.params)
+    P, L = int(n_rows), len(labels)
+    if P < 0:
+        raise ValueError("n_rows=%d" % P)
+    if P == 0:
+        return Pool.from_arrays(domain, np.zeros((0, L)), np.zeros((0, L), bool))
+    eng, obs = _history_inputs(domain, trials, gamma, hist)
+    t, lib = eng.torch, eng.lib
+    d = _DevicePool()
+    d.vals = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device)
+    d.active = t.zeros((max(L, 1), P), dtype=t.uint8, device=eng.device)
+    d.taken = t.zeros(P, dtype=t.uint8, device=eng.device)
+    d.taken_current = True
+    d.ranges = None
+    d.S = t.empty(P, dtype=t.float64, device=eng.device)
+    d.terms = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device) if keep_terms else None
+    d.rows_out = d.count = d.scratch = None
+    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    per = max(1, CHUNK_ELEMS // P)
+    xbuf = t.empty(min(per, max(L, 1)) * P, dtype=t.float64, device=eng.device)
+
+    def draw(js):
+        """Labels ``js`` drawn and scored: the draws into their columns, the
+        log-densities left in the engine's buffers at the returned offsets."""
+        works = [obs.work(labels[j], domain.specs[labels[j]], j, n_cand=P, n_total=P,
+                          key=T.label_key(seed, labels[j]), cand_base=0) for j in js]
+        res = eng.run(works, prior_weight=prior_weight, lf=linear_forgetting, precision=64,
+                      outputs=True, device_outputs=True, x_ptr=xbuf.data_ptr(), **obs.run_kwargs)
+        off = np.asarray([r.extra["out_off"] for r in res], np.int64)
+        for j, o in zip(js, off):  # (device to device)
+            d.vals[j].copy_(xbuf[int(o):int(o) + P])
+        return off
+
+    chunks = [list(range(c0, min(L, c0 + per))) for c0 in range(0, L, per)]
+    n_active = None
+    if len(chunks) > 1:
+        # the fold runs in label order and needs every row's activity: the
+        # selectors' columns first (their draws do not depend on the chunking)
+        sel = [labels.index(lab) for lab in _selectors(domain, labels)]
+        for c0 in range(0, len(sel), per):
+            draw(sel[c0:c0 + per])
+        n_active = _rows_active(eng, domain, labels, d, P, sp)
+    init = 1
+    for js in chunks:
+        off = draw(js)
+        if n_active is None:
+            n_active = _rows_active(eng, domain, labels, d, P, sp)
+        d_bl, d_al = eng.device_output_ptrs()
+        cols = np.asarray(js, np.int64)
+        _L.check(lib.tpe_pool_fold(d_bl, d_al, off.ctypes.data, cols.ctypes.data, len(js),
+                                   d.active.data_ptr(), P, P, init, d.S.data_ptr(),
+                                   d.terms.data_ptr() if keep_terms else None, P, sp),
+                 "tpe_pool_fold")
+        init = 0
+    if not chunks:  # a space without labels: S = 0
+        n_active = t.zeros(1, dtype=t.int64, device=eng.device)
+        _L.check(lib.tpe_pool_fold(None, None, None, None, 0, None, P, P, 1, d.S.data_ptr(), None,
+                                   P, sp), "tpe_pool_fold")
+    self = SampledPool.__new__(SampledPool)
+    self.domain, self.labels = domain, labels
+    self._n_rows, self._born_on, self._host = P, eng.device, None
+    self._d_n_active, self._n_active = n_active[:L], None
+    self.taken = np.zeros(P, np.uint8)
+    self.row_of = {}
+    self._device = {eng.device: d}
+    return self
 
 
 class _GridBlock(object):
@@ -750,4 +1014,113 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     docs = trial_docs(ids, domain, trials, [pool.config(r) for r in rows])
     if verbose:
         logger.info("tpe.suggest_from_pool: %d rows in %f seconds" % (len(rows), time.time() - t0))
+    return docs
+
+
+def _keep_rows(keep, labels, vals, n):
+    """Row mask of ``keep`` over n rows, called in chunks of at most
+    ``KEEP_CHUNK``; ``vals``: (n, L), NaN where a label is not live."""
+    ok = np.ones(n, bool)
+    for lo in range(0, n, KEEP_CHUNK):
+        hi = min(n, lo + KEEP_CHUNK)
+        mask = np.asarray(keep({lab: vals[lo:hi, j] for j, lab in enumerate(labels)}))
+        if mask.shape != (hi - lo,):
+            raise ValueError("keep returned shape %s for %d rows" % (mask.shape, hi - lo))
+        ok[lo:hi] = mask.astype(bool)
+    return ok
+
+
+def _stored_config(domain, labels, vals, active):
+    """{live label: stored value} of one row of stored values."""
+    out = {}
+    for j in np.flatnonzero(active):
+        lab = labels[j]
+        v = vals[j]
+        out[lab] = int(round(v)) if domain.specs[lab].kind in INT_KINDS else float(v)
+    return out
+
+
+def take_rows(pool, rows_dev, k):
+    """Rows ``rows_dev[:k]`` (device int64) of a sampled pool as host blocks
+    (k, L): stored values (randint's ``low`` restored) and activity --
+    tpe_pool_take, the only per-row data such a call reads back."""
+    from . import tpe as T
+    eng = T.engine()
+    d, t, L = pool._born(), eng.torch, len(pool.labels)
+    out_v = t.empty((k, max(L, 1)), dtype=t.float64, device=eng.device)
+    out_a = t.empty((k, max(L, 1)), dtype=t.uint8, device=eng.device)
+    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    _L.check(eng.lib.tpe_pool_take(d.vals.data_ptr(), d.active.data_ptr(), len(pool), L,
+                                   rows_dev.data_ptr(), k, out_v.data_ptr(), out_a.data_ptr(),
+                                   sp), "tpe_pool_take")
+    vals = out_v.cpu().numpy().reshape(k, max(L, 1))[:, :L]
+    active = out_a.cpu().numpy().reshape(k, max(L, 1))[:, :L].astype(bool)
+    for j, lab in enumerate(pool.labels):
+        off = int_offset(pool.domain.specs[lab])
+        if off:
+            vals[:, j] += off
+    return vals, active
+
+
+def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
+                    prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
+                    verbose=True):
+    """An ``algo`` for fmin on any space: one document per id, k distinct
+    points from one history (``max_queue_len=k``, asynchronous backends).
+
+    Past the startup phase it samples a fresh pool of ``n_EI_candidates`` rows
+    (``Pool.sample`` with this ``seed``) and returns the first ``len(new_ids)``
+    untaken rows by the pool's born S -- larger S first, NaN before
+    everything, equal scores to the smaller row.  Only those rows come back
+    from the device.  Fewer untaken rows than ids: that many documents; none:
+    ``[]``.  While the history is shorter than ``n_startup_jobs`` it returns
+    ``rand.suggest_device``'s documents.
+
+    ``keep(cols)``, optional (``GridPool``'s rules): called in chunks of at
+    most ``KEEP_CHUNK`` rows with ``cols`` the {label: float64 array} of the
+    chunk (NaN where the label is not live); rows whose entry of the returned
+    boolean mask is false are marked taken before the selection -- the
+    survivors of a feasibility check.  A host predicate costs one readback of
+    the pool.  In the startup phase ``keep`` sees ``n_EI_candidates`` prior
+    rows (``rand.draw_priors``) and the ids get the first rows it accepts.
+
+    Rows are distinct as rows; on a purely discrete space two of them can hold
+    the same configuration (not deduplicated: ``Pool`` and ``GridPool`` are
+    for enumerable spaces).  Under torch.distributed every rank samples and
+    scores the same pool and returns the same documents."""
+    from . import rand
+    from . import tpe as T
+    t0 = time.time()
+    domain = as_domain(domain)
+    labels = list(domain.params)
+    n = max(int(n_EI_candidates), 0)
+    hist = T.collect_history(trials, labels)
+    if hist.tids.size < n_startup_jobs:
+        if keep is None:
+            return rand.suggest_device(new_ids, domain, trials, seed)
+        _, draws = rand.draw_priors(domain, seed, n)  # (L, n) stored values
+        vals = np.ascontiguousarray(draws.T)
+        sel = _selectors(domain, labels)
+        active = _host_active(domain, labels, sel, vals[:, [labels.index(s) for s in sel]])
+        vals[~active] = np.nan
+        rows = np.flatnonzero(_keep_rows(keep, labels, vals, n))[:len(new_ids)]
+        configs = [_stored_config(domain, labels, vals[r], active[r]) for r in rows]
+        return trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
+    pool = _sample(domain, trials, seed, n, prior_weight, gamma, linear_forgetting, False,
+                   hist=hist)
+    if keep is not None and len(pool):
+        pool.mark_taken(np.flatnonzero(~_keep_rows(keep, labels, pool.vals, len(pool))))
+    k = min(len(new_ids), pool.n_untaken)
+    if k == 0:
+        return []
+    eng = T.engine()
+    d = pool.device(eng) if keep is not None else pool._born()
+    rows = _topk_device(eng, d, len(pool), k)
+    vals, active = take_rows(pool, d.rows_out, len(rows))
+    pool.mark_taken(rows)
+    configs = [_stored_config(domain, labels, vals[i], active[i]) for i in range(len(rows))]
+    docs = trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
+    if verbose:
+        logger.info("tpe.suggest_sampled: %d of %d rows in %f seconds"
+                    % (len(rows), len(pool), time.time() - t0))
     return docs

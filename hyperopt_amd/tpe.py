@@ -27,7 +27,9 @@ all-gather + device max-loc (hyperopt_amd/dist.py).
 ``Pool`` / ``score_configs`` / ``suggest_from_pool`` (hyperopt_amd/pool.py)
 rank a fixed set of configurations with the same posteriors and return
 several distinct documents per call; ``GridPool`` is the pool of a Cartesian
-product of per-label axes, scored without building its rows.
+product of per-label axes, scored without building its rows; ``Pool.sample``
+/ ``suggest_sampled`` is the pool of a free space, its rows drawn from the
+posterior and ranked without leaving the device.
 """
 from __future__ import annotations
 
@@ -779,4 +781,5 @@ def _suggest_many(requests, shard_studies=False):
 
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
-from .pool import GridPool, Pool, score_configs, suggest_from_pool  # noqa: E402,F401
+from .pool import (GridPool, Pool, SampledPool, score_configs,  # noqa: E402,F401
+                   suggest_from_pool, suggest_sampled)

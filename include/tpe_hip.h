@@ -679,6 +679,49 @@ int64_t tpe_pool_topk_scratch_bytes(int64_t n_rows, int64_t k);
 int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t n_rows, int64_t k,
                   int64_t* out_rows, int64_t* out_count, void* scratch, void* stream);
 
+/* ---- a pool sampled from the posterior (tpe.Pool.sample) --------------------
+ * The scorers' own draws (out_x, candidate r of every label's stream) read as
+ * configuration r, in the pool layout above.
+ *
+ * tpe_rows_active: which labels are live in each row, from the row's own
+ * selector values.  The space's liveness is a program in CSR form: label j's
+ * clauses are [host_label_off[j], host_label_off[j + 1]), clause c's terms
+ * [host_clause_off[c], host_clause_off[c + 1]).  A term holds in row r iff
+ * llrint(vals[col * ld + r]) == value (never for a NaN or an infinity), a
+ * clause iff all its terms hold (none: always), a label is live iff one of its
+ * clauses holds (none: never).  Writes active[j * ld + r] (0 / 1) for r <
+ * n_rows and adds label j's live rows to n_active[j] (device, zeroed by the
+ * caller; integer adds).  Limits: TPE_COND_MAX_LABELS labels,
+ * TPE_COND_MAX_CLAUSES clauses, TPE_COND_MAX_TERMS terms -- a larger program
+ * returns TPE_E_UNSUPPORTED.  host_*: host arrays, read before the call
+ * returns. */
+#define TPE_COND_MAX_LABELS 128
+#define TPE_COND_MAX_CLAUSES 256
+#define TPE_COND_MAX_TERMS 256
+typedef struct tpe_cond_term {
+  int32_t col;          /* the selector's column, in [0, n_labels)             */
+  int32_t value;        /* the branch index the selector must hold             */
+} tpe_cond_term;
+int tpe_rows_active(const double* vals, int64_t ld, int64_t n_rows, int n_labels,
+                    const int32_t* host_label_off, const int32_t* host_clause_off,
+                    const tpe_cond_term* host_terms, int n_terms, uint8_t* active,
+                    int64_t* n_active, void* stream);
+/* tpe_pool_ranges: out[2 j], out[2 j + 1] (device) = (min, max) of label j's
+ * live finite values, with host_positive[j] != 0 of those > 0 only; a label
+ * without such a value: (+inf, -inf).  -0.0 orders below +0.0.  Exact and
+ * independent of block scheduling (integer min / max of order-preserving
+ * keys). */
+int tpe_pool_ranges(const double* vals, const uint8_t* active, int64_t ld, int64_t n_rows,
+                    int n_labels, const uint8_t* host_positive, double* out, void* stream);
+/* tpe_pool_take: rows[0, k) (device, e.g. tpe_pool_topk's out_rows) gathered
+ * into out_vals (k, n_labels) fp64 and out_active (k, n_labels) bytes,
+ * row-major; a row outside [0, ld) gives NaN / 0. */
+int tpe_pool_take(const double* vals, const uint8_t* active, int64_t ld, int n_labels,
+                  const int64_t* rows, int64_t k, double* out_vals, uint8_t* out_active,
+                  void* stream);
+/* host: writes sizeof(tpe_cond_term) to out[0..n); returns 1 */
+int tpe_sampled_struct_sizes(int32_t* out, int n);
+
 /* ---- a grid pool: the product of per-label axes (tpe.GridPool) ---------------
  * The criterion above is separable: once the scorers have left log l / log g
  * of every axis value in bl / al, the score of a row of the product is a sum
