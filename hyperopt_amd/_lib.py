@@ -157,6 +157,9 @@ _SIGNATURES = {
     "tpe_pool_ranges": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P]),
     "tpe_pool_take": (_I, [_P, _P, _I64, _I, _P, _I64, _P, _P, _P]),
     "tpe_sampled_struct_sizes": (_I, [_P, _I]),
+    "tpe_pool_distinct_scratch_bytes": (_I64, [_I64, _I64]),
+    "tpe_pool_distinct": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _I64, _P, _I64, _P, _I, _P, _P,
+                               _P, _P, _P]),
     "tpe_grid_fold": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),

@@ -34,6 +34,12 @@ ones above, and ``tpe_pool_take`` brings back the winners only
 (csrc/tpe_sampled.hip).  ``suggest_sampled`` is the ``algo`` around it: k
 distinct documents per call on any space.
 
+``distinct_rows`` names, per row, the first row that holds its configuration
+-- or the history row that does: an open-addressing table over whole rows
+built on the device (csrc/tpe_distinct.hip), against the history already in
+HBM.  ``distinct=True`` makes ``suggest_sampled`` / ``suggest_from_pool``
+suggest fresh configurations only.
+
 ``GridPool`` is the pool of a Cartesian product of per-label axes.  S is
 separable over the axes, so the scorers see every axis value once and
 ``tpe_grid_fold`` (csrc/tpe_grid.hip) decodes the rows and sums the per-value
@@ -221,7 +227,7 @@ class _DevicePool(object):
     them --, activity (L, P) bytes, the taken mask, and per label the
     (min, max) of its live values in the scoring coordinate."""
     __slots__ = ("vals", "active", "taken", "taken_current", "ranges", "S", "terms", "rows_out",
-                 "count", "scratch")
+                 "count", "scratch", "first", "mask", "distinct_scratch")
 
 
 class Pool(object):
@@ -286,8 +292,9 @@ class Pool(object):
         the posterior is the prior mixture; a startup rule is the caller's.
 
         Rows are distinct as rows: on a purely discrete space two rows can hold
-        the same configuration (``Pool`` / ``GridPool`` are for enumerable
-        spaces).  A born S and a later ``score_configs`` of the same rows under the
+        the same configuration (``tpe.distinct_rows`` names the first row of
+        every configuration; ``suggest_sampled(distinct=True)`` suggests only
+        those).  A born S and a later ``score_configs`` of the same rows under the
         same history may differ in their last bits: a log-domain label is scored
         at its drawn log coordinate when born, at log(exp(z)) when injected."""
         return _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting,
@@ -369,6 +376,7 @@ class Pool(object):
             d.S = t.empty(max(P, 1), dtype=t.float64, device=eng.device)
             d.terms = None
             d.rows_out = d.count = d.scratch = None
+            d.first = d.mask = d.distinct_scratch = None
             self._device[eng.device] = d
         if not d.taken_current:
             d.taken[:len(self)].copy_(t.from_numpy(self.taken))
@@ -505,6 +513,7 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
     d.S = t.empty(P, dtype=t.float64, device=eng.device)
     d.terms = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device) if keep_terms else None
     d.rows_out = d.count = d.scratch = None
+    d.first = d.mask = d.distinct_scratch = None
     sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
     per = max(1, CHUNK_ELEMS // P)
     xbuf = t.empty(min(per, max(L, 1)) * P, dtype=t.float64, device=eng.device)
@@ -917,9 +926,102 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
     return eng, d
 
 
-def _topk_device(eng, d, P, k):
-    """Rows of the first k untaken rows by d.S, in rank order (numpy int64)."""
+def _mirror(pool, eng):
+    """The pool's device mirror with a current taken mask; a sampled pool's is
+    the one it was born with, as it stands (no ranges: nothing is scored)."""
+    if isinstance(pool, SampledPool) and eng.device == pool._born_on:
+        d = pool._born()
+        if not d.taken_current:
+            d.taken[:len(pool)].copy_(eng.torch.from_numpy(pool.taken))
+            d.taken_current = True
+        return d
+    return pool.device(eng)
+
+
+def _seen_rows(eng, hist):
+    """The rows of ``hist`` as tpe_pool_distinct's seen list: (keep-alive
+    tensors, vals ptr, active ptr, ld, rows ptr or None, T).  The HBM mirror of
+    the trials' cache where LevelInputs would gather from it (position t of the
+    list is history row t), else one upload of ``hist.vals`` / ``hist.active``."""
+    from . import tpe as T
+    t = eng.torch
+    n = 0 if hist is None else int(hist.tids.size)
+    if n == 0:
+        return (), None, None, 0, None, 0
+    if T.USE_DEVICE_HISTORY and hist.col is not None:
+        dh = hist.col.device_history(eng)
+        rows = None
+        if hist.rows is not None:
+            rows = t.from_numpy(np.ascontiguousarray(hist.rows, np.int32)).to(eng.device)
+        return ((dh, rows), dh.vals.data_ptr(), dh.active.data_ptr(), dh.ld,
+                None if rows is None else rows.data_ptr(), n)
+    active = np.asarray(hist.active, bool)
+    vals = t.from_numpy(np.ascontiguousarray(np.where(active, hist.vals, 0.0).T)).to(eng.device)
+    act = t.from_numpy(np.ascontiguousarray(active.T).view(np.uint8)).to(eng.device)
+    return (vals, act), vals.data_ptr(), act.data_ptr(), n, None, n
+
+
+def _distinct_device(eng, pool, d, hist):
+    """tpe_pool_distinct of the pool's mirror ``d`` against the rows of
+    ``hist`` (None: no seen set): ``d.first`` (int64) and ``d.mask`` =
+    ``d.taken | (first != row)`` on the device."""
     t, lib = eng.torch, eng.lib
+    P, L = len(pool), len(pool.labels)
+    if d.first is None:
+        d.first = t.empty(max(P, 1), dtype=t.int64, device=eng.device)
+        d.mask = t.empty(max(P, 1), dtype=t.uint8, device=eng.device)
+    if P == 0:
+        return
+    _alive, sv, sa, sld, srows, n_seen = _seen_rows(eng, hist)
+    need = lib.tpe_pool_distinct_scratch_bytes(P, n_seen)
+    if d.distinct_scratch is None or d.distinct_scratch.numel() < need:
+        d.distinct_scratch = t.empty(need, dtype=t.uint8, device=eng.device)
+    # a history holds randint(low, high) with ``low`` included, a pool without
+    shift = np.asarray([int_offset(pool.domain.specs[lab]) or 0 for lab in pool.labels],
+                       np.float64)
+    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    _L.check(lib.tpe_pool_distinct(d.vals.data_ptr() if L else None,
+                                   d.active.data_ptr() if L else None, d.vals.shape[1], P, L,
+                                   sv, sa, sld, srows, n_seen,
+                                   shift.ctypes.data if shift.any() else None, 64,
+                                   d.taken.data_ptr(), d.first.data_ptr(), d.mask.data_ptr(),
+                                   d.distinct_scratch.data_ptr(), sp), "tpe_pool_distinct")
+
+
+GRID_DISTINCT = ("GridPool rows are distinct by construction; exclude evaluated rows with "
+                 "GridPool.exclude")
+
+
+def distinct_rows(pool, trials=None, domain=None):
+    """``first`` (int64 (P,)) of a ``Pool`` / ``SampledPool``: two rows hold the
+    same configuration iff the same labels are live in them and every live
+    value is equal as an fp64 number (-0.0 == +0.0, all NaNs equal).
+    ``first[r]`` is the smallest pool row that holds row r's configuration --
+    r itself for the first of its class -- or, with ``trials``, ``-1 - t`` when
+    the configuration is that of row t of ``collect_history(trials,
+    pool.labels)`` (the smallest such t): the rows a suggest conditions on, so
+    pending and failed trials are seen too.  A row is fresh iff ``first[r] ==
+    r``.  Computed on the device against the resident history
+    (csrc/tpe_distinct.hip); only ``first`` comes back."""
+    from . import tpe as T
+    if isinstance(pool, GridPool):
+        raise ValueError(GRID_DISTINCT)
+    if domain is not None and list(as_domain(domain).params) != pool.labels:
+        raise ValueError("the pool was built for another space (labels differ)")
+    if len(pool) == 0:
+        return np.zeros(0, np.int64)
+    eng = T.engine()
+    hist = None if trials is None else T.collect_history(trials, pool.labels)
+    d = _mirror(pool, eng)
+    _distinct_device(eng, pool, d, hist)
+    return d.first[:len(pool)].cpu().numpy()
+
+
+def _topk_device(eng, d, P, k, taken=None):
+    """Rows of the first k untaken rows by d.S, in rank order (numpy int64);
+    ``taken``: a device mask to read in place of d.taken."""
+    t, lib = eng.torch, eng.lib
+    taken = d.taken if taken is None else taken
     k = min(int(k), P)
     if k <= 0 or P == 0:
         return np.zeros(0, np.int64)
@@ -930,7 +1032,7 @@ def _topk_device(eng, d, P, k):
         d.rows_out = t.empty(k, dtype=t.int64, device=eng.device)
         d.count = t.zeros(1, dtype=t.int64, device=eng.device)
     sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
-    _L.check(lib.tpe_pool_topk(d.S.data_ptr(), d.taken.data_ptr(), P, k, d.rows_out.data_ptr(),
+    _L.check(lib.tpe_pool_topk(d.S.data_ptr(), taken.data_ptr(), P, k, d.rows_out.data_ptr(),
                                d.count.data_ptr(), d.scratch.data_ptr(), sp), "tpe_pool_topk")
     n = int(d.count.item())
     return d.rows_out[:n].cpu().numpy()
@@ -962,12 +1064,16 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     return S, np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
 
 
-def startup_rows(pool, seed, k):
+def startup_rows(pool, seed, k, stale=None):
     """The startup phase's rows: k of the untaken rows (of a grid pool: that are
     not excluded either), uniformly without
     replacement, a function of (seed, taken set) alone:
-    ``untaken[np.random.RandomState(seed).choice(untaken.size, k, replace=False)]``."""
+    ``untaken[np.random.RandomState(seed).choice(untaken.size, k, replace=False)]``.
+    ``stale``: a row mask; its rows count as taken (``distinct=True``: the rows
+    that are not fresh)."""
     free = pool.taken == 0
+    if stale is not None:
+        free &= np.asarray(stale) == 0
     if getattr(pool, "excluded", None) is not None:  # (a GridPool's keep / exclude)
         free &= pool.excluded == 0
     untaken = np.flatnonzero(free)
@@ -978,7 +1084,8 @@ def startup_rows(pool, seed, k):
 
 
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0,
-                      n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True):
+                      n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True,
+                      distinct=False):
     """An ``algo`` for fmin (``partial(tpe.suggest_from_pool, pool=pool)``): one
     document per id, the first id the best untaken row of ``pool`` by
     ``score_configs``, the second the next best, and so on -- larger S first,
@@ -988,10 +1095,20 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     stops).  While the history is shorter than ``n_startup_jobs``
     (tpe.py:909-911) the rows are ``startup_rows(pool, seed, k)``.  Under
     torch.distributed every rank scores the whole pool and returns the same
-    documents."""
+    documents.
+
+    ``distinct=True``: only fresh rows are suggested (``distinct_rows``) -- the
+    first row of every configuration of the pool that no row of the history
+    holds, pending and failed trials included; a pool with repeated rows never
+    gives one configuration twice and never one that ``trials`` already has.
+    Fewer fresh untaken rows than ids: that many documents; none: ``[]``.  A
+    taken row still counts as the first of its class.  A ``GridPool`` raises
+    ValueError: its rows are distinct by construction."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
+    if distinct and isinstance(pool, GridPool):
+        raise ValueError(GRID_DISTINCT)
     t0 = time.time()
     domain = as_domain(domain)
     if list(domain.params) != pool.labels:
@@ -1001,11 +1118,19 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
         return []
     hist = T.collect_history(trials, pool.labels)
     if hist.tids.size < n_startup_jobs:
-        rows = startup_rows(pool, seed, k)
+        stale = None
+        if distinct:
+            eng = T.engine()
+            d = _mirror(pool, eng)
+            _distinct_device(eng, pool, d, hist)
+            stale = d.first[:len(pool)].cpu().numpy() != np.arange(len(pool))
+        rows = startup_rows(pool, seed, k, stale)
     else:
         eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
                                False, hist=hist)
-        rows = _topk_device(eng, d, len(pool), k)
+        if distinct:
+            _distinct_device(eng, pool, d, hist)
+        rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
     rows = [int(r) for r in rows]
     pool.mark_taken(rows)
     ids = list(new_ids)[:len(rows)]
@@ -1064,7 +1189,7 @@ def take_rows(pool, rows_dev, k):
 
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
-                    verbose=True):
+                    verbose=True, distinct=False):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -1085,9 +1210,19 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     rows (``rand.draw_priors``) and the ids get the first rows it accepts.
 
     Rows are distinct as rows; on a purely discrete space two of them can hold
-    the same configuration (not deduplicated: ``Pool`` and ``GridPool`` are
-    for enumerable spaces).  Under torch.distributed every rank samples and
-    scores the same pool and returns the same documents."""
+    the same configuration, and a fresh pool knows nothing of the trials
+    already made.  ``distinct=True`` suggests fresh rows only
+    (``distinct_rows``, on the device: no readback): the first row of every
+    configuration of the pool that no row of the history holds -- evaluated,
+    pending and failed trials alike.  The documents are pairwise distinct
+    configurations, none of them in ``trials``; fewer fresh rows than ids:
+    that many documents; none: ``[]``, so fmin stops once a discrete space is
+    used up.  With ``keep``, a rejected row still counts as the first row of
+    its class: a pure predicate gives equal rows equal verdicts.  In the
+    startup phase the ``n_EI_candidates`` prior rows go through the same pass
+    and the ids get the first fresh (kept) rows in row order.  Under
+    torch.distributed every rank samples and scores the same pool and returns
+    the same documents."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
@@ -1096,14 +1231,21 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)
     if hist.tids.size < n_startup_jobs:
-        if keep is None:
+        if keep is None and not distinct:
             return rand.suggest_device(new_ids, domain, trials, seed)
         _, draws = rand.draw_priors(domain, seed, n)  # (L, n) stored values
         vals = np.ascontiguousarray(draws.T)
         sel = _selectors(domain, labels)
         active = _host_active(domain, labels, sel, vals[:, [labels.index(s) for s in sel]])
         vals[~active] = np.nan
-        rows = np.flatnonzero(_keep_rows(keep, labels, vals, n))[:len(new_ids)]
+        ok = np.ones(n, bool) if keep is None else _keep_rows(keep, labels, vals, n)
+        if distinct and n:
+            eng = T.engine()
+            prior = Pool.from_arrays(domain, vals, active)
+            d = prior.device(eng)
+            _distinct_device(eng, prior, d, hist)
+            ok &= d.first[:n].cpu().numpy() == np.arange(n)
+        rows = np.flatnonzero(ok)[:len(new_ids)]
         configs = [_stored_config(domain, labels, vals[r], active[r]) for r in rows]
         return trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
     pool = _sample(domain, trials, seed, n, prior_weight, gamma, linear_forgetting, False,
@@ -1114,8 +1256,12 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     if k == 0:
         return []
     eng = T.engine()
-    d = pool.device(eng) if keep is not None else pool._born()
-    rows = _topk_device(eng, d, len(pool), k)
+    d = _mirror(pool, eng)
+    if distinct:
+        _distinct_device(eng, pool, d, hist)
+    rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
+    if not len(rows):
+        return []
     vals, active = take_rows(pool, d.rows_out, len(rows))
     pool.mark_taken(rows)
     configs = [_stored_config(domain, labels, vals[i], active[i]) for i in range(len(rows))]

@@ -29,7 +29,9 @@ rank a fixed set of configurations with the same posteriors and return
 several distinct documents per call; ``GridPool`` is the pool of a Cartesian
 product of per-label axes, scored without building its rows; ``Pool.sample``
 / ``suggest_sampled`` is the pool of a free space, its rows drawn from the
-posterior and ranked without leaving the device.
+posterior and ranked without leaving the device; ``distinct_rows`` /
+``distinct=True`` keep to the first row of every configuration that the
+history does not hold yet.
 """
 from __future__ import annotations
 
@@ -781,5 +783,5 @@ def _suggest_many(requests, shard_studies=False):
 
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
-from .pool import (GridPool, Pool, SampledPool, score_configs,  # noqa: E402,F401
+from .pool import (GridPool, Pool, SampledPool, distinct_rows, score_configs,  # noqa: E402,F401
                    suggest_from_pool, suggest_sampled)

@@ -722,6 +722,43 @@ int tpe_pool_take(const double* vals, const uint8_t* active, int64_t ld, int n_l
 /* host: writes sizeof(tpe_cond_term) to out[0..n); returns 1 */
 int tpe_sampled_struct_sizes(int32_t* out, int n);
 
+/* ---- distinct configurations of a pool (tpe.distinct_rows) -------------------
+ * Two rows hold the same configuration iff their activity bytes agree for
+ * every label and, for every label live in them, their values are equal as
+ * fp64 numbers with -0.0 == +0.0 and all NaNs equal (the scorers' order_key);
+ * entries of labels that are not live are ignored.
+ *
+ * tpe_pool_distinct: for the pool rows [0, n_rows) (layout above) and a list
+ * of n_seen seen rows -- label-major like the pool, at seen_vals / seen_active
+ * with leading dimension seen_ld (a DeviceHistory's vals / active / ld);
+ * position t of the list is row seen_rows[t] (device int32; an entry outside
+ * [0, seen_ld) is ignored), or row t when seen_rows is NULL --
+ *   first[r] = -1 - t, t the smallest position of the list whose row holds
+ *              r's configuration, if there is one; otherwise
+ *            = the smallest pool row that holds r's configuration.
+ * A row is fresh iff first[r] == r.  host_seen_shift (host, per label, or
+ * NULL; read before the call returns): subtracted from the seen value of the
+ * label before it is compared (a history stores randint(low, high) with `low`
+ * included, a pool without); a nonzero entry only among the first
+ * TPE_DISTINCT_SHIFT_LABELS labels (else TPE_E_UNSUPPORTED).  mask_out
+ * (nullable): mask_out[r] = (taken_in ? taken_in[r] : 0) | (first[r] != r),
+ * tpe_pool_topk's `taken`; nothing past n_rows is written.  hash_bits in
+ * [0, 64]: the bits of the row hash that are kept -- 64 in the product; fewer
+ * put unequal rows on one probe chain (0: all rows on one), which costs time
+ * and nothing else.  Exact (rows are equal only after a value-by-value
+ * comparison) and independent of block scheduling (integer atomics on an
+ * open-addressing table in `scratch`); asynchronous on `stream`, no
+ * allocation.  scratch: tpe_pool_distinct_scratch_bytes(n_rows, n_seen) bytes
+ * (-1: bad arguments), 8-byte aligned.  n_rows == 0 and n_seen == 0 are
+ * legal. */
+#define TPE_DISTINCT_SHIFT_LABELS 4096
+int64_t tpe_pool_distinct_scratch_bytes(int64_t n_rows, int64_t n_seen);
+int tpe_pool_distinct(const double* vals, const uint8_t* active, int64_t ld, int64_t n_rows,
+                      int n_labels, const double* seen_vals, const uint8_t* seen_active,
+                      int64_t seen_ld, const int32_t* seen_rows, int64_t n_seen,
+                      const double* host_seen_shift, int hash_bits, const uint8_t* taken_in,
+                      int64_t* first, uint8_t* mask_out, void* scratch, void* stream);
+
 /* ---- a grid pool: the product of per-label axes (tpe.GridPool) ---------------
  * The criterion above is separable: once the scorers have left log l / log g
  * of every axis value in bl / al, the score of a row of the product is a sum
