@@ -218,8 +218,8 @@ __global__ __launch_bounds__(kBS) void k_score_pruned64(
         y = lgmm ? log(x) : x;
       } else if (J.flags & TPE_F_DRAW32) {
         // the table path's fp32 stream (the exact re-score of an overflowed band)
-        const float y32 = draw32(M, J.key, J.cand_base + li, lo_on, hi_on, (float)J.low,
-                                 (float)J.high);
+        const float y32 = draw32(M, J.key, J.cand_base + li, lo_on, hi_on, bound32(J.low),
+                                 bound32(J.high));
         x = cand_value(y32, lgmm);
         y = score_coord(y32, lgmm);  // (LGMM1: log of the returned value, as INJ)
       } else {

@@ -434,8 +434,8 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(POW2 ? TPE_
       const int64_t t0 = base + (int64_t)threadIdx.x * kLatR;
       const int nv = (int)max((int64_t)0, min((int64_t)kLatR, n_lim - t0));
       float x[kLatR];
-      draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, (float)J.low,
-                          (float)J.high, lgmm, s_stage + (threadIdx.x / kWave) * (kLatR * kWave), s_list + (threadIdx.x / kWave) * kRetryList,
+      draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, bound32(J.low),
+                          bound32(J.high), lgmm, s_stage + (threadIdx.x / kWave) * (kLatR * kWave), s_list + (threadIdx.x / kWave) * kRetryList,
                           x);
       const float inv_q32 = (float)(1.0 / J.q);
       const int kmin = (int)J.lat_kmin, nl = (int)J.lat_n;
@@ -484,8 +484,8 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(POW2 ? TPE_
         const int64_t t0 = base + (int64_t)threadIdx.x * kLatR;
         const int nv = (int)max((int64_t)0, min((int64_t)kLatR, n_lim - t0));
         float x[kLatR];
-        draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, (float)J.low,
-                            (float)J.high, lgmm, s_stage + (threadIdx.x / kWave) * (kLatR * kWave), s_list + (threadIdx.x / kWave) * kRetryList,
+        draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, bound32(J.low),
+                            bound32(J.high), lgmm, s_stage + (threadIdx.x / kWave) * (kLatR * kWave), s_list + (threadIdx.x / kWave) * kRetryList,
                             x);
 #pragma unroll
         for (int r = 0; r < kLatR; ++r)

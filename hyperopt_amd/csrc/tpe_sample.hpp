@@ -226,6 +226,21 @@ __device__ __forceinline__ float attempt32_first(const Mix& M, uint64_t key, int
   return second ? fmaf(sgb, z1, mub) : fmaf(sga, z0, mua);
 }
 
+// A job's fp64 bound as the fp32 stream compares against it: the smallest
+// float >= b.  For a float y, b <= y is then exactly bound32(b) <= y, and
+// y < b exactly y < bound32(b) -- so an accepted (or clamped) draw lies in
+// [low, high) of the fp64 bounds, where (float)low may lie below low
+// ((float)0.7 < 0.7).  A bound that fp32 holds exactly is unchanged.
+__device__ __forceinline__ float bound32(double b) {
+  const float f = (float)b;
+  // the next float up, on the bit pattern: +1 above zero, -1 below, the
+  // smallest subnormal from either zero (a few integer operations where
+  // nextafterf is a call's worth: the samplers convert per tile)
+  const uint32_t u = __float_as_uint(f);
+  const uint32_t up = f == 0.0f ? 1u : (f > 0.0f ? u + 1u : u - 1u);
+  return (double)f < b ? __uint_as_float(up) : f;
+}
+
 __device__ __forceinline__ bool accept32(float y, bool lo_on, bool hi_on, float lo, float hi) {
   return (!lo_on || lo <= y) && (!hi_on || y < hi);
 }

@@ -284,8 +284,8 @@ __global__ __launch_bounds__(kBS) void k_score32(
 #pragma unroll
     for (int r = 0; r < kR32; ++r) {
       const int64_t li = base + r * kBS + threadIdx.x;
-      x[r] = li < J.n_cand ? draw32(M, J.key, J.cand_base + li, lo_on, hi_on, (float)J.low,
-                                    (float)J.high)
+      x[r] = li < J.n_cand ? draw32(M, J.key, J.cand_base + li, lo_on, hi_on, bound32(J.low),
+                                    bound32(J.high))
                            : 1.0f;
     }
   }
@@ -406,7 +406,7 @@ __device__ __forceinline__ int bin_of(float y, float lo, float scale) {
 // coordinate (log x for LGMM1: its value is exp(y) in fp64)
 __device__ __forceinline__ float cand32(const Mix& M, const tpe_job& J, int64_t li, bool lo_on,
                                         bool hi_on) {
-  return draw32(M, J.key, J.cand_base + li, lo_on, hi_on, (float)J.low, (float)J.high);
+  return draw32(M, J.key, J.cand_base + li, lo_on, hi_on, bound32(J.low), bound32(J.high));
 }
 
 // K1: draw every candidate once (kept in `gen`, generation order, coalesced)
@@ -767,8 +767,8 @@ __global__ __launch_bounds__(kBS) void k_sample(const tpe_job* __restrict__ jobs
     const int64_t t0 = base + (int64_t)threadIdx.x * kLatR;
     const int nv = (int)max((int64_t)0, min((int64_t)kLatR, J.n_cand - t0));
     float x[kLatR];
-    draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, (float)J.low,
-                        (float)J.high, lgmm && quant,
+    draw32_pairs<kLatR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, bound32(J.low),
+                        bound32(J.high), lgmm && quant,
                         s_stage + (threadIdx.x / kWave) * (kLatR * kWave),
                         s_list + (threadIdx.x / kWave) * kRetryList, x);
 #pragma unroll

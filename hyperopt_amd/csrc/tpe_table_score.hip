@@ -195,8 +195,8 @@ __global__ __launch_bounds__(kBS) void k_score_table(
         x[r] = (float)Tb.origin + w * __builtin_amdgcn_fractf((float)(t0 + r) * 0.6180339887f);
 #else
       const int nv = (int)max((int64_t)0, min((int64_t)kTR, J.n_cand - t0));
-      draw32_pairs<kTR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, (float)J.low,
-                        (float)J.high, false, reinterpret_cast<float*>(rows), s_list + (threadIdx.x / kWave) * kRetryList, x);
+      draw32_pairs<kTR>(M, J.key, J.cand_base + t0, nv, lo_on, hi_on, bound32(J.low),
+                        bound32(J.high), false, reinterpret_cast<float*>(rows), s_list + (threadIdx.x / kWave) * kRetryList, x);
 #endif
     }
     // per-thread argmax in fp32 over the thread's candidates r = 0..kTR-1
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(TPE_SCORE_W
               nullptr, nmix};
   const int64_t t0 = base + (int64_t)threadIdx.x * kTRF;
   const int nvalid = (int)max((int64_t)0, min((int64_t)kTRF, J.n_cand - t0));
-  const float lo32 = (float)J.low, hi32 = (float)J.high;
+  const float lo32 = bound32(J.low), hi32 = bound32(J.high);
   uint16_t* wlist = s_list + (threadIdx.x / kWave) * kRetryList;
   // the candidates, in the scoring coordinate y (log x for LGMM1), into the
   // wave's stage (slot r of lane l at r * 64 + l)

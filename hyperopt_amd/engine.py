@@ -38,6 +38,10 @@ from . import dist as hdist
 EPS = 1e-12  # tpe.py:32
 DEFAULT_LF = 25  # tpe.py:36
 DRAW32_MAX_SLOT = 1 << 12  # fp32 lattice draws only while |k| <= 2^12
+# fp32 draws of an unquantized label only while the fp32 spacing at the far end
+# of its support is at most prior_sigma / DRAW32_MIN_STEPS (DESIGN.md "Scale
+# and offset"); a coarser label takes the fp64 stream and the exact scorer
+DRAW32_MIN_STEPS = 500
 LATTICE_CAP = 1 << 22  # max lattice slots per quantized label before the dense fallback
 LAT_PACK_MAX = 1 << 16  # lattice slots of a level initialised through the upload (else memset)
 TABLE_CAP = 1 << 15  # cells per label in the cell-table path (128 B each)
@@ -142,18 +146,42 @@ def posterior_params(kind, args):
         floor = -math.inf
         if kind == "qloguniform":
             floor = max(EPS, math.exp(low))  # tpe.py:527-532
-        return dict(family=fam, transform=L.OBS_LOG if fam == L.LGMM1 else L.OBS_IDENTITY,
-                    floor=floor, prior_mu=0.5 * (high + low), prior_sigma=1.0 * (high - low),
-                    low=low, high=high, q=q, bounded=True)
+        return _with_draw32(dict(
+            family=fam, transform=L.OBS_LOG if fam == L.LGMM1 else L.OBS_IDENTITY,
+            floor=floor, prior_mu=0.5 * (high + low), prior_sigma=1.0 * (high - low),
+            low=low, high=high, q=q, bounded=True))
     if kind in ("normal", "qnormal", "lognormal", "qlognormal"):
         mu, sigma = float(args[0]), float(args[1])
         q = float(args[2]) if kind.startswith("q") else None
         fam = L.LGMM1 if "log" in kind else L.GMM1
         floor = EPS if kind == "qlognormal" else -math.inf  # tpe.py:567
-        return dict(family=fam, transform=L.OBS_LOG if fam == L.LGMM1 else L.OBS_IDENTITY,
-                    floor=floor, prior_mu=mu, prior_sigma=sigma, low=0.0, high=0.0, q=q,
-                    bounded=False)
+        return _with_draw32(dict(
+            family=fam, transform=L.OBS_LOG if fam == L.LGMM1 else L.OBS_IDENTITY,
+            floor=floor, prior_mu=mu, prior_sigma=sigma, low=0.0, high=0.0, q=q,
+            bounded=False))
     raise ValueError("not a continuous prior: %r" % (kind,))
+
+
+def _with_draw32(P):
+    """Adds ``draw32``: whether fp32 can resolve the label's draws.  The fp32
+    stream forms mu + sigma z in absolute coordinates (x, or log x for the log
+    kinds), so its values sit on the fp32 grid at the support's magnitude --
+    [low, high], or prior_mu +- 9 prior_sigma for an unbounded label (the
+    prior's own range: a property of the space, so a cached plan keeps its
+    scorer) -- while a fitted bandwidth can be as small as prior_sigma / 100
+    (tpe.py:454-459).  False once that grid is coarser than
+    prior_sigma / DRAW32_MIN_STEPS: the analogue of DRAW32_MAX_SLOT."""
+    if P["bounded"]:
+        far = max(abs(P["low"]), abs(P["high"]))
+    else:
+        far = abs(P["prior_mu"]) + 9.0 * P["prior_sigma"]
+    with np.errstate(all="ignore"):
+        step = float(np.spacing(np.float32(far)))
+    # (a degenerate prior -- sigma <= 0, infinite bounds -- keeps its route and
+    # fails where it always did)
+    P["draw32"] = bool(not (P["prior_sigma"] > 0.0 and math.isfinite(step)) or
+                       step * DRAW32_MIN_STEPS <= P["prior_sigma"])
+    return P
 
 
 @functools.lru_cache(maxsize=4096)
@@ -1128,6 +1156,10 @@ class Engine:
                     self.exact64 == "auto" and m >= PRUNED64_MIN_COMP)) else "cont"
             n = n_inj(works[i]) if inj(i) else int(works[i].n_total or works[i].n_cand)
             mode = scorer
+            if not inj(i) and not params[i]["draw32"]:
+                # fp32 cannot resolve this label's draws: the fp64 stream,
+                # scored exactly (whatever fp32 scorer was asked for)
+                return "pruned64"
             if mode == "auto":
                 mode = "cont"
                 if not inj(i):
@@ -1222,7 +1254,7 @@ class Engine:
                     J["bin_lo"][pos], J["bin_hi"][pos] = _injected_range(w, P)
             elif modes[i] == "pruned64" and inj(i):
                 J["bin_lo"][pos], J["bin_hi"][pos] = _injected_range(w, P, fp32=False)
-            elif modes[i] == "pruned64" and precision == 32:
+            elif modes[i] == "pruned64" and precision == 32 and P["draw32"]:
                 flags |= L.F_DRAW32  # the fp32 stream (the table path's draws)
             elif modes[i] == "sorted":
                 J["bin_lo"][pos], J["bin_hi"][pos] = _support(w, P)
@@ -1271,6 +1303,10 @@ class Engine:
         below it the fp32 stream scored exactly in fp64 by tpe_score_pruned64
         -- so the argmax is exact at every size; with per-candidate outputs or
         injected candidates: dense).
+        A drawn label whose draws fp32 cannot resolve (posterior_params'
+        ``draw32``: a span far smaller than its magnitude) takes the fp64
+        stream and tpe_score_pruned64 whatever the scorer, and ``sample_only``
+        returns that stream.
         ``pruned=False`` is the old spelling of scorer="dense".  fp64 always
         runs the exact dense kernel.  ``posteriors``: fit only, and return the
         fitted mixtures in ``LabelResult.extra`` ("below" / "above" as
@@ -1925,10 +1961,21 @@ class Engine:
         a, b = _slice_of(lv.plan.groups, g)
         if lv.opts.sample_only:
             if kind in ("cont", "lat", "qfb"):
-                L.check(st.lib.tpe_sample(lv.base + lv.o_jobs + a * L.JOB_DTYPE.itemsize,
-                                          lv.plan.jobs[a:b].ctypes.data_as(ctypes.c_void_p), b - a,
-                                          lv.d_segs, lv.d_mu, lv.d_sig, lv.d_cdf, lv.opts.precision,
-                                          st.d_x, lv.sp), "tpe_sample")
+                # the stream the suggest path scores: fp64 for an unquantized
+                # label fp32 cannot resolve (posterior_params' draw32), in runs
+                # of jobs that draw alike
+                plan, JS = lv.plan, L.JOB_DTYPE.itemsize
+                prec = [64 if kind == "cont" and not plan.inj(plan.order[p]) and
+                        not plan.params[plan.order[p]]["draw32"]
+                        else lv.opts.precision for p in range(a, b)]
+                p0 = a
+                for p in range(a + 1, b + 1):
+                    if p == b or prec[p - a] != prec[p0 - a]:
+                        L.check(st.lib.tpe_sample(
+                            lv.base + lv.o_jobs + p0 * JS,
+                            plan.jobs[p0:p].ctypes.data_as(ctypes.c_void_p), p - p0, lv.d_segs,
+                            lv.d_mu, lv.d_sig, lv.d_cdf, prec[p0 - a], st.d_x, lv.sp), "tpe_sample")
+                        p0 = p
             return
         on_side = st.side is not None and side_kind
         kst = st.side if on_side else None

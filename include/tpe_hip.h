@@ -60,6 +60,12 @@ enum {
                            it, those calls skip their memsets               */
   /* (TPE_F_DRAW32 on an unquantized job: the fp32 candidate stream -- the
      table path's -- scored exactly by tpe_score_pruned64)                   */
+  /* The fp32 stream compares a draw against the smallest floats >= low and
+     >= high, so every fp32 draw lies in [low, high) of the fp64 bounds; a
+     caller should keep a label on the fp32 stream only while the fp32
+     spacing at its bounds' magnitude is small against prior_sigma / 100, the
+     smallest bandwidth a fit produces (the Python engine: 500 steps per
+     prior_sigma).                                                           */
 };
 
 /*

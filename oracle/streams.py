@@ -212,9 +212,19 @@ def _bm_pair(ta, tb):
     return r * np.cos(2.0 * np.pi * tb), r * np.sin(2.0 * np.pi * tb)
 
 
+def bound32(b):
+    """A bound as the fp32 stream compares against it: the smallest float >= b
+    (tpe_sample.hpp bound32), so that low <= y < high holds in fp64 for every
+    accepted or clamped fp32 draw.  A bound fp32 holds exactly is unchanged."""
+    f = np.float32(b)
+    if float(f) < b:
+        f = np.nextafter(f, np.float32(np.inf))
+    return float(f)
+
+
 def gmm_draw32(cdf, mu, sigma, key, g, low=None, high=None):
     """Candidates g of the fp32 stream, computed in fp64 from the fp32-rounded
-    mu / sigma / bounds.
+    mu / sigma and the fp32 bounds (bound32).
 
     Attempt 0 of candidates 4m .. 4m+3 is one call at counter (m, 0, SAMP):
     word j picks candidate 4m+j's component, and the words' residuals inside
@@ -232,8 +242,7 @@ def gmm_draw32(cdf, mu, sigma, key, g, low=None, high=None):
     mu32 = np.asarray(mu, np.float64).astype(np.float32).astype(np.float64)
     sg32 = np.asarray(sigma, np.float64).astype(np.float32).astype(np.float64)
     g = np.atleast_1d(np.asarray(g, np.int64))
-    lo, hi = _bounds(low, high)
-    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    lo, hi = (bound32(b) for b in _bounds(low, high))
     n = g.size
     r = draw_words(key, g >> 2, 0, SAMP)
     pair = ((g & 2) != 0)
