@@ -25,6 +25,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+import numbers
 import os
 import time
 from dataclasses import dataclass, field, replace
@@ -1433,6 +1434,8 @@ class Engine:
         (_Replay); None: take the full path."""
         if not (self._replays and isinstance(works, WorkBatch) and opts.stream is None):
             return None
+        if not isinstance(opts.lf, numbers.Integral):  # (7.9 must not find lf = 7's record)
+            return None
         sig = _Replay.signature(self, works, opts,
                                 self.torch.cuda.current_stream(self.device).cuda_stream)
         rp = self._replays.get(sig) if sig is not None else None
@@ -1447,6 +1450,7 @@ class Engine:
         """The options as the level runs them -- the hooks' implied outputs,
         the scorer's name -- checked; and the WorkBatch, if ``works`` is one."""
         outputs, scorer = opts.outputs, opts.scorer
+        check_lf(opts.lf)
         if opts.sample_only:
             outputs = True
         if scorer is None:
@@ -2720,6 +2724,15 @@ def _lat_prefix(text):
     if v < 0 or v % 4096:
         raise ValueError("TPE_LAT_PREFIX must be 0 or a positive multiple of 4096, got %d" % v)
     return v
+
+
+def check_lf(lf):
+    """linear_forgetting as an int: an integer >= 0 (0: no forgetting, as the
+    reference's ``if LF and ...``, tpe.py:441).  A fractional or negative value
+    is an error here -- it used to be truncated / to switch the ramp off."""
+    if not isinstance(lf, numbers.Integral) or lf < 0:
+        raise ValueError("linear_forgetting must be an integer >= 0, got %r" % (lf,))
+    return int(lf)
 
 
 def _raise_errors(err):

@@ -49,7 +49,7 @@ from . import dist as hdist
 from . import rand
 from .base import as_domain, doc_loss
 from .engine import (DEFAULT_LF, TABLE_MIN_CAND, Engine, LabelResult, LabelWork, WorkBatch,
-                     _lattice_range, _params)
+                     _lattice_range, _params, check_lf)
 from .walk import decode as _decode  # engine value -> (switch value, stored value)
 from .walk import decode_level, docs_matrix, int_offset, next_level, trial_docs, trials_columnar
 
@@ -401,6 +401,7 @@ def _open_study(qi, new_ids, domain, trials, seed, kw, shard=None, verbose=False
     the study's candidates are dealt over the ranks (dist.shard)."""
     st = _Study()
     st.qi, st.new_ids, st.trials, st.seed, st.kw = qi, new_ids, trials, seed, kw
+    check_lf(kw["linear_forgetting"])  # (Engine._check_opts' rule, before any prior draw)
     st.domain = domain = as_domain(domain)  # (hyperopt's own Domain too: fmin(algo=tpe.suggest))
     st.labels = labels = list(domain.params)
     st.hist = hist = collect_history(trials, labels)

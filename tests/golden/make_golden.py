@@ -349,7 +349,89 @@ def gen_e2e(ho):
         save("e2e_" + name, arrays, meta)
 
 
+# ---------------------------------------------------------------------------
+# unit-level vectors at non-default linear forgetting and prior weight
+# ---------------------------------------------------------------------------
+SETTINGS_LF = (1, 2, 7, 24, 26, 1000)
+SETTINGS_PW = (1e-3, 0.3, 7.5)
+SETTINGS_N_CAP = 300
+SETTINGS_RANDINT = (3, 9)                      # a non-zero `low`
+SETTINGS_P = (0.1, 0.2, 0.3, 0.15, 0.25)       # K*(pw*p) != (K*pw)*p at 0.3 and 1e-3
+# the ramp's last entry fl((num-1)*step + start) misses 1.0 by one ulp here,
+# were it not pinned (np.linspace sets it to `stop`)
+SETTINGS_PIN = ((1, 15), (2, 10))
+
+
+def settings_grid():
+    """(lf, n) pairs: n around lf (no ramp, a ramp of 1, 2, 3 entries) and 2 lf + 1."""
+    pairs = []
+    for lf in SETTINGS_LF:
+        for n in (lf - 1, lf, lf + 1, lf + 2, lf + 3, 2 * lf + 1):
+            n = min(n, SETTINGS_N_CAP)
+            if (lf, n) not in pairs:
+                pairs.append((lf, n))
+    return pairs + [p for p in SETTINGS_PIN if p not in pairs]
+
+
+def gen_unit_settings(ho):
+    """adaptive_parzen_normal, ap_randint_sampler and ap_categorical_sampler
+    (tpe.py:399-467, 578-615) with LF= and prior_weight= away from 25 and 1.
+    The categorical `p` is 2-D, as in the live graph (pyll/base.py:1053-1060)."""
+    tpe, pyll = ho.tpe, ho.pyll
+    rng = np.random.RandomState(4321)
+    arrays, meta = {}, {"numpy": np.__version__, "parzen": [], "cat": []}
+    low, high = SETTINGS_RANDINT
+    p = np.asarray(SETTINGS_P)
+    K = p.size
+
+    def cat_post(kind, obs, pw, lf):
+        fn = tpe.adaptive_parzen_samplers[kind]
+        if kind == "randint":
+            post = fn(pyll.as_apply(obs), pw, low, high, size=5,
+                      rng=np.random.RandomState(0), LF=lf)
+        else:
+            post = fn(pyll.as_apply(obs), pw, pyll.as_apply(np.tile(p, (5, 1))), size=5,
+                      rng=np.random.RandomState(0), LF=lf)
+        return np.asarray(pyll.rec_eval(post.pos_args[0]), float)
+
+    for lf, n in settings_grid():
+        obs = rng.uniform(-5, 5, n)
+        i = len(meta["parzen"])
+        arrays["parzen%d_obs" % i] = obs
+        for pw in SETTINGS_PW:
+            w, mu, sig = tpe.adaptive_parzen_normal(obs, pw, 0.0, 10.0, LF=lf)
+            arrays["parzen%d_pw%g_w" % (i, pw)] = w
+            arrays["parzen%d_pw%g_mu" % (i, pw)] = mu
+            arrays["parzen%d_pw%g_sigma" % (i, pw)] = sig
+        meta["parzen"].append(dict(lf=lf, n=n, prior_mu=0.0, prior_sigma=10.0))
+
+        # category ids 0..K-1 (randint adds `low`); "alone": the observation at
+        # ramp position num-1 is the only one of the top category
+        variants = [("random", rng.randint(0, K, n))]
+        if (lf, n) in SETTINGS_PIN:
+            alone = rng.randint(0, K - 1, n)
+            alone[n - lf - 1] = K - 1
+            variants.append(("alone", alone))
+        for tag, cobs in variants:
+            for kind in ("randint", "categorical"):
+                if kind == "categorical" and n == 0:
+                    continue  # the reference raises (bincount of an empty list with p)
+                j = len(meta["cat"])
+                kobs = (cobs + (low if kind == "randint" else 0)).astype(np.int64)
+                arrays["cat%d_obs" % j] = kobs
+                for pw in SETTINGS_PW:
+                    arrays["cat%d_pw%g_p" % (j, pw)] = cat_post(kind, kobs, pw, lf)
+                meta["cat"].append(dict(kind=kind, lf=lf, n=n, obs=tag))
+    meta.update(prior_weights=list(SETTINGS_PW), randint=list(SETTINGS_RANDINT),
+                p=list(SETTINGS_P))
+    save("units_settings", arrays, meta)
+
+
+GENERATORS = {"units": gen_units, "e2e": gen_e2e, "units_settings": gen_unit_settings}
+
 if __name__ == "__main__":
+    # every fixture, or only the ones named:  make_golden.py units_settings
+    names = sys.argv[1:] or list(GENERATORS)
     ho = load_reference()
-    gen_units(ho)
-    gen_e2e(ho)
+    for name in names:
+        GENERATORS[name](ho)

@@ -468,3 +468,33 @@ def test_engine_switch_without_diag_warns(monkeypatch):
         assert E._knob("TPE_SIDE_STREAM", "1") == "1"
     monkeypatch.setenv("TPE_DIAG", "1")
     assert E._knob("TPE_SIDE_STREAM", "1") == "0"
+
+
+@pytest.mark.parametrize("bad", [-1, -25, 7.9, 0.5, 25.0, "7", None, np.float64(7.0)])
+def test_linear_forgetting_must_be_a_non_negative_integer(bad):
+    """Engine._check_opts: a fractional lf used to be truncated (7.9 -> 7) and
+    a negative one silently meant "no ramp"; both raise now, and tpe.suggest /
+    suggest_many raise the same error before anything is drawn."""
+    from hyperopt_amd import hp
+    from hyperopt_amd.engine import Engine, LabelWork, _LevelOpts
+    eng = Engine.__new__(Engine)  # option logic only: no device state
+    eng._init_host_state()
+    works = [LabelWork("u", "uniform", (-5.0, 5.0), np.zeros(3), np.zeros(5))]
+    with pytest.raises(ValueError, match="linear_forgetting"):
+        eng._check_opts(works, _LevelOpts(1.0, bad))
+    domain = Domain(lambda p: 0.0, {"x": hp.uniform("x", -5, 5)})
+    with pytest.raises(ValueError, match="linear_forgetting"):
+        tpe.suggest([0], domain, Trials(), 0, linear_forgetting=bad, verbose=False)
+    with pytest.raises(ValueError, match="linear_forgetting"):
+        tpe.suggest_many([tpe.SuggestRequest([0], domain, Trials(), 0, linear_forgetting=bad)])
+
+
+@pytest.mark.parametrize("ok", [0, 1, 25, 1000, np.int32(7), np.int64(26)])
+def test_linear_forgetting_integers_pass(ok):
+    from hyperopt_amd.engine import Engine, LabelWork, _LevelOpts, check_lf
+    eng = Engine.__new__(Engine)
+    eng._init_host_state()
+    works = [LabelWork("u", "uniform", (-5.0, 5.0), np.zeros(3), np.zeros(5))]
+    opts, batch = eng._check_opts(works, _LevelOpts(1.0, ok))
+    assert batch is None and opts.scorer == "auto"
+    assert check_lf(ok) == int(ok) and type(check_lf(ok)) is int

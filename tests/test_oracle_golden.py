@@ -70,6 +70,54 @@ def test_categorical_posterior(i, pw):
     _same(p, UNITS["cat%d_pw%g_p" % (i, pw)])
 
 
+SETTINGS, SMETA = load("units_settings")
+
+
+@pytest.mark.parametrize("i", range(len(SMETA["parzen"])))
+def test_parzen_settings(i):
+    """adaptive_parzen_normal at LF and prior weight away from the defaults
+    (make_golden.gen_unit_settings): every array bit for bit."""
+    m = SMETA["parzen"][i]
+    obs = SETTINGS["parzen%d_obs" % i]
+    assert obs.size == m["n"]
+    for pw in SMETA["prior_weights"]:
+        w, mu, sig = O.adaptive_parzen_normal(obs, pw, m["prior_mu"], m["prior_sigma"], m["lf"])
+        _same(w, SETTINGS["parzen%d_pw%g_w" % (i, pw)])
+        _same(mu, SETTINGS["parzen%d_pw%g_mu" % (i, pw)])
+        _same(sig, SETTINGS["parzen%d_pw%g_sigma" % (i, pw)])
+
+
+@pytest.mark.parametrize("i", range(len(SMETA["cat"])))
+def test_categorical_posterior_settings(i):
+    """ap_randint_sampler / ap_categorical_sampler (2-D p) at the same settings."""
+    m = SMETA["cat"][i]
+    obs = SETTINGS["cat%d_obs" % i]
+    assert obs.size == m["n"]
+    for pw in SMETA["prior_weights"]:
+        if m["kind"] == "randint":
+            p = O.randint_posterior(obs, pw, *SMETA["randint"], lf=m["lf"])
+        else:
+            p = O.categorical_posterior(obs, pw, np.tile(SMETA["p"], (5, 1)), lf=m["lf"])
+        _same(p, SETTINGS["cat%d_pw%g_p" % (i, pw)])
+
+
+def test_settings_fixture_covers_the_grid():
+    lfs, pairs = {1, 2, 7, 24, 26, 1000}, set()
+    for m in SMETA["parzen"]:
+        pairs.add((m["lf"], m["n"]))
+    for lf in lfs:
+        for n in (lf - 1, lf, lf + 1, lf + 2, lf + 3, 2 * lf + 1):
+            assert (lf, min(n, 300)) in pairs
+    assert {(1, 15), (2, 10)} <= pairs
+    assert SMETA["prior_weights"] == [1e-3, 0.3, 7.5]
+    cats = {(m["kind"], m["lf"], m["n"], m["obs"]) for m in SMETA["cat"]}
+    for lf, n in pairs:
+        assert ("randint", lf, n, "random") in cats
+        assert n == 0 or ("categorical", lf, n, "random") in cats
+    for pin in ((1, 15), (2, 10)):
+        assert ("randint",) + pin + ("alone",) in cats and ("categorical",) + pin + ("alone",) in cats
+
+
 def _label_pipeline(arrays, meta, lab):
     spec = meta["specs"][lab]
     oi = arrays["obs_idxs/" + lab]
