@@ -22,12 +22,25 @@ constexpr int kCatKey = 256;  // categories of the rank-key fast path (8-bit cat
 // at counter (g >> 2, attempt 0) -- four candidates per call -- and its
 // category is the first k with word < thr[k], thr[k] = ceil(cdf[k] / cdf[K-1]
 // * 2^32): the inverse CDF at 2^-32 resolution, the same rule as the
-// continuous samplers' component choice.
+// continuous samplers' component choice.  A threshold saturates at kThrSat =
+// 2^32 - 1, so that one word is below no threshold; it goes where 2^32 - 2
+// goes, to the first category whose threshold saturates (cat_edge: its
+// interval ends at 2^32).  That category has mass; the ones after it -- a
+// trailing category of probability zero, which hp.pchoice allows -- take no
+// word at all.
+constexpr uint32_t kThrSat = 0xFFFFFFFFu;
 __device__ __forceinline__ uint32_t cat_thr(const double* cdf, int K, int k) {
   const double t = ceil(cdf[k] / cdf[K - 1] * 4294967296.0);
-  return (t >= 4294967295.0) ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
+  return (t >= 4294967295.0) ? kThrSat : (t > 0.0 ? (uint32_t)t : 0u);
+}
+// end of category k's word interval [cat_edge(k - 1), cat_edge(k)); k = -1: 0
+__device__ __forceinline__ uint64_t cat_edge(const double* cdf, int K, int k) {
+  if (k < 0) return 0ull;
+  const uint32_t t = cat_thr(cdf, K, k);
+  return t == kThrSat ? (1ull << 32) : (uint64_t)t;
 }
 __device__ __forceinline__ int cat_search(const double* cdf, int K, uint32_t w) {
+  w = min(w, kThrSat - 1u);
   int lo = 0, hi = K - 1;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -154,14 +167,18 @@ __global__ __launch_bounds__(kBS) void k_score_cat(
   __syncthreads();
   const bool in_regs = K <= KR;  // block-uniform
   uint32_t thr[KR - 1];
+  int klast = 0;  // the first category whose threshold saturates (at most K - 1)
 #pragma unroll
-  for (int j = 0; j + 1 < KR; ++j) thr[j] = (in_regs && j + 1 < K) ? s_thr[j] : 0xFFFFFFFFu;
+  for (int j = 0; j + 1 < KR; ++j) {
+    thr[j] = (in_regs && j + 1 < K) ? s_thr[j] : kThrSat;
+    klast += (thr[j] != kThrSat) ? 1 : 0;
+  }
   auto category = [&](uint32_t w) __attribute__((always_inline)) -> int {
     if (in_regs) {
       int k = 0;
 #pragma unroll
       for (int j = 0; j + 1 < KR; ++j) k += (w >= thr[j]) ? 1 : 0;
-      return min(k, K - 1);
+      return min(k, klast);  // (k > klast for the word 2^32 - 1 alone)
     }
     return cat_search(cb, K, w);
   };
@@ -240,10 +257,10 @@ __global__ __launch_bounds__(kBS) void k_cat_decide(
     const int K = CB.n_cat;
     for (int k = threadIdx.x; k < K && !open; k += kBS) {
       const double sk = logp[CB.p_off + k] - logp[CA.p_off + k];
-      // category k takes the words [thr[k-1], thr[k]) (thr[-1] = 0, the last one
-      // up to 2^32)
-      const uint64_t t0 = k > 0 ? cat_thr(cdf + CB.p_off, K, k - 1) : 0ull;
-      const uint64_t t1 = k < K - 1 ? (uint64_t)cat_thr(cdf + CB.p_off, K, k) : (1ull << 32);
+      // category k takes the words [cat_edge(k - 1), cat_edge(k)): none when it
+      // has no mass, a trailing category included
+      const uint64_t t0 = cat_edge(cdf + CB.p_off, K, k - 1);
+      const uint64_t t1 = cat_edge(cdf + CB.p_off, K, k);
       open = better(sk, INT64_MAX, b.score, b.index) && t1 > t0;
     }
     open = __syncthreads_or(open);

@@ -16,8 +16,12 @@ namespace {
 // ---------------------------------------------------------------------------
 // categorical posteriors
 // ---------------------------------------------------------------------------
-// numpy's pairwise_sum for float64 (n <= 8192: one buffer), so
-// `pseudocounts / np.sum(pseudocounts)` is reproduced bit for bit.
+// numpy's pairwise_sum for float64, so `pseudocounts / np.sum(pseudocounts)`
+// is reproduced bit for bit.  np.sum reduces a contiguous array buffer by
+// buffer: one pairwise sum up to kNpBuf elements, and past that the pairwise
+// sums of the consecutive kNpBuf-element chunks added in order (np_sum).
+constexpr int64_t kNpBuf = 8192;  // numpy's reduction buffer, in elements
+
 __device__ double np_pw_leaf(const double* a, int64_t n) {
   if (n < 8) {
     double r = 0.0;
@@ -71,6 +75,14 @@ __device__ double np_pairwise_sum(const double* a, int64_t n) {
     }
   }
   return ret;
+}
+
+// np.sum of n contiguous doubles (called by one thread of the block)
+__device__ double np_sum(const double* a, int64_t n) {
+  double total = np_pairwise_sum(a, std::min(n, kNpBuf));
+  for (int64_t s = kNpBuf; s < n; s += kNpBuf)
+    total += np_pairwise_sum(a + s, std::min(n - s, kNpBuf));
+  return total;
 }
 
 constexpr int kCatBS = 256;
@@ -493,7 +505,7 @@ __global__ __launch_bounds__(kCatBS) void k_cat_finalize(const tpe_cat_seg* __re
   const tpe_cat_seg& S = segs[blockIdx.x];
   const int K = S.n_cat;
   __shared__ double total;
-  if (threadIdx.x == 0) total = np_pairwise_sum(p + S.p_off, K);
+  if (threadIdx.x == 0) total = np_sum(p + S.p_off, K);
   __syncthreads();
   for (int k = threadIdx.x; k < K; k += kCatBS) {
     const double pk = p[S.p_off + k] / total;

@@ -295,13 +295,30 @@ def gmm_draw32(cdf, mu, sigma, key, g, low=None, high=None):
 # ---------------------------------------------------------------------------
 # categorical candidates
 # ---------------------------------------------------------------------------
+def categorical_of_word(cdf, w):
+    """Category of the 32-bit words w by the threshold rule on the categories'
+    cdf.  The word 2^32 - 1, below no saturated threshold, goes where 2^32 - 2
+    goes: to the first category whose threshold saturates (it has mass), never
+    to a trailing category of probability zero."""
+    return component_thr(thresholds(cdf), np.minimum(_u64(w), np.uint64(0xFFFFFFFE)))
+
+
 def categorical_draw(cdf, key, g):
     """Category of candidates g: word g & 3 of the call at counter
-    (g >> 2, 0, SAMP), by the threshold rule on the categories' cdf."""
+    (g >> 2, 0, SAMP), by categorical_of_word."""
     g = np.atleast_1d(np.asarray(g, np.int64))
     r = draw_words(key, g >> 2, 0, SAMP)
     w = r[np.arange(g.size), (g & 3)]
-    return component_thr(thresholds(cdf), w)
+    return categorical_of_word(cdf, w)
+
+
+def categorical_intervals(cdf):
+    """(lo, hi): category k takes the words [lo[k], hi[k]) under
+    categorical_draw's rule -- thr[k-1] to thr[k], the first category counting
+    from 0 and a saturated threshold as 2^32."""
+    thr = thresholds(cdf)
+    hi = np.where(thr == np.uint64(0xFFFFFFFF), np.uint64(1 << 32), thr)
+    return np.concatenate([[np.uint64(0)], hi[:-1]]), hi
 
 
 # ---------------------------------------------------------------------------
