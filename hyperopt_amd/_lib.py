@@ -168,6 +168,7 @@ _SIGNATURES = {
     "tpe_graph_destroy": (_I, [_P]),
     "tpe_check_transcendentals": (_I, [_P, _P]),
     "tpe_fold_check": (_I, [_P, _I64, ctypes.c_double, _I64, _I, _P, _P]),
+    "tpe_exp_neg64_check": (_I, [_P, _I64, _P, _P]),
     "tpe_mixture_scratch_bytes": (_I64, [_I, _I]),
     "tpe_mixture_prepare": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tpe_smallest_rows": (_I64, [_P, _I64, _I64, _P]),

@@ -3,7 +3,8 @@
 // and broadcast_best's argmax (tpe.py:649-658) over the components the
 // table's plan (tpe_table.hip) cannot rule out.
 //
-// Exports: tpe_pruned64_partials, tpe_score_pruned64.
+// Exports: tpe_pruned64_partials, tpe_score_pruned64, tpe_exp_neg64_check
+// (the sum's exp on a caller's arguments, for the tests).
 #include "tpe_table.hpp"
 
 namespace tpe {
@@ -41,9 +42,14 @@ constexpr int kP64N = kBS * kR64P;       // candidates per block (sorted togethe
 // rint(32 v / ln2), r = v - n ln2/32 (Cody-Waite, the high part's 32 bits
 // keep n ln2_hi exact), exp(r) by its degree-6 Taylor polynomial (|r| <=
 // ln2/64: truncation < 2^-57), times 2^((n mod 32)/32) from a 32-entry table
-// (correctly rounded) and 2^(n div 32) -- ~1 ulp, the library exp's accuracy,
-// with 13 instead of 17 dependent fp64 steps and no overflow branch (round 6,
-// with 2 048 candidates per block: fp64 C3 level 256 -> 217 ms, same-box A/B)
+// (correctly rounded) and 2^(n div 32) -- within 3.25 * 2^-53 relative (three
+// roundings, the truncation, the reduction), plus 2^-1074 where the result is
+// subnormal; measured through tpe_exp_neg64_check on 1.26e6 arguments (every
+// reduction tie among them): at most 1.93 ulp of the result (2.73 * 2^-53
+// relative) on normal results, one unit of 2^-1074 on subnormal ones -- a
+// sum of such terms keeps the scorer's 1e-13 -- with 13 instead of 17
+// dependent fp64 steps and no overflow branch (round 6, with 2 048
+// candidates per block: fp64 C3 level 256 -> 217 ms, same-box A/B)
 __constant__ double kExp2Tab[32] = {
     0x1.0000000000000p+0, 0x1.059b0d3158574p+0, 0x1.0b5586cf9890fp+0, 0x1.11301d0125b51p+0,
     0x1.172b83c7d517bp+0, 0x1.1d4873168b9aap+0, 0x1.2387a6e756238p+0, 0x1.29e9df51fdee1p+0,
@@ -262,10 +268,34 @@ __global__ __launch_bounds__(kBS) void k_score_pruned64(
   b = block_best<kBS>(b, red);
   if (threadIdx.x == 0) *P = tpe_best{b.score, b.index, b.value, 0};
 }
+
+// exp_neg64 on a caller's arguments (tpe_exp_neg64_check: the table staged in
+// LDS as k_score_pruned64 stages it)
+__global__ __launch_bounds__(kBS) void k_exp_neg64_check(const double* __restrict__ v, int64_t n,
+                                                         double* __restrict__ out) {
+  __shared__ double s_etab[32];
+  if (threadIdx.x < 32) s_etab[threadIdx.x] = kExp2Tab[threadIdx.x];
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * kBS;
+  for (int64_t i = (int64_t)blockIdx.x * kBS + threadIdx.x; i < n; i += stride)
+    out[i] = exp_neg64(v[i], s_etab);
+}
 }  // namespace
 }  // namespace tpe
 
 using namespace tpe;
+
+extern "C" int tpe_exp_neg64_check(const double* v, int64_t n, double* out, void* stream) {
+  if (n < 0 || (n > 0 && (!v || !out))) {
+    set_error("tpe_exp_neg64_check: bad arguments (n=%lld)", (long long)n);
+    return TPE_E_ARG;
+  }
+  if (n == 0) return TPE_OK;
+  const int64_t blocks = (n + kBS - 1) / kBS;
+  hipLaunchKernelGGL(k_exp_neg64_check, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBS),
+                     0, (hipStream_t)stream, v, n, out);
+  return check_launch("tpe_exp_neg64_check");
+}
 
 extern "C" int64_t tpe_pruned64_partials(const tpe_job* host_jobs, int n_jobs) {
   return tiles_per_job(host_jobs, n_jobs, kP64N) * n_jobs;

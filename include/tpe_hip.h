@@ -921,6 +921,12 @@ int tpe_check_transcendentals(double* out, void* stream);
  * the serial chain s = s + w bit for bit. */
 int tpe_fold_check(const double* list, int64_t n, double s0, int64_t done, int scope, double* out,
                    void* stream);
+/* Self-check of the pruned exact fp64 scorer's exp (exp_neg64, tpe_pruned64.hip):
+ * out[i] = exp_neg64(v[i]) for i in [0, n), v and out device arrays,
+ * asynchronous on `stream`.  exp_neg64 is specified for v <= 0 and NaN: 0
+ * below -745.2, NaN for NaN, else exp(v) within 3.25 * 2^-53 relative (plus
+ * 2^-1074 absolute where the result is subnormal). */
+int tpe_exp_neg64_check(const double* v, int64_t n, double* out, void* stream);
 
 /* host: writes sizeof(tpe_seg, tpe_cat_seg, tpe_job, tpe_best, tpe_table, tpe_gather,
  * tpe_history, tpe_prior, tpe_op, tpe_band, tpe_colspec) to out[0..n); returns 11 */

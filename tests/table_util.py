@@ -2,7 +2,10 @@
 is shared with test_gpu_band_paths.py): a job's tpe_table record, its region
 of the engine's cell buffer decoded into exact doubles, its slices of the
 plan's reach windows and wide list, the points of a cell as the kernels form
-them, and the fp64 reference of what a cell stores.
+them, and the fp64 reference of what a cell stores.  The plan alone
+(read_plan, check_plan) is shared with test_gpu_pruned64_stages.py: the
+pruned exact fp64 scorer asks for the same plan with its own margin and draw
+bound and builds no cells.
 """
 import numpy as np
 
@@ -16,6 +19,8 @@ COOP_CELLS = 4096  # kCoopCells: tables of at most this many cells build a quad 
 DRAW_Z = 5.8      # kDrawZ
 RHO_LIM = 5.8     # kRhoLim
 TAU_TABLE = 17.0  # TPE_TAU_TABLE
+DRAW_Z64 = 8.7    # kDrawZ64 (tpe_pruned64.hip)
+TAU_EXACT = 40.0  # kTauExact (tpe_pruned64.hip)
 AB_MAX = 0.6768   # kAbMax
 
 
@@ -103,12 +108,42 @@ def _dev(eng, name, a, b, dtype):
     return eng._bufs[name][a:b].cpu().numpy().view(dtype).copy()
 
 
-def read_table(eng, pos):
+def _read_plan(T, eng, pos):
+    """The plan part of job ``pos``: its tpe_job, tpe_table and (host) segment
+    records, and both mixtures' slices of coef64, reach_hi, reach_lo and
+    wide_idx, the below mixture's of mu and sigma."""
     segs, jobs = eng.last_plan[0], eng.last_plan[3]
-    T = Table()
     T.job = job = jobs[pos].copy()
     ts = L.TABLE_DTYPE.itemsize
     T.tab = _dev(eng, "tables", ts * pos, ts * (pos + 1), L.TABLE_DTYPE)[0]
+    T.seg_b, T.seg_a = segs[int(job["below"])].copy(), segs[int(job["above"])].copy()
+    for half, sg in (("b", T.seg_b), ("a", T.seg_a)):
+        k0, k1 = int(sg["comp_off"]), int(sg["comp_off"]) + int(sg["n_obs"]) + 1
+        setattr(T, "coef_" + half, _dev(eng, "coef64", 32 * k0, 32 * k1, np.float64).reshape(-1, 4))
+        setattr(T, "reach_hi_" + half, _dev(eng, "reach_hi", 8 * k0, 8 * k1, np.float64))
+        setattr(T, "reach_lo_" + half, _dev(eng, "reach_lo", 8 * k0, 8 * k1, np.float64))
+        setattr(T, "wide_" + half, _dev(eng, "wide_idx", 4 * k0, 4 * k1, np.int32))
+        if half == "b":
+            T.mu_b = _dev(eng, "mu", 8 * k0, 8 * k1, np.float64)
+            T.sigma_b = _dev(eng, "sigma", 8 * k0, 8 * k1, np.float64)
+    return T
+
+
+def read_plan(eng, pos):
+    """Job ``pos`` of the level an engine just ran with the pruned exact fp64
+    scorer (precision=64, exact64="pruned"; one scorer group, so the job's
+    tpe_table record is record ``pos``): the plan part of a Table -- such a
+    job has no cells (tbl_cap == 0)."""
+    T = _read_plan(Table(), eng, pos)
+    assert int(T.job["tbl_cap"]) == 0
+    T.nb = T.cap = 0
+    return T
+
+
+def read_table(eng, pos):
+    jobs = eng.last_plan[3]
+    T = _read_plan(Table(), eng, pos)
+    job = T.job
     T.nb, T.cap = nb, cap = int(T.tab["nb"]), int(job["tbl_cap"])
     assert 1 <= nb <= cap
     first = int(jobs["tbl_off"][jobs["tbl_cap"] > 0].min())
@@ -128,16 +163,6 @@ def read_table(eng, pos):
     o = (cap * 72 + 15) & ~15
     assert o + 16 * cap <= SLOT_B * cap
     T.q = raw[o:o + 16 * cap].view(np.float32).reshape(cap, 4)[:nb].astype(np.float64)
-    T.seg_b, T.seg_a = segs[int(job["below"])].copy(), segs[int(job["above"])].copy()
-    for half, sg in (("b", T.seg_b), ("a", T.seg_a)):
-        k0, k1 = int(sg["comp_off"]), int(sg["comp_off"]) + int(sg["n_obs"]) + 1
-        setattr(T, "coef_" + half, _dev(eng, "coef64", 32 * k0, 32 * k1, np.float64).reshape(-1, 4))
-        setattr(T, "reach_hi_" + half, _dev(eng, "reach_hi", 8 * k0, 8 * k1, np.float64))
-        setattr(T, "reach_lo_" + half, _dev(eng, "reach_lo", 8 * k0, 8 * k1, np.float64))
-        setattr(T, "wide_" + half, _dev(eng, "wide_idx", 4 * k0, 4 * k1, np.int32))
-        if half == "b":
-            T.mu_b = _dev(eng, "mu", 8 * k0, 8 * k1, np.float64)
-            T.sigma_b = _dev(eng, "sigma", 8 * k0, 8 * k1, np.float64)
     return T
 
 
@@ -187,6 +212,44 @@ def plan_comp(coef, T, prior_sigma):
         wide = inv <= 4.0 / prior_sigma  # (the prior itself: inv = 1 / prior_sigma)
         r = z / inv * (1.0 + 1e-9) + 1e-12 * np.abs(mu)
     return wide, np.where(wide, -np.inf, mu + r), np.where(wide, np.inf, mu - r), hk
+
+
+def check_plan(T, reach=True):
+    """The plan's windows (statement F of test_gpu_table_cells.py, whatever
+    the margin and draw bound the plan was asked for): reach_hi / reach_lo are
+    the running max / reversed running min of plan_comp restated from the
+    record's own floors (relative 1e-12), the wide list and its counts, the
+    admissible half-widths.  ``reach=False``: the reach arrays have been
+    planned over since (a band overflow's exact re-score); the wide list does
+    not depend on the margin."""
+    tab = T.tab
+    for half, seg, Tx, nwide, hx in (("b", T.seg_b, "T_below", "n_wide_below", "h_below"),
+                                     ("a", T.seg_a, "T_above", "n_wide_above", "h_above")):
+        coef = getattr(T, "coef_" + half)
+        rh, rl = getattr(T, "reach_hi_" + half), getattr(T, "reach_lo_" + half)
+        psig = float(seg["prior_sigma"])
+        assert psig > 0.0 and np.all(np.diff(coef[:, 0]) >= 0.0)  # sorted by mean
+        wide, hr, lr, hk = plan_comp(coef, float(tab[Tx]), psig)
+        assert wide.any()  # the prior at least
+        want_hi = np.maximum.accumulate(hr)
+        want_lo = np.minimum.accumulate(lr[::-1])[::-1]
+        for got, want in ((rh, want_hi), (rl, want_lo)) if reach else ():
+            inf = np.isinf(want)
+            np.testing.assert_array_equal(got[inf], want[inf])
+            np.testing.assert_allclose(got[~inf], want[~inf], rtol=1e-12, atol=0)
+            assert np.all(got[1:] >= got[:-1])  # non-decreasing
+        # a wide component holds -inf / +inf in its own slot: the running
+        # extremes pass over it unchanged
+        k = np.flatnonzero(wide)
+        prev = np.where(k > 0, rh[np.maximum(k - 1, 0)], -np.inf)
+        nxt = np.where(k < wide.size - 1, rl[np.minimum(k + 1, wide.size - 1)], np.inf)
+        if reach:
+            np.testing.assert_array_equal(rh[k], prev)
+            np.testing.assert_array_equal(rl[k], nxt)
+        n = int(tab[nwide])
+        assert n == k.size
+        np.testing.assert_array_equal(getattr(T, "wide_" + half)[:n], k)
+        np.testing.assert_allclose(float(tab[hx]), hk.min(), rtol=1e-12, atol=0)
 
 
 def mix_eps(items, coop):

@@ -54,6 +54,18 @@ def test_fold_check_argument_errors():
         assert b"tpe_fold_check" in lib.tpe_last_error()
 
 
+def test_exp_neg64_check_argument_errors():
+    """tpe_exp_neg64_check rejects a negative n and a missing array before it
+    launches anything; n = 0 is nothing to do."""
+    lib = L.load()
+    buf = (ctypes.c_double * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for args in ((p, -1, p), (None, 4, p), (p, 4, None)):
+        assert lib.tpe_exp_neg64_check(*args, None) == -1, args
+        assert b"tpe_exp_neg64_check" in lib.tpe_last_error()
+    assert lib.tpe_exp_neg64_check(None, 0, None, None) == 0
+
+
 def _ops(*records):
     ops = np.zeros(len(records), L.OP_DTYPE)
     for i, (code, args) in enumerate(records):

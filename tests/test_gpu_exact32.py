@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 KINDS = [("uniform", (-5.0, 5.0), lambda r, n: r.uniform(-5, 5, n)),
          ("normal", (0.0, 2.0), lambda r, n: r.normal(0, 2, n)),
-         ("loguniform", (-5.0, 0.0), lambda r, n: np.exp(r.uniform(-5, 0, n)))]
+         ("loguniform", (-5.0, 0.0), lambda r, n: np.exp(r.uniform(-5, 0, n))),
+         ("lognormal", (0.0, 1.0), lambda r, n: np.exp(r.normal(0, 1, n)))]
 
 
 @pytest.fixture(scope="module")

@@ -254,33 +254,7 @@ def _check_plan(T, reach=True):
     with its own exclusion margin -- the table's are gone; the wide list does
     not depend on the margin."""
     tab = T.tab
-    for half, seg, Tx, nwide, hx in (("b", T.seg_b, "T_below", "n_wide_below", "h_below"),
-                                     ("a", T.seg_a, "T_above", "n_wide_above", "h_above")):
-        coef = getattr(T, "coef_" + half)
-        rh, rl = getattr(T, "reach_hi_" + half), getattr(T, "reach_lo_" + half)
-        psig = float(seg["prior_sigma"])
-        assert psig > 0.0 and np.all(np.diff(coef[:, 0]) >= 0.0)  # sorted by mean
-        wide, hr, lr, hk = TU.plan_comp(coef, float(tab[Tx]), psig)
-        assert wide.any()  # the prior at least
-        want_hi = np.maximum.accumulate(hr)
-        want_lo = np.minimum.accumulate(lr[::-1])[::-1]
-        for got, want in ((rh, want_hi), (rl, want_lo)) if reach else ():
-            inf = np.isinf(want)
-            np.testing.assert_array_equal(got[inf], want[inf])
-            np.testing.assert_allclose(got[~inf], want[~inf], rtol=1e-12, atol=0)
-            assert np.all(got[1:] >= got[:-1])  # non-decreasing
-        # a wide component holds -inf / +inf in its own slot: the running
-        # extremes pass over it unchanged
-        k = np.flatnonzero(wide)
-        prev = np.where(k > 0, rh[np.maximum(k - 1, 0)], -np.inf)
-        nxt = np.where(k < wide.size - 1, rl[np.minimum(k + 1, wide.size - 1)], np.inf)
-        if reach:
-            np.testing.assert_array_equal(rh[k], prev)
-            np.testing.assert_array_equal(rl[k], nxt)
-        n = int(tab[nwide])
-        assert n == k.size
-        np.testing.assert_array_equal(getattr(T, "wide_" + half)[:n], k)
-        np.testing.assert_allclose(float(tab[hx]), hk.min(), rtol=1e-12, atol=0)
+    TU.check_plan(T, reach=reach)
     # the stored bound is mix_eps of the build's deepest sum, cooperative or per wave
     coop = T.nb <= TU.COOP_CELLS
     want = TU.mix_eps(int(tab["build_items"]), coop)
