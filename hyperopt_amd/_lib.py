@@ -65,6 +65,14 @@ COND_TERM_DTYPE = np.dtype([("col", "<i4"), ("value", "<i4")], align=True)
 # tpe_rows_active's program limits (tpe_hip.h TPE_COND_MAX_*)
 COND_MAX_LABELS, COND_MAX_CLAUSES, COND_MAX_TERMS = 128, 256, 256
 E_UNSUPPORTED = -3
+# the joint criterion (tpe_hip.h tpe_joint_label, TPE_JOINT_*)
+JOINT_LABEL_DTYPE = np.dtype([
+    ("kind", "<i4"), ("flags", "<i4"), ("col", "<i4"), ("n_cat", "<i4"), ("lo", "<f8"),
+    ("hi", "<f8"), ("q", "<f8"), ("prior_mu", "<f8"), ("prior_sigma", "<f8"), ("prior_r", "<f8"),
+    ("shift", "<f8"), ("tab_off", "<i8")], align=True)
+JOINT_CONT, JOINT_QUANT, JOINT_CAT = 0, 1, 2
+JOINT_LOG, JOINT_BOUNDED = 1, 2
+JOINT_MAX_CAT = 65536
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
 # tpe_run_ops record codes (tpe_hip.h TPE_OP_*): entry point -> code
@@ -161,6 +169,13 @@ _SIGNATURES = {
     "tpe_pool_distinct": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _I64, _P, _I64, _P, _I, _P, _P,
                                _P, _P, _P]),
     "tpe_grid_fold": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
+    "tpe_joint_set_doubles": (_I64, [_I, _I64]),
+    "tpe_joint_scratch_bytes": (_I64, [_I64, _I64]),
+    "tpe_joint_prep": (_I, [_P, _P, _I, _P, _P, _I64, _I, _P, _I64, _P, _P]),
+    "tpe_joint_score": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _P, _P,
+                             _P, _P]),
+    "tpe_joint_chunk": (_I, []),
+    "tpe_joint_struct_sizes": (_I, [_P, _I]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),
@@ -251,6 +266,9 @@ def load():
     lib.tpe_sampled_struct_sizes(ctypes.cast(ssz, _P), 1)
     if tuple(ssz) != (COND_TERM_DTYPE.itemsize,):
         raise ImportError("hyperopt_amd: tpe_cond_term size mismatch %s" % (tuple(ssz),))
+    lib.tpe_joint_struct_sizes(ctypes.cast(ssz, _P), 1)
+    if tuple(ssz) != (JOINT_LABEL_DTYPE.itemsize,):
+        raise ImportError("hyperopt_amd: tpe_joint_label size mismatch %s" % (tuple(ssz),))
     _lib = lib
     return lib
 

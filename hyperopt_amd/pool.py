@@ -44,6 +44,12 @@ suggest fresh configurations only.
 separable over the axes, so the scorers see every axis value once and
 ``tpe_grid_fold`` (csrc/tpe_grid.hip) decodes the rows and sums the per-value
 terms; the device holds the axes, S and the taken mask, 9 bytes per row.
+
+``joint=True`` (``score_configs``, ``suggest_from_pool``, ``suggest_sampled``)
+replaces the sum over the always-live labels by one Parzen mixture over whole
+configurations, J = log L_below - log L_above (joint.py; csrc/tpe_joint.hip
+builds both sets from the resident history and scores the rows); the fold
+adds the terms of the labels under a ``switch`` onto J.
 """
 from __future__ import annotations
 
@@ -55,6 +61,7 @@ import time
 import numpy as np
 
 from . import _lib as _L
+from . import joint as _J
 from .base import as_domain
 from .engine import CONTINUOUS, _params
 from .walk import INT_KINDS, int_offset, trial_docs
@@ -879,14 +886,48 @@ def _history_inputs(domain, trials, gamma, hist=None):
     return eng, obs
 
 
-def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None):
+GRID_JOINT = ("the joint criterion is not separable over the axes of a GridPool; score its rows "
+              "as a Pool (GridPool.to_pool())")
+
+
+def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None):
+    """J (joint.py) of every pool row into ``d.S``.  ``parts``: a (3, P) device
+    tensor for log L below, log L above and J."""
+    from . import tpe as T
+    if hist.tids.size:
+        isb, isa = T.split_masks(hist, gamma)
+    else:
+        isb = isa = np.zeros(0, bool)
+    _J.score_device(eng, domain, hist, _seen_rows(eng, hist), isb, isa, d.vals, d.vals.shape[1],
+                    len(pool.labels), len(pool), d.S, prior_weight, lf, jkw["bandwidth"],
+                    jkw["cat_smoothing"], parts)
+    if parts is not None:  # (row 2: J itself, before the fold adds to S)
+        parts[2, :len(pool)].copy_(d.S[:len(pool)])
+
+
+def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None,
+                  joint=None, parts=None):
     """S of every pool row into the pool's device buffer ``S`` (and the
-    per-label terms into ``terms``); returns (engine, device pool)."""
+    per-label terms into ``terms``); returns (engine, device pool).  ``joint``:
+    None, or the joint criterion's keywords (``bandwidth``, ``cat_smoothing``)
+    -- S starts from J and the fold adds the other labels' terms."""
     if isinstance(pool, GridPool):
+        if joint is not None:
+            raise ValueError(GRID_JOINT)
         return _score_grid(domain, trials, pool, prior_weight, gamma, lf, False, hist)[:2]
     if list(domain.params) != pool.labels:
         raise ValueError("the pool was built for another space (labels differ)")
-    eng, obs = _history_inputs(domain, trials, gamma, hist)
+    if joint is not None:
+        from . import tpe as T
+        # (ValueError on a space without a joint label)
+        jcols = [m.col for m in _J.label_models(domain)]
+        if hist is None:
+            hist = T.collect_history(trials, pool.labels)
+        rest = [j for j in range(len(pool.labels)) if pool.n_active[j] and j not in jcols]
+        # (a flat space has no other label: no observation inputs, no fold)
+        eng, obs = _history_inputs(domain, trials, gamma, hist) if rest else (T.engine(), None)
+    else:
+        eng, obs = _history_inputs(domain, trials, gamma, hist)
     d = pool.device(eng)
     t, lib = eng.torch, eng.lib
     P = len(pool)
@@ -898,7 +939,13 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
     todo = [j for j in range(len(pool.labels)) if pool.n_active[j]]
     per = max(1, CHUNK_ELEMS // P)
     init = 1
-    for c0 in range(0, max(len(todo), 1), per):
+    if joint is not None:
+        _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, joint, hist, parts)
+        todo, init = rest, 0
+        if want_terms:  # the joint labels have no term of their own
+            for j in jcols:
+                d.terms[j].fill_(float("nan"))
+    for c0 in range(0, len(todo) if joint is not None else max(len(todo), 1), per):
         js = todo[c0:c0 + per]
         off = np.zeros(max(len(js), 1), np.int64)
         d_bl = d_al = None
@@ -1038,8 +1085,19 @@ def _topk_device(eng, d, P, k, taken=None):
     return d.rows_out[:n].cpu().numpy()
 
 
+def _joint_kw(joint, bandwidth, cat_smoothing):
+    """``_score_device``'s ``joint``: None, or the criterion's keywords."""
+    if not joint:
+        return None
+    if not bandwidth > 0.0 or not cat_smoothing >= 0.0:
+        raise ValueError("bandwidth=%r must be > 0, cat_smoothing=%r >= 0"
+                         % (bandwidth, cat_smoothing))
+    return dict(bandwidth=float(bandwidth), cat_smoothing=float(cat_smoothing))
+
+
 def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
-                  return_terms=False):
+                  return_terms=False, joint=False, bandwidth=_J.BANDWIDTH,
+                  cat_smoothing=_J.CAT_SMOOTHING):
     """S (module doc) of every pool row as an fp64 (P,) array; with
     ``return_terms`` also the (P, L) matrix of per-label terms log l - log g,
     NaN where the label is inactive.  Exact fp64 scoring, whatever the pool
@@ -1048,20 +1106,39 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
 
     For a ``GridPool`` the terms are per axis value, not per row:
     ``return_terms`` gives {label: (V_l,) array of T_l}, all NaN for a label
-    live in no block."""
+    live in no block.
+
+    ``joint=True``: the joint criterion of ``hyperopt_amd.joint`` -- one
+    Parzen mixture over all the labels live in every configuration, J = log
+    L_below - log L_above, with ``bandwidth`` and ``cat_smoothing`` -- in
+    place of those labels' terms: S[r] starts from J[r] and the terms of the
+    row's other live labels (those under a ``switch``) are added in
+    ``domain.params`` order; on a flat space S = J.  ``return_terms`` then
+    gives (S, terms, J), ``terms`` NaN in the joint labels' columns.  A
+    ``GridPool`` raises ValueError (J is not separable over axes:
+    ``GridPool.to_pool()``), and so does a space without a joint label."""
     domain = as_domain(domain)
+    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
     if isinstance(pool, GridPool):
+        if jkw is not None:
+            raise ValueError(GRID_JOINT)
         eng, d, terms = _score_grid(domain, trials, pool, prior_weight, gamma,
                                     linear_forgetting, return_terms)
         S = d.S[:len(pool)].cpu().numpy()
         return (S, terms) if return_terms else S
-    eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
-                           return_terms)
     P = len(pool)
+    parts = None
+    if jkw is not None and return_terms:  # (J is read before the fold adds to it)
+        from . import tpe as T
+        eng = T.engine()
+        parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
+    eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
+                           return_terms, joint=jkw, parts=parts)
     S = d.S[:P].cpu().numpy()
     if not return_terms:
         return S
-    return S, np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
+    terms = np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
+    return (S, terms) if parts is None else (S, terms, parts[2, :P].cpu().numpy())
 
 
 def startup_rows(pool, seed, k, stale=None):
@@ -1085,7 +1162,8 @@ def startup_rows(pool, seed, k, stale=None):
 
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0,
                       n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True,
-                      distinct=False):
+                      distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
+                      cat_smoothing=_J.CAT_SMOOTHING):
     """An ``algo`` for fmin (``partial(tpe.suggest_from_pool, pool=pool)``): one
     document per id, the first id the best untaken row of ``pool`` by
     ``score_configs``, the second the next best, and so on -- larger S first,
@@ -1103,12 +1181,19 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     gives one configuration twice and never one that ``trials`` already has.
     Fewer fresh untaken rows than ids: that many documents; none: ``[]``.  A
     taken row still counts as the first of its class.  A ``GridPool`` raises
-    ValueError: its rows are distinct by construction."""
+    ValueError: its rows are distinct by construction.
+
+    ``joint=True`` ranks by ``score_configs(joint=True, bandwidth=...,
+    cat_smoothing=...)``: the same selection, ``distinct`` and startup rules,
+    other scores.  A ``GridPool`` raises ValueError."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
+    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
+    if jkw is not None and isinstance(pool, GridPool):
+        raise ValueError(GRID_JOINT)
     t0 = time.time()
     domain = as_domain(domain)
     if list(domain.params) != pool.labels:
@@ -1127,7 +1212,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
         rows = startup_rows(pool, seed, k, stale)
     else:
         eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
-                               False, hist=hist)
+                               False, hist=hist, joint=jkw)
         if distinct:
             _distinct_device(eng, pool, d, hist)
         rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
@@ -1189,7 +1274,8 @@ def take_rows(pool, rows_dev, k):
 
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
-                    verbose=True, distinct=False):
+                    verbose=True, distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
+                    cat_smoothing=_J.CAT_SMOOTHING):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -1222,11 +1308,20 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     startup phase the ``n_EI_candidates`` prior rows go through the same pass
     and the ids get the first fresh (kept) rows in row order.  Under
     torch.distributed every rank samples and scores the same pool and returns
-    the same documents."""
+    the same documents.
+
+    ``joint=True``: the pool is sampled as above -- from the factorised
+    posteriors' streams, ``Pool.sample`` unchanged -- and its rows are ranked
+    by ``score_configs(joint=True, ...)`` on that pool in place of the born S.
+    This re-ranks candidates of the factorised l; it does not draw from the
+    joint l.  The startup phase is unchanged."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
     domain = as_domain(domain)
+    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
+    if jkw is not None:
+        _J.label_models(domain)  # (ValueError on a space without a joint label)
     labels = list(domain.params)
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)
@@ -1256,6 +1351,9 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     if k == 0:
         return []
     eng = T.engine()
+    if jkw is not None:  # S: the joint criterion in place of the born scores
+        _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
+                      hist=hist, joint=jkw)
     d = _mirror(pool, eng)
     if distinct:
         _distinct_device(eng, pool, d, hist)

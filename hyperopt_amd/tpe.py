@@ -31,7 +31,9 @@ product of per-label axes, scored without building its rows; ``Pool.sample``
 / ``suggest_sampled`` is the pool of a free space, its rows drawn from the
 posterior and ranked without leaving the device; ``distinct_rows`` /
 ``distinct=True`` keep to the first row of every configuration that the
-history does not hold yet.
+history does not hold yet.  ``joint=True`` ranks a pool's rows by one Parzen
+mixture over whole configurations instead of a sum over labels
+(hyperopt_amd/joint.py; ``joint_labels``, ``joint_score_numpy``).
 """
 from __future__ import annotations
 
@@ -786,3 +788,4 @@ def _suggest_many(requests, shard_studies=False):
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, score_configs,  # noqa: E402,F401
                    suggest_from_pool, suggest_sampled)
+from .joint import joint_labels, score_numpy as joint_score_numpy  # noqa: E402,F401

@@ -786,6 +786,77 @@ int tpe_grid_fold(const double* bl, const double* al, const int64_t* host_off,
                   const int64_t* host_radix, int n_labels, int64_t row_begin, int64_t n_rows,
                   double* S_out, void* stream);
 
+/* ---- a joint (multivariate) Parzen criterion over a pool's rows --------------
+ * (tpe.score_configs(joint=True); the model: hyperopt_amd/joint.py.)  One set
+ * -- below or above -- is a mixture of n + 1 product kernels over the D joint
+ * labels, one per trial of the set in row order and the prior last:
+ *   a_i      = log w_i + sum_d log k_{d,i}(c_d)   (d in list order, from log w_i)
+ *   log L(c) = m + log sum_i exp(a_i - m),  m = max_i a_i   (-inf when m is).
+ * A label's factor, with t(x) = log(max(x, 1e-12)) for TPE_JOINT_LOG and x
+ * otherwise, sigma the set's bandwidth for a trial component and prior_sigma
+ * for the prior, Phi the device's normal_cdf and Z = Phi(hi) - Phi(lo) for
+ * TPE_JOINT_BOUNDED (else 1):
+ *   TPE_JOINT_CONT   -u^2 - log(sigma sqrt(2 pi)) - log Z,
+ *                    u = (t(x) - mu) * (1 / (sqrt(2) sigma))
+ *   TPE_JOINT_QUANT  log(Phi(t(x + q/2)) - Phi(t(x - q/2))) - log Z, the edges
+ *                    clipped to [lo, hi] when bounded; otherwise a lower edge
+ *                    <= 0 of a log label gives Phi = 0; a mass <= 0: -inf
+ *   TPE_JOINT_CAT    tables[tab_off + x] where x equals the component's
+ *                    category, tables[tab_off + n_cat + x] where not, and
+ *                    tables[tab_off + 2 n_cat + x] for the prior component.
+ *
+ * A prepared set is tpe_joint_set_doubles(D, n) doubles on the device (-1: bad
+ * arguments), 16-byte aligned.  The caller writes its head: log w (n + 1),
+ * then the D bandwidths sigma, then the D values 1 / (sqrt(2) sigma).
+ * tpe_joint_prep writes the rest from a label-major history (hist_vals /
+ * hist_active, leading dimension hist_ld, hist_cols columns; a DeviceHistory's):
+ * component i < n is history row rows[i] (device int32), or row i when rows
+ * is NULL; per label its mu -- t(value - shift), the category for a discrete
+ * label -- and the constant of the factor above.  The labels are given twice:
+ * host_labels is read before the call returns (checks), labels is the same
+ * array on the device.
+ *
+ * tpe_joint_score: out[i] = log L(row row_begin + i) - (sub ? sub[i] : 0) for
+ * i in [0, n_rows), rows of a label-major pool (vals, ld, n_cols columns; label
+ * d's column is labels[d].col).  The components are scored in chunks of
+ * TPE_JOINT_CHUNK (one partial (m, s) per row and chunk in `scratch`,
+ * tpe_joint_scratch_bytes(n_rows, n) bytes, 16-byte aligned) and merged in
+ * chunk order.  A row's bits depend on the row, the set and that constant
+ * alone: not on the grid, the row window or block scheduling; no
+ * floating-point atomics.  Limits: D <= TPE_COND_MAX_LABELS, n_cat <=
+ * TPE_JOINT_MAX_CAT, else TPE_E_UNSUPPORTED; bad arguments return TPE_E_ARG
+ * before any launch.  Asynchronous on `stream`, no allocation. */
+#define TPE_JOINT_CHUNK 256
+#define TPE_JOINT_MAX_CAT 65536
+enum { TPE_JOINT_CONT = 0, TPE_JOINT_QUANT = 1, TPE_JOINT_CAT = 2 };
+enum { TPE_JOINT_LOG = 1, TPE_JOINT_BOUNDED = 2 };
+typedef struct tpe_joint_label {
+  int32_t kind;         /* TPE_JOINT_CONT / QUANT / CAT                        */
+  int32_t flags;        /* TPE_JOINT_LOG | TPE_JOINT_BOUNDED                   */
+  int32_t col;          /* the label's column in the pool and in the history   */
+  int32_t n_cat;        /* CAT: number of options                              */
+  double lo, hi;        /* BOUNDED: the bounds in the fit coordinate           */
+  double q;             /* QUANT: the step                                     */
+  double prior_mu, prior_sigma;
+  double prior_r;       /* 1 / (sqrt(2) prior_sigma)                           */
+  double shift;         /* subtracted from a history value (randint's low)     */
+  int64_t tab_off;      /* CAT: its 3 n_cat entries of `tables`                */
+} tpe_joint_label;
+int64_t tpe_joint_set_doubles(int n_labels, int64_t n);
+int64_t tpe_joint_scratch_bytes(int64_t n_rows, int64_t n);
+int tpe_joint_prep(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                   int n_labels, const double* hist_vals, const uint8_t* hist_active,
+                   int64_t hist_ld, int hist_cols, const int32_t* rows, int64_t n, double* set,
+                   void* stream);
+int tpe_joint_score(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                    int n_labels, const double* tables, int64_t n_tables, const double* set,
+                    int64_t n, const double* vals, int64_t ld, int n_cols, int64_t row_begin,
+                    int64_t n_rows, const double* sub, double* out, void* scratch, void* stream);
+/* host: TPE_JOINT_CHUNK as the library was built */
+int tpe_joint_chunk(void);
+/* host: writes sizeof(tpe_joint_label) to out[0..n); returns 1 */
+int tpe_joint_struct_sizes(int32_t* out, int n);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
