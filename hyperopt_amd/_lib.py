@@ -176,6 +176,9 @@ _SIGNATURES = {
                              _P, _P]),
     "tpe_joint_chunk": (_I, []),
     "tpe_joint_struct_sizes": (_I, [_P, _I]),
+    "tpe_joint_sample": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _P, ctypes.c_double, _I64, _I64,
+                              _P, _I64, _I, _P, _P]),
+    "tpe_joint_sample_stage": (_I, []),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),

@@ -26,7 +26,7 @@
 // A row's bits depend on the row, the set and kJChunk / kJPer only: a thread
 // owns its row alone, every sum has a fixed order, there are no atomics, and
 // the row window only moves the row to another thread.
-#include "tpe_common.hpp"
+#include "tpe_joint.hpp"
 
 namespace tpe {
 namespace {
@@ -40,20 +40,7 @@ constexpr int kJMaxD = TPE_COND_MAX_LABELS;
 constexpr double kNegInf = -INFINITY;
 static_assert(kJChunk % kJPer == 0, "a chunk is whole passes");
 
-struct JComp {  // one (label, component) entry of a prepared set
-  double mu, cst;
-};
-
-// the set buffer: log w (C) | the trial components' sigma (D) | their
-// 1 / (sqrt(2) sigma) (D) | pad to an even count | JComp (D x C, label-major)
-__host__ __device__ inline int64_t set_comp_off(int n_labels, int64_t C) {
-  return (C + 2 * (int64_t)n_labels + 1) & ~(int64_t)1;
-}
-
-// the fit coordinate of a stored value
-__device__ __forceinline__ double fit_coord(double v, bool is_log) {
-  return is_log ? log(fmax(v, kEps)) : v;
-}
+// (JComp, set_comp_off and fit_coord: tpe_joint.hpp)
 
 // log of a component's mass of [tl, tu], -inf when it has none.  Not inlined:
 // the erf and log bodies bring some forty fp64 constants that the compiler
@@ -225,8 +212,10 @@ __global__ __launch_bounds__(kJBS) void k_joint_merge(const double2* __restrict_
 }
 
 inline int64_t joint_chunks(int64_t n) { return (n + 1 + kJChunk - 1) / kJChunk; }
+}  // namespace
 
-// TPE_OK, or the error set: the labels' kinds and limits
+// TPE_OK, or the error set: the labels' kinds and limits (shared with the
+// sampler: tpe_joint.hpp)
 int check_joint_labels(const char* fn, const tpe_joint_label* hl, int n_labels, int n_cols,
                        int64_t n_tables) {
   if (n_labels <= 0 || !hl) {
@@ -257,7 +246,6 @@ int check_joint_labels(const char* fn, const tpe_joint_label* hl, int n_labels, 
   }
   return TPE_OK;
 }
-}  // namespace
 }  // namespace tpe
 
 using namespace tpe;

@@ -53,6 +53,38 @@ m = max a_i, summed in component order; m = -inf gives -inf.  NaN
 ``score_numpy`` is this definition in vectorised numpy, for CPU-only users and
 for checking; the device path (csrc/tpe_joint.hip, driven by pool.py) builds
 the components from the HBM-resident history and scores the pool there.
+
+Drawing (``Pool.sample(joint=True)``, csrc/tpe_joint_sample.hip).
+Row g of a joint-drawn pool is one draw from the below set's mixture above:
+components 0 .. n - 1 its trials in ascending row order, component n the
+prior.  Philox counters are {g lo, g hi, attempt, stream} as everywhere
+(oracle/streams.py), the stream word ``STREAM_JOINT`` = 0x4A4F494E ("JOIN"),
+distinct from SAMP / RETR / PRIO / ANNL.
+
+  component    key ``component_key(seed)`` = ``_mix64(_mix64(_seed_word(seed)) ^
+               STREAM_JOINT)`` (tpe.py's mixing functions; a function of the
+               seed alone, no label's hash enters), call (g, 0): word x picks
+               the first i with ``cdf[i] > x 2^-32 cdf[-1]``
+               (``streams.component_cdf``), ``cdf = sample_cdf(n, lf,
+               prior_weight)`` = cumsum of the ramp and the prior's weight.
+  label d      key ``tpe.label_key(seed, label_d)``, attempts a = 0, 1, ... at
+               (g, a).
+    continuous, quantized   ``t = mu + sigma normal_f64(y, z, w)`` with the
+               component's (mu, sigma) -- the trial's mu_i and the set's
+               bandwidth, or (mu_p, sigma_p).  A bounded kind accepts lo <= t
+               < hi; after 256 rejections the last t is clamped to lo or to
+               nextafter(hi, -inf) (``draw64``'s rule).  x = exp(t) for the
+               log kinds, else t; a quantized label stores rint(x / q) q.
+               This is the distribution whose density or mass the factor
+               table above states (for a log kind in t: the Jacobian left out
+               there belongs to the density in x).
+    categorical, randint   attempt 0 only.  A trial component of category c_i
+               keeps c_i when ``x 2^-32 (1 + a) < 1``, else takes
+               ``categorical_of_word(cumsum(p), y)``; the prior component
+               ``categorical_of_word(cumsum(p), x)``.  The stored value is
+               the category index (randint(low, high) without ``low``).
+
+A row's values are a function of (seed, g, the set, the label list) alone.
 """
 from __future__ import annotations
 
@@ -69,6 +101,7 @@ from .walk import int_offset
 BANDWIDTH = 0.2
 CAT_SMOOTHING = 1.0
 ROWS_PER_CALL = 1 << 14  # pool rows per tpe_joint_score call: bounds its scratch
+STREAM_JOINT = 0x4A4F494E  # "JOIN": the Philox stream word of the joint draws
 
 _erf = np.vectorize(math.erf, otypes=[np.float64])
 
@@ -88,6 +121,20 @@ def forgetting_weights(n, lf):
     if n < lf:
         return np.ones(n)
     return np.concatenate([np.linspace(1.0 / n, 1.0, num=n - lf), np.ones(lf)])
+
+
+def component_key(seed):
+    """The 64-bit Philox key of the joint draws' component pick (module doc):
+    the suggest seed's word mixed once more, xor the stream word, through the
+    splitmix finaliser.  No label enters it."""
+    from . import tpe as T
+    return T._mix64(T._mix64(T._seed_word(seed)) ^ STREAM_JOINT)
+
+
+def sample_cdf(n, lf, prior_weight):
+    """The running sum of a set's n + 1 component weights, the prior last:
+    what the component pick searches."""
+    return np.cumsum(np.concatenate([forgetting_weights(n, lf), [float(prior_weight)]]))
 
 
 def log_weights(n, lf, prior_weight):
@@ -301,13 +348,13 @@ def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp
     return dset, n, drows
 
 
-def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, prior_weight,
-                 linear_forgetting, bandwidth, cat_smoothing, parts=None):
-    """J of rows [0, P) of the label-major device pool ``d_vals`` (leading
-    dimension ``ld``, ``n_cols`` columns) into the device vector ``out``.
-    ``seen``: ``pool._seen_rows(eng, hist)``; ``parts``: a device tensor whose
-    rows 0 and 1 (>= P long) receive log L_below and log L_above."""
-    t, lib = eng.torch, eng.lib
+def prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight, linear_forgetting,
+                 bandwidth, cat_smoothing):
+    """The space's label records and both sets on the device: (dj, [below,
+    above], stream pointer), a set as ``_prepare_set`` returns it.  ``seen``:
+    ``pool._seen_rows(eng, hist)``; ``n_cols``: the columns of the history
+    (and of the pool: both are in ``domain.params`` order)."""
+    t = eng.torch
     models = label_models(domain)
     dj = _device_labels(eng, models, cat_smoothing)
     sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
@@ -318,10 +365,25 @@ def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, 
         rows = set_rows(hist, mask, cols)
         if view is not None:
             rows = np.asarray(view)[rows]
-        # (the history has the pool's columns: both are in domain.params order)
         sets.append(_prepare_set(eng, dj, seen, n_cols, rows, linear_forgetting, prior_weight,
                                  bandwidth, sp))
-    D = len(models)
+    return dj, sets, sp
+
+
+def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, prior_weight,
+                 linear_forgetting, bandwidth, cat_smoothing, parts=None, prepared=None):
+    """J of rows [0, P) of the label-major device pool ``d_vals`` (leading
+    dimension ``ld``, ``n_cols`` columns) into the device vector ``out``.
+    ``seen``: ``pool._seen_rows(eng, hist)``; ``parts``: a device tensor whose
+    rows 0 and 1 (>= P long) receive log L_below and log L_above;
+    ``prepared``: ``prepare_sets``' result for the same arguments, where the
+    caller has made it already."""
+    t, lib = eng.torch, eng.lib
+    if prepared is None:
+        prepared = prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
+                                linear_forgetting, bandwidth, cat_smoothing)
+    dj, sets, sp = prepared
+    D = len(dj.models)
     tab = None if dj.tables is None else dj.tables.data_ptr()
     win = min(max(P, 1), ROWS_PER_CALL)
     need = max(lib.tpe_joint_scratch_bytes(win, n) for _, n, _ in sets)
@@ -345,3 +407,31 @@ def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, 
             # call without ``parts`` because it is made by the same call
             score(0, r0, k, None, parts[0].data_ptr() + 8 * r0)
         score(0, r0, k, la, out.data_ptr() + 8 * r0)
+
+
+def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals, ld,
+                  n_cols, row_base, n_rows, comp_out=None):
+    """Rows [row_base, row_base + n_rows) of the joint draw (module doc) from
+    the below set of ``prepared`` (``prepare_sets``) into rows [0, n_rows) of
+    the joint labels' columns of the label-major device block ``d_vals``
+    (tpe_joint_sample).  ``comp_out``: a device int32 tensor for the rows'
+    components.  Three small uploads: the component cdf, the discrete labels'
+    cdf table and the keys."""
+    from . import tpe as T
+    t, lib = eng.torch, eng.lib
+    dj, sets, sp = prepared
+    dset, n, _ = sets[0]
+    cdf = t.from_numpy(sample_cdf(n, linear_forgetting, prior_weight)).to(eng.device)
+    cats = [np.cumsum(m.p) for m in dj.models if m.kind == _L.JOINT_CAT]
+    cat_cdf = t.from_numpy(np.concatenate(cats)).to(eng.device) if cats else None
+    keys = np.asarray([T.label_key(seed, m.label) for m in dj.models] + [component_key(seed)],
+                      np.uint64)
+    d_keys = t.from_numpy(keys.view(np.int64)).to(eng.device)
+    _L.check(lib.tpe_joint_sample(dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
+                                  dset.data_ptr(), n, cdf.data_ptr(),
+                                  None if cat_cdf is None else cat_cdf.data_ptr(),
+                                  0 if cat_cdf is None else cat_cdf.numel(), d_keys.data_ptr(),
+                                  1.0 + float(cat_smoothing), row_base, n_rows,
+                                  d_vals.data_ptr(), ld, n_cols,
+                                  None if comp_out is None else comp_out.data_ptr(), sp),
+             "tpe_joint_sample")

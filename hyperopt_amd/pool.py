@@ -50,6 +50,10 @@ replaces the sum over the always-live labels by one Parzen mixture over whole
 configurations, J = log L_below - log L_above (joint.py; csrc/tpe_joint.hip
 builds both sets from the resident history and scores the rows); the fold
 adds the terms of the labels under a ``switch`` onto J.
+``Pool.sample(joint=True)`` / ``suggest_sampled(joint=True, draw="joint")``
+also draw the always-live labels of every row from the below set's joint
+mixture (csrc/tpe_joint_sample.hip), so the candidates themselves follow an
+interaction between labels.
 """
 from __future__ import annotations
 
@@ -288,7 +292,8 @@ class Pool(object):
 
     @classmethod
     def sample(cls, domain, trials, seed, n_rows, prior_weight=1.0, gamma=0.25,
-               linear_forgetting=25, keep_terms=False):
+               linear_forgetting=25, keep_terms=False, joint=False, bandwidth=_J.BANDWIDTH,
+               cat_smoothing=_J.CAT_SMOOTHING):
         """``tpe.Pool.sample(domain, trials, seed, n_rows, ...)``: the pool whose
         row r holds candidate r of every label's posterior stream (below
         posterior l; key ``label_key(seed, label)``, candidates [0, n_rows)), every
@@ -303,9 +308,20 @@ class Pool(object):
         every configuration; ``suggest_sampled(distinct=True)`` suggests only
         those).  A born S and a later ``score_configs`` of the same rows under the
         same history may differ in their last bits: a log-domain label is scored
-        at its drawn log coordinate when born, at log(exp(z)) when injected."""
+        at its drawn log coordinate when born, at log(exp(z)) when injected.
+
+        ``joint=True``: the joint labels (``tpe.joint_labels``: live in every
+        configuration) of row r are one draw from the below set's joint
+        mixture (joint.py, "Drawing"; ``bandwidth``, ``cat_smoothing``), made
+        on the device by ``tpe_joint_sample``; a space without such a label
+        raises ValueError.  The labels under a ``switch`` are drawn and scored
+        as above, with the same keys and values.  The pool is born with the
+        joint criterion's S: J of the drawn rows, then the fold of the live
+        non-joint labels' own terms onto it -- ``score_configs(joint=True)`` of
+        the same pool (bit for bit on a flat space).  ``keep_terms`` leaves NaN
+        in the joint labels' columns."""
         return _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting,
-                       keep_terms)
+                       keep_terms, joint=_joint_kw(joint, bandwidth, cat_smoothing))
 
     def _setup(self, domain, labels, vals, active):
         _validate(domain, labels, vals, active)
@@ -499,17 +515,27 @@ def _rows_active(eng, domain, labels, d, P, sp):
 
 
 def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting, keep_terms,
-            hist=None):
-    """``Pool.sample``."""
+            hist=None, joint=None):
+    """``Pool.sample``.  ``joint``: None, or the joint criterion's keywords
+    (``_joint_kw``): the joint labels come from ``tpe_joint_sample`` and S
+    starts from J."""
     from . import tpe as T
     domain = as_domain(domain)
     labels = list(domain.params)
     P, L = int(n_rows), len(labels)
     if P < 0:
         raise ValueError("n_rows=%d" % P)
+    jcols = []
+    if joint is not None:  # (ValueError on a space without a joint label)
+        jcols = [m.col for m in _J.label_models(domain)]
     if P == 0:
         return Pool.from_arrays(domain, np.zeros((0, L)), np.zeros((0, L), bool))
-    eng, obs = _history_inputs(domain, trials, gamma, hist)
+    if joint is not None and hist is None:
+        hist = T.collect_history(trials, labels)
+    if joint is not None and len(jcols) == L:
+        eng, obs = T.engine(), None  # (a flat space: no label is left to the engine)
+    else:
+        eng, obs = _history_inputs(domain, trials, gamma, hist)
     t, lib = eng.torch, eng.lib
     d = _DevicePool()
     d.vals = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device)
@@ -537,16 +563,38 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
             d.vals[j].copy_(xbuf[int(o):int(o) + P])
         return off
 
-    chunks = [list(range(c0, min(L, c0 + per))) for c0 in range(0, L, per)]
+    todo = [j for j in range(L) if j not in jcols]
+    chunks = [todo[c0:c0 + per] for c0 in range(0, len(todo), per)]
     n_active = None
+    prepared = None
+    if joint is not None:
+        # the joint labels' columns: one draw per row from the below set's mixture
+        isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+        prepared = _J.prepare_sets(eng, domain, hist, _seen_rows(eng, hist), isb, isa, L,
+                                   prior_weight, linear_forgetting, joint["bandwidth"],
+                                   joint["cat_smoothing"])
+        _J.sample_device(eng, prepared, seed, prior_weight, linear_forgetting,
+                         joint["cat_smoothing"], d.vals, P, L, 0, P)
     if len(chunks) > 1:
         # the fold runs in label order and needs every row's activity: the
         # selectors' columns first (their draws do not depend on the chunking)
         sel = [labels.index(lab) for lab in _selectors(domain, labels)]
+        sel = [j for j in sel if j not in jcols]
         for c0 in range(0, len(sel), per):
             draw(sel[c0:c0 + per])
         n_active = _rows_active(eng, domain, labels, d, P, sp)
     init = 1
+    if joint is not None:
+        if not chunks:
+            n_active = _rows_active(eng, domain, labels, d, P, sp)
+        # S starts from J of the drawn rows; the fold below adds the other labels
+        _J.score_device(eng, domain, hist, None, None, None, d.vals, P, L, P, d.S, prior_weight,
+                        linear_forgetting, joint["bandwidth"], joint["cat_smoothing"],
+                        prepared=prepared)
+        init = 0
+        if keep_terms:  # the joint labels have no term of their own
+            for j in jcols:
+                d.terms[j].fill_(float("nan"))
     for js in chunks:
         off = draw(js)
         if n_active is None:
@@ -558,7 +606,7 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
                                    d.terms.data_ptr() if keep_terms else None, P, sp),
                  "tpe_pool_fold")
         init = 0
-    if not chunks:  # a space without labels: S = 0
+    if not chunks and joint is None:  # a space without labels: S = 0
         n_active = t.zeros(1, dtype=t.int64, device=eng.device)
         _L.check(lib.tpe_pool_fold(None, None, None, None, 0, None, P, P, 1, d.S.data_ptr(), None,
                                    P, sp), "tpe_pool_fold")
@@ -1275,7 +1323,7 @@ def take_rows(pool, rows_dev, k):
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
                     verbose=True, distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
-                    cat_smoothing=_J.CAT_SMOOTHING):
+                    cat_smoothing=_J.CAT_SMOOTHING, draw="factorised"):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -1310,14 +1358,25 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     torch.distributed every rank samples and scores the same pool and returns
     the same documents.
 
-    ``joint=True``: the pool is sampled as above -- from the factorised
-    posteriors' streams, ``Pool.sample`` unchanged -- and its rows are ranked
-    by ``score_configs(joint=True, ...)`` on that pool in place of the born S.
-    This re-ranks candidates of the factorised l; it does not draw from the
-    joint l.  The startup phase is unchanged."""
+    ``joint=True``: the pool's rows are ranked by the joint criterion
+    (``score_configs(joint=True, ...)``) in place of the factorised S.  Where
+    the rows come from is ``draw``'s choice.  ``draw="factorised"`` (the
+    default) samples the pool as above -- from the factorised posteriors'
+    streams, ``Pool.sample`` unchanged -- and re-ranks it: candidates of the
+    factorised l under the joint score.  ``draw="joint"`` (needs
+    ``joint=True``; ValueError otherwise, as for any other string) samples it
+    with ``Pool.sample(joint=True)``: the always-live labels of every row are
+    one draw from the joint l, and the pool is ranked by the S it is born
+    with.  ``keep``, ``distinct``, the k-documents rule and the startup phase
+    are the same for both."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
+    if draw not in ("factorised", "joint"):
+        raise ValueError("draw=%r: 'factorised' or 'joint'" % (draw,))
+    if draw == "joint" and not joint:
+        raise ValueError("draw='joint' draws from the joint criterion's below mixture: it needs "
+                         "joint=True")
     domain = as_domain(domain)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
     if jkw is not None:
@@ -1344,14 +1403,14 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         configs = [_stored_config(domain, labels, vals[r], active[r]) for r in rows]
         return trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
     pool = _sample(domain, trials, seed, n, prior_weight, gamma, linear_forgetting, False,
-                   hist=hist)
+                   hist=hist, joint=jkw if draw == "joint" else None)
     if keep is not None and len(pool):
         pool.mark_taken(np.flatnonzero(~_keep_rows(keep, labels, pool.vals, len(pool))))
     k = min(len(new_ids), pool.n_untaken)
     if k == 0:
         return []
     eng = T.engine()
-    if jkw is not None:  # S: the joint criterion in place of the born scores
+    if jkw is not None and draw != "joint":  # S: the joint criterion in place of the born scores
         _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
                       hist=hist, joint=jkw)
     d = _mirror(pool, eng)

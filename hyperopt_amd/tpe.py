@@ -33,7 +33,10 @@ posterior and ranked without leaving the device; ``distinct_rows`` /
 ``distinct=True`` keep to the first row of every configuration that the
 history does not hold yet.  ``joint=True`` ranks a pool's rows by one Parzen
 mixture over whole configurations instead of a sum over labels
-(hyperopt_amd/joint.py; ``joint_labels``, ``joint_score_numpy``).
+(hyperopt_amd/joint.py; ``joint_labels``, ``joint_score_numpy``);
+``Pool.sample(joint=True)`` / ``suggest_sampled(joint=True, draw="joint")``
+also draw the rows from that mixture (``joint_component_key``: the key of the
+draws' component pick).
 """
 from __future__ import annotations
 
@@ -788,4 +791,5 @@ def _suggest_many(requests, shard_studies=False):
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, score_configs,  # noqa: E402,F401
                    suggest_from_pool, suggest_sampled)
-from .joint import joint_labels, score_numpy as joint_score_numpy  # noqa: E402,F401
+from .joint import (component_key as joint_component_key, joint_labels,  # noqa: E402,F401
+                    score_numpy as joint_score_numpy)

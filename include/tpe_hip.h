@@ -857,6 +857,51 @@ int tpe_joint_chunk(void);
 /* host: writes sizeof(tpe_joint_label) to out[0..n); returns 1 */
 int tpe_joint_struct_sizes(int32_t* out, int n);
 
+/* ---- rows drawn from a set's joint mixture (tpe.Pool.sample(joint=True)) -----
+ * tpe_joint_sample: row g = row_base + r, r in [0, n_rows), is one draw from the
+ * mixture of a prepared set (above: n trial components in row order, the prior
+ * last), written to vals[labels[d].col * ld + r] for every label d -- a
+ * label-major block of n_cols columns whose row 0 is row row_base.  Philox
+ * counters are {g lo, g hi, attempt, 0x4A4F494E "JOIN"}; keys (device) holds
+ * the D label keys, then the component key.
+ *   component   key keys[D], call (g, 0): word x picks the first i with
+ *               cdf[i] > x 2^-32 cdf[n] -- cdf: n + 1 doubles on the device, the
+ *               running sum of the components' weights, the prior's last.
+ *   TPE_JOINT_CONT / QUANT   key keys[d], attempts a = 0, 1, ... at (g, a):
+ *               t = mu + sigma z, z the Box-Muller normal of words y, z, w;
+ *               (mu, sigma) the component's (the set's mu and bandwidth of
+ *               label d, or prior_mu / prior_sigma).  TPE_JOINT_BOUNDED accepts
+ *               lo <= t < hi; after 256 rejections the last t is clamped to lo
+ *               or to nextafter(hi, -inf).  x = exp(t) for TPE_JOINT_LOG, else
+ *               t; QUANT stores rint(x / q) q.
+ *   TPE_JOINT_CAT   key keys[d], call (g, 0).  The label's cdf is the n_cat
+ *               doubles at cat_cdf[tab_off / 3] (device; n_cat_cdf doubles in
+ *               all: one n_cat-entry running sum of the prior probabilities
+ *               per discrete label, packed in the order of `tables`, so tab_off
+ *               is a multiple of 3).  A trial component of category c keeps c
+ *               when x 2^-32 one_plus_a < 1 (one_plus_a = 1 + cat_smoothing
+ *               >= 1) and otherwise draws with word y; the prior component
+ *               draws with word x.  A word picks the first k with word <
+ *               ceil(cdf[k] / cdf[n_cat - 1] 2^32) (saturated at 2^32 - 1; the
+ *               word 2^32 - 1 is read as 2^32 - 2), the last k if none.  The
+ *               stored value is the category index.
+ * comp_out (device, nullable): comp_out[r] = the row's component, n for the
+ * prior.  One thread per (row, label), 256 rows per block; the cdf is staged
+ * in LDS up to TPE_JOINT_SAMPLE_STAGE components and searched in global memory
+ * above.  A row's values depend on (keys, g, the set, the labels) alone: not on
+ * the grid, the row window or block scheduling; no atomics.  Limits as above
+ * (TPE_E_UNSUPPORTED); n < 2^31 - 1, n_rows <= ld; bad arguments return
+ * TPE_E_ARG before any launch; n_rows == 0 is a no-op.  Asynchronous on
+ * `stream`, no allocation. */
+#define TPE_JOINT_SAMPLE_STAGE 64
+int tpe_joint_sample(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                     int n_labels, const double* set, int64_t n, const double* cdf,
+                     const double* cat_cdf, int64_t n_cat_cdf, const uint64_t* keys,
+                     double one_plus_a, int64_t row_base, int64_t n_rows, double* vals,
+                     int64_t ld, int n_cols, int32_t* comp_out, void* stream);
+/* host: TPE_JOINT_SAMPLE_STAGE as the library was built */
+int tpe_joint_sample_stage(void);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
