@@ -160,6 +160,7 @@ _SIGNATURES = {
     "tpe_anneal_struct_sizes": (_I, [_P, _I]),
     "tpe_pool_fold": (_I, [_P, _P, _P, _P, _I, _P, _I64, _I64, _I, _P, _P, _I64, _P]),
     "tpe_pool_topk_scratch_bytes": (_I64, [_I64, _I64]),
+    "tpe_pool_topk_layout": (_I, [_I64, _I64, _P, _I]),
     "tpe_pool_topk": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
     "tpe_rows_active": (_I, [_P, _I64, _I64, _I, _P, _P, _P, _I, _P, _P, _P]),
     "tpe_pool_ranges": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P]),

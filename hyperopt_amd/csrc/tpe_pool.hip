@@ -304,6 +304,27 @@ __global__ __launch_bounds__(kPBS) void k_pool_rank(const PoolCtl* __restrict__ 
 
 inline int64_t pool_tiles(int64_t n_rows) { return (n_rows + kPTile - 1) / kPTile; }
 constexpr int64_t kCtlBytes = 64, kHistBytes = 8 * kPBins;
+static_assert(sizeof(PoolCtl) == kCtlBytes, "PoolCtl is the scratch's first 64 bytes");
+
+// byte offsets of a call's scratch: tpe_pool_topk, its size query and
+// tpe_pool_topk_layout all read them here
+struct PoolLayout {
+  int64_t n_tiles, kk;  // tiles of kPTile rows; candidate slots, min(k, n_rows)
+  int64_t ctl, hist, tile, cand_key, cand_row, total;
+};
+
+inline PoolLayout pool_layout(int64_t n_rows, int64_t k) {
+  PoolLayout p;
+  p.n_tiles = pool_tiles(n_rows);
+  p.kk = k < n_rows ? k : n_rows;
+  p.ctl = 0;
+  p.hist = p.ctl + kCtlBytes;
+  p.tile = p.hist + kHistBytes;
+  p.cand_key = p.tile + 16 * p.n_tiles;
+  p.cand_row = p.cand_key + 8 * p.kk;
+  p.total = p.cand_row + 8 * p.kk;
+  return p;
+}
 }  // namespace
 }  // namespace tpe
 
@@ -355,8 +376,20 @@ extern "C" int tpe_pool_fold(const double* bl, const double* al, const int64_t* 
 
 extern "C" int64_t tpe_pool_topk_scratch_bytes(int64_t n_rows, int64_t k) {
   if (n_rows < 0 || k < 0) return -1;
-  const int64_t kk = k < n_rows ? k : n_rows;
-  return kCtlBytes + kHistBytes + 16 * pool_tiles(n_rows) + 16 * kk;
+  return pool_layout(n_rows, k).total;
+}
+
+extern "C" int tpe_pool_topk_layout(int64_t n_rows, int64_t k, int64_t* out, int n) {
+  if (n_rows < 0 || k < 0 || n < 0 || (n > 0 && !out)) {
+    set_error("tpe_pool_topk_layout: n_rows=%lld k=%lld n=%d", (long long)n_rows, (long long)k,
+              n);
+    return -1;
+  }
+  const PoolLayout p = pool_layout(n_rows, k);
+  const int64_t v[7] = {p.ctl, p.hist, p.tile, p.cand_key, p.cand_row, p.total, kPTile};
+  const int m = n < 7 ? n : 7;
+  for (int i = 0; i < m; ++i) out[i] = v[i];
+  return m;
 }
 
 extern "C" int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t n_rows, int64_t k,
@@ -378,18 +411,18 @@ extern "C" int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t 
     set_error("tpe_pool_topk: null pointer");
     return TPE_E_ARG;
   }
-  const int64_t n_tiles = pool_tiles(n_rows);
+  const PoolLayout lay = pool_layout(n_rows, k);
+  const int64_t n_tiles = lay.n_tiles, kk = lay.kk;
   if (n_tiles > 2147483647) {
     set_error("tpe_pool_topk: n_rows=%lld does not fit a launch", (long long)n_rows);
     return TPE_E_ARG;
   }
-  const int64_t kk = k < n_rows ? k : n_rows;
   uint8_t* ws = static_cast<uint8_t*>(scratch);
-  PoolCtl* ctl = reinterpret_cast<PoolCtl*>(ws);
-  unsigned long long* hist = reinterpret_cast<unsigned long long*>(ws + kCtlBytes);
-  int64_t* tile_cnt = reinterpret_cast<int64_t*>(ws + kCtlBytes + kHistBytes);
-  uint64_t* cand_key = reinterpret_cast<uint64_t*>(tile_cnt + 2 * n_tiles);
-  int64_t* cand_row = reinterpret_cast<int64_t*>(cand_key + kk);
+  PoolCtl* ctl = reinterpret_cast<PoolCtl*>(ws + lay.ctl);
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(ws + lay.hist);
+  int64_t* tile_cnt = reinterpret_cast<int64_t*>(ws + lay.tile);
+  uint64_t* cand_key = reinterpret_cast<uint64_t*>(ws + lay.cand_key);
+  int64_t* cand_row = reinterpret_cast<int64_t*>(ws + lay.cand_row);
   const dim3 tiles((unsigned)n_tiles), bs(kPBS);
   hipLaunchKernelGGL(k_pool_init, dim3(1), dim3(kPBins), 0, st, ctl, hist, kk);
   for (int pass = 0; pass < kPPasses; ++pass) {

@@ -680,8 +680,28 @@ int tpe_pool_fold(const double* bl, const double* al, const int64_t* host_off,
  * (a multi-block radix select over the score bits, then a ranking of the
  * selected rows); no floating-point atomics, the result does not depend on
  * block scheduling.  scratch: tpe_pool_topk_scratch_bytes(n_rows, k) bytes
- * (-1: bad arguments). */
+ * (-1: bad arguments).
+ *
+ * tpe_pool_topk_layout (host only, no GPU call): where a call with these
+ * (n_rows, k) keeps its intermediate state in `scratch`, which is still there
+ * when the call has ended.  Writes up to n of these seven numbers to out and
+ * returns how many it wrote (-1: bad arguments): the byte offsets of
+ *   [0] the control block, five 64-bit words: prefix (the key T of the last
+ *       selected row once the eight passes are done), mask (the key bits
+ *       decided so far), k_rem (rows with key == T that are selected), k_eff
+ *       (rows selected: min(k, untaken rows)), n_less (selected rows with
+ *       key < T); three more words pad it to 64 bytes,
+ *   [1] the 256 uint64 radix bins (zero after every pass),
+ *   [2] the tile table, two int64 per tile of out[6] rows: the number of
+ *       untaken rows with key < T and with key == T in the tiles before it,
+ *   [3] cand_key and [4] cand_row, min(k, n_rows) 64-bit slots each: the
+ *       selected rows -- those with key < T in row order, then the first k_rem
+ *       with key == T -- before they are ranked,
+ * then [5] the total, tpe_pool_topk_scratch_bytes(n_rows, k), and [6] the rows
+ * per tile.  key = ~order_key(score): ascending key is rank order, every NaN
+ * has key 1, -0.0 the key of +0.0. */
 int64_t tpe_pool_topk_scratch_bytes(int64_t n_rows, int64_t k);
+int tpe_pool_topk_layout(int64_t n_rows, int64_t k, int64_t* out, int n);
 int tpe_pool_topk(const double* score, const uint8_t* taken, int64_t n_rows, int64_t k,
                   int64_t* out_rows, int64_t* out_count, void* scratch, void* stream);
 
