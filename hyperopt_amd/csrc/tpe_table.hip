@@ -299,7 +299,9 @@ __device__ __forceinline__ bool build_mix(const tpe_seg& S, const double* __rest
   // coop (block-uniform): the block's four waves build the same four cells
   // and split the items; otherwise every wave builds its own four cells
   constexpr int kNW = kBS / kWave;
-  const int wv = coop ? (int)threadIdx.x / kWave : 0;
+  // (the wave's index read as a scalar: what depends on it alone stays out of
+  // the vector registers)
+  const int wv = coop ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave) : 0;
   const int stride = coop ? 16 * kNW : 16;
   const int64_t off = S.comp_off;
   const int nwin = max(0, k_hi - k_lo + 1);
@@ -742,7 +744,9 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(TPE_BUILD_W
     W->nb = g.nb;
     W->slope = 0.0f;  // raised by k_table_score (the next launch)
   }
-  const int wid = threadIdx.x / kWave, row = lane_id() >> 4;
+  // (wid as a scalar: the quad, its cells' numbers and the span's ends are
+  // wave-uniform and stay in scalar registers)
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), row = lane_id() >> 4;
   float* region = cells + J.tbl_off * (kSlotB / 4);
   __shared__ BuildLds X;
   // four consecutive cells (a "quad", one per 16-lane row) per wave; a label

@@ -15,7 +15,7 @@ import bench  # noqa: E402
 from oracle import tpe_oracle as O  # noqa: E402
 
 RHO = 5.8
-TAU = 25.0
+TAU = 17.0  # TPE_TAU_TABLE, the table's exclusion margin
 CAP = 1 << 15
 
 
@@ -63,10 +63,32 @@ def included(S, T, y0, h):
     return np.count_nonzero(S["lc"] - 0.5 * zn * zn >= T)
 
 
+def pairs(B, A, P, ys, hh):
+    """Component-cell pairs the build sums on the cells centred at ``ys``: the
+    components of both mixtures that pass the exclusion test on each cell."""
+    return sum(included(B, P["below"][0], y, hh) + included(A, P["above"][0], y, hh) for y in ys)
+
+
 def main():
     space = bench.c3_space()
     vals, losses = bench.c3_history(space)
     sp = bench.split(vals, losses)
+    total = 0
+    for lab, kind, args in space:
+        if kind not in ("uniform", "loguniform", "normal", "lognormal"):
+            continue
+        below, above = sp[lab]
+        B, A = mixture(kind, args, below), mixture(kind, args, above)
+        a, b, P = plan(B, A)
+        h = min(P["below"][1].min(), P["above"][1].min())
+        nb = min(CAP, max(1, math.ceil((b - a) / (2 * h))))
+        hh = (b - a) / (2 * nb)
+        # every 8th cell, scaled: the count varies slowly from cell to cell
+        ys = a + hh * (2 * np.arange(nb) + 1)
+        n = pairs(B, A, P, ys[::8], hh) * nb / len(ys[::8])
+        total += n
+        print("%-5s %-10s nb %6d  component-cell pairs %.4g" % (lab, kind, nb, n))
+    print("C3: total component-cell pairs of the unquantized labels %.4g" % total)
     for lab in ("u0", "lu0", "n0"):
         kind, args = [(k, a) for l_, k, a in space if l_ == lab][0]
         below, above = sp[lab]
