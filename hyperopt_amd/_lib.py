@@ -73,6 +73,7 @@ JOINT_LABEL_DTYPE = np.dtype([
 JOINT_CONT, JOINT_QUANT, JOINT_CAT = 0, 1, 2
 JOINT_LOG, JOINT_BOUNDED = 1, 2
 JOINT_MAX_CAT = 65536
+JOINT_OUT_SCATTER, JOINT_OUT_ADD = 1, 2  # tpe_joint_score_rows' out_mode
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
 # tpe_run_ops record codes (tpe_hip.h TPE_OP_*): entry point -> code
@@ -180,6 +181,11 @@ _SIGNATURES = {
     "tpe_joint_sample": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _P, ctypes.c_double, _I64, _I64,
                               _P, _I64, _I, _P, _P]),
     "tpe_joint_sample_stage": (_I, []),
+    "tpe_rows_compact_scratch_bytes": (_I64, [_I64]),
+    "tpe_rows_compact_layout": (_I, [_P, _I]),
+    "tpe_rows_compact": (_I, [_P, _I64, _P, _P, _P, _P]),
+    "tpe_joint_score_rows": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64,
+                                  _I64, _P, _P, _I, _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),

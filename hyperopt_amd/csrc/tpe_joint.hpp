@@ -1,6 +1,8 @@
-// tpe_joint.hpp -- what the joint criterion's scorer (tpe_joint.hip) and its
-// sampler (tpe_joint_sample.hip) share: the layout of a prepared set, the fit
-// coordinate and the label checks of the entry points.
+// tpe_joint.hpp -- what the joint criterion's scorer (tpe_joint.hip), its
+// scorer by row list (tpe_joint_tree.hip) and its sampler
+// (tpe_joint_sample.hip) share: the layout of a prepared set, the fit
+// coordinate, the label checks of the entry points and the scorers' constants.
+// (The two scorers' one arithmetic is in tpe_joint_pass.hpp.)
 #pragma once
 
 #include "tpe_common.hpp"
@@ -13,6 +15,24 @@ int check_joint_labels(const char* fn, const tpe_joint_label* hl, int n_labels, 
                        int64_t n_tables);
 
 namespace {
+constexpr int kJBS = 256;                 // threads (rows) per block
+constexpr int kJChunk = TPE_JOINT_CHUNK;  // components per partial
+// components per pass, their a_i in registers: 8 gives 108 VGPRs (4 waves per
+// SIMD), 16 gives 172 (2 waves), 4 gives 91 (5 waves) but half the work per
+// LDS read and barrier
+constexpr int kJPer = 8;
+constexpr int kJMaxD = TPE_COND_MAX_LABELS;
+constexpr double kNegInf = -INFINITY;
+static_assert(kJChunk % kJPer == 0, "a chunk is whole passes");
+
+// log of a component's mass of [tl, tu], -inf when it has none.  Not inlined:
+// the erf and log bodies bring some forty fp64 constants that the compiler
+// otherwise keeps in registers across the whole scoring loop.
+__device__ __noinline__ double log_mass(double tu, double tl, double mu, double sigma) {
+  const double mass = normal_cdf(tu, mu, sigma) - normal_cdf(tl, mu, sigma);
+  return mass > 0.0 ? log(mass) : kNegInf;
+}
+
 struct JComp {  // one (label, component) entry of a prepared set
   double mu, cst;
 };

@@ -85,6 +85,56 @@ distinct from SAMP / RETR / PRIO / ANNL.
                the category index (randint(low, high) without ``low``).
 
 A row's values are a function of (seed, g, the set, the label list) alone.
+
+Groups (``joint="tree"``, csrc/tpe_joint_tree.hip).  The
+criterion above covers the labels live in every configuration; on a space
+that opens with a ``switch`` that is the selector alone.  ``joint="tree"``
+gives every label a joint mixture: one per group of labels that share an
+activation condition.
+
+  groups       ``domain.live_program()`` gives every label a tuple of clauses.
+               Labels with identical clause tuples form a group, its labels in
+               ``domain.params`` order; groups are ordered by the position of
+               their first label (``joint_groups``).  The group with the empty
+               clause is the root group: its labels are ``joint_labels(domain)``
+               and it comes first.  A space without a program (a ``switch`` on
+               an expression) that is not flat raises ValueError; a label-free
+               space raises as above.  Per group D_g <= ``TPE_COND_MAX_LABELS``
+               and K <= ``TPE_JOINT_MAX_CAT``.
+  sets         the below / above split is the global one (``split_masks``).
+               Group g's below (above) set is the rows of that side in which
+               every label of g is active -- ``set_rows`` with the group's
+               columns; a row with only some of them (foreign trials) is left
+               out and does not count in n.  Weights, the prior component,
+               factors, ``cat_smoothing`` and the mixture sum are the ones
+               above with D_g for D in the bandwidth exponent and n the
+               group's set size.  An empty set (a branch never tried) is the
+               prior alone.
+  criterion    ``J_g(c) = log L_below,g(c) - log L_above,g(c)`` over group g's
+               labels, for the rows c in which g is live.  S(c) is the
+               sequential fp64 sum, in group order, of J_g(c) over the groups
+               live in row c, starting as S = J_root (assigned, not added to
+               0.0): on a flat space S has the bits of ``joint=True``.  Every
+               label is joint: no univariate term is added.  NaN ranks first.
+               ``score_configs(joint="tree", return_terms=True)`` gives (S,
+               terms, J): ``terms`` all NaN, J the (P, G) matrix of J_g, NaN
+               where group g is not live in the row; S is exactly the
+               sequential fold of J's live columns.
+  drawing      every group's labels are drawn for all P rows from that group's
+               below mixture by the rule above (entries of rows in which the
+               group turns out not to be live are ignored, as a sampled pool
+               ignores them for any label under a ``switch``).  Label keys
+               stay ``tpe.label_key(seed, label)``.  The root group's
+               component key stays ``component_key(seed)``; group g's is
+               ``group_component_key(seed, first label of g)`` =
+               ``_mix64(label_key(seed, first label) ^ STREAM_JOINT)``, so no
+               two groups pick their components from one Philox word.  One
+               ``tpe_rows_active`` after all groups gives the activity, and
+               the pool is born with the tree S of its own rows.
+
+Not built: a group conditioned on its ancestors' non-selector labels -- the
+chain-rule ratio L(ctx + g) / L(ctx), which would see a root label interact
+with a branch label.  Groups are independent mixtures.
 """
 from __future__ import annotations
 
@@ -111,6 +161,51 @@ def joint_labels(domain):
     domain = as_domain(domain)
     live = set(domain.reachable({}))
     return [lab for lab in domain.params if lab in live]
+
+
+class Group(object):
+    """A group of labels that share an activation condition: ``clauses`` (the
+    labels' common entry of ``domain.live_program()``; ``()`` for the root
+    group) and ``labels`` in ``domain.params`` order."""
+    __slots__ = ("clauses", "labels")
+
+    def __init__(self, clauses, labels):
+        self.clauses, self.labels = clauses, labels
+
+    def __repr__(self):
+        return "Group(%r, %r)" % (self.clauses, self.labels)
+
+
+def joint_groups(domain):
+    """The groups of ``joint="tree"`` (module doc, "Groups"), the root group
+    first: a list of ``Group``.  ValueError on a label-free space, and on a
+    space without a liveness program that is not flat."""
+    domain = as_domain(domain)
+    root = joint_labels(domain)
+    if not root:
+        label_models(domain)  # (raises: the space has no joint label)
+    prog = domain.live_program()
+    if prog is None:
+        if len(root) == len(domain.params):
+            return [Group(((),), root)]
+        raise ValueError("joint='tree' needs the space's liveness as a program, and this space "
+                         "has none: a switch is selected by something other than a bare "
+                         "hp.choice / hp.pchoice / hp.randint(n) label")
+    groups = {}
+    for lab in domain.params:  # (a dict keeps the order of first insertion)
+        groups.setdefault(prog[lab], []).append(lab)
+    out = [Group(clauses, labs) for clauses, labs in groups.items()]
+    # the walk that orders ``domain.params`` meets a switch's selector before
+    # its branches, so the first label is always live: the root group leads
+    assert out[0].clauses == ((),) and out[0].labels == root
+    return out
+
+
+def group_component_key(seed, first_label):
+    """The Philox key of the component pick of the group whose first label is
+    ``first_label`` (not the root group: that one keeps ``component_key``)."""
+    from . import tpe as T
+    return T._mix64(T.label_key(seed, first_label) ^ STREAM_JOINT)
 
 
 def forgetting_weights(n, lf):
@@ -150,12 +245,14 @@ class LabelModel(object):
                  "n_cat", "p", "offset")
 
 
-def label_models(domain):
-    """One ``LabelModel`` per joint label; ValueError on a label-free space."""
+def label_models(domain, group=None):
+    """One ``LabelModel`` per joint label -- per label of the list ``group``
+    where one is given (a group of ``joint_groups``); ValueError on a
+    label-free space."""
     domain = as_domain(domain)
     labels = list(domain.params)
     out = []
-    for lab in joint_labels(domain):
+    for lab in (joint_labels(domain) if group is None else group):
         spec = domain.specs[lab]
         m = LabelModel()
         m.label, m.col = lab, labels.index(lab)
@@ -270,16 +367,25 @@ def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing):
 
 def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
                 linear_forgetting=25, bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING,
-                return_parts=False):
+                return_parts=False, tree=False):
     """J (module doc) of the configurations ``vals`` -- (P, L) stored values in
     ``domain.params`` column order, as ``Pool.vals`` holds them -- under the
     history ``hist`` (``tpe.collect_history``), in numpy: fp64 (P,).  On a
     space without ``switch`` J is the whole criterion; the univariate terms
     of conditional labels are the device path's (``score_configs``).
     ``active`` is accepted for symmetry with ``Pool``: the joint labels are
-    live in every row.  ``return_parts``: (J, log L_below, log L_above)."""
+    live in every row.  ``return_parts``: (J, log L_below, log L_above).
+
+    ``tree=True``: S of ``joint="tree"`` (module doc, "Groups") -- the whole
+    criterion on any space with a liveness program.  ``active`` ((P, L); None:
+    where ``vals`` is not NaN) says where a group is live.  ``return_parts``:
+    (S, J, log L_below, log L_above), the last three (P, G) matrices, NaN
+    where the group is not live."""
     from . import tpe as T
     domain = as_domain(domain)
+    if tree:
+        return _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma,
+                                 linear_forgetting, bandwidth, cat_smoothing, return_parts)
     models = label_models(domain)
     vals = np.asarray(vals, np.float64)
     cols = [m.col for m in models]
@@ -292,6 +398,32 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
     with np.errstate(invalid="ignore"):
         J = out[0] - out[1]
     return (J, out[0], out[1]) if return_parts else J
+
+
+def _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma, lf, bandwidth, smoothing,
+                      return_parts):
+    from . import tpe as T
+    groups = joint_groups(domain)
+    vals = np.asarray(vals, np.float64)
+    active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
+    P, G = vals.shape[0], len(groups)
+    isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+    parts = np.full((3, P, G), np.nan)  # J, log L_below, log L_above
+    S = None
+    for g, grp in enumerate(groups):
+        models = label_models(domain, grp.labels)
+        cols = [m.col for m in models]
+        live = active[:, cols].all(1)
+        if (active[:, cols].any(1) != live).any() or (g == 0 and not live.all()):
+            raise ValueError("a group's labels are not active together in some row")
+        x = vals[live][:, cols]
+        lb, la = (_set_log_l(models, hist, set_rows(hist, mask, cols), x, lf, prior_weight,
+                             bandwidth, smoothing) for mask in (isb, isa))
+        with np.errstate(invalid="ignore"):
+            parts[0, live, g], parts[1, live, g], parts[2, live, g] = lb - la, lb, la
+            # (S starts as J_root, assigned: the root group is live in every row)
+            S = parts[0, :, 0].copy() if g == 0 else np.where(live, S + parts[0, :, g], S)
+    return (S, parts[0], parts[1], parts[2]) if return_parts else S
 
 
 # -- device path -----------------------------------------------------------------
@@ -349,13 +481,14 @@ def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp
 
 
 def prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight, linear_forgetting,
-                 bandwidth, cat_smoothing):
+                 bandwidth, cat_smoothing, group=None):
     """The space's label records and both sets on the device: (dj, [below,
     above], stream pointer), a set as ``_prepare_set`` returns it.  ``seen``:
     ``pool._seen_rows(eng, hist)``; ``n_cols``: the columns of the history
-    (and of the pool: both are in ``domain.params`` order)."""
+    (and of the pool: both are in ``domain.params`` order); ``group``: the
+    labels of one group of ``joint_groups`` in place of the joint labels."""
     t = eng.torch
-    models = label_models(domain)
+    models = label_models(domain, group)
     dj = _device_labels(eng, models, cat_smoothing)
     sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
     cols = [m.col for m in models]
@@ -410,13 +543,14 @@ def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, 
 
 
 def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals, ld,
-                  n_cols, row_base, n_rows, comp_out=None):
+                  n_cols, row_base, n_rows, comp_out=None, comp_key=None):
     """Rows [row_base, row_base + n_rows) of the joint draw (module doc) from
     the below set of ``prepared`` (``prepare_sets``) into rows [0, n_rows) of
     the joint labels' columns of the label-major device block ``d_vals``
     (tpe_joint_sample).  ``comp_out``: a device int32 tensor for the rows'
-    components.  Three small uploads: the component cdf, the discrete labels'
-    cdf table and the keys."""
+    components; ``comp_key``: the component pick's key where it is not
+    ``component_key(seed)`` (a group that is not the root's).  Three small
+    uploads: the component cdf, the discrete labels' cdf table and the keys."""
     from . import tpe as T
     t, lib = eng.torch, eng.lib
     dj, sets, sp = prepared
@@ -424,8 +558,8 @@ def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoo
     cdf = t.from_numpy(sample_cdf(n, linear_forgetting, prior_weight)).to(eng.device)
     cats = [np.cumsum(m.p) for m in dj.models if m.kind == _L.JOINT_CAT]
     cat_cdf = t.from_numpy(np.concatenate(cats)).to(eng.device) if cats else None
-    keys = np.asarray([T.label_key(seed, m.label) for m in dj.models] + [component_key(seed)],
-                      np.uint64)
+    keys = np.asarray([T.label_key(seed, m.label) for m in dj.models] +
+                      [component_key(seed) if comp_key is None else comp_key], np.uint64)
     d_keys = t.from_numpy(keys.view(np.int64)).to(eng.device)
     _L.check(lib.tpe_joint_sample(dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
                                   dset.data_ptr(), n, cdf.data_ptr(),
@@ -435,3 +569,81 @@ def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoo
                                   d_vals.data_ptr(), ld, n_cols,
                                   None if comp_out is None else comp_out.data_ptr(), sp),
              "tpe_joint_sample")
+
+
+# -- groups on the device (module doc, "Groups") ---------------------------------
+def prepare_tree(eng, domain, hist, seen, isb, isa, n_cols, prior_weight, linear_forgetting,
+                 bandwidth, cat_smoothing):
+    """``prepare_sets`` per group of ``joint_groups(domain)``: [(group,
+    prepared)], the root group (the joint labels) first."""
+    return [(grp, prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
+                               linear_forgetting, bandwidth, cat_smoothing, group=grp.labels))
+            for grp in joint_groups(domain)]
+
+
+def sample_tree_device(eng, tree, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals, ld,
+                       n_cols, row_base, n_rows):
+    """``sample_device`` per group of ``tree`` (``prepare_tree``): every group's
+    columns for all the rows, the root group under ``component_key(seed)``,
+    the others under their ``group_component_key``."""
+    for g, (grp, prepared) in enumerate(tree):
+        key = None if g == 0 else group_component_key(seed, grp.labels[0])
+        sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals,
+                      ld, n_cols, row_base, n_rows, comp_key=key)
+
+
+def score_tree_device(eng, domain, hist, seen, isb, isa, d_vals, d_active, ld, n_cols, P, out,
+                      prior_weight, linear_forgetting, bandwidth, cat_smoothing, parts=None,
+                      tree=None):
+    """S of ``joint="tree"`` for rows [0, P) of the label-major device pool
+    ``d_vals`` / ``d_active`` (bytes; leading dimension ``ld``) into the device
+    vector ``out``.  The root group goes through ``score_device`` (out = J_root:
+    the flat case is that code alone).  Every other group, in order: both sets
+    prepared from the group's rows of the history, the pool's rows in which the
+    group is live compacted once into a device list (tpe_rows_compact on the
+    first label's activity: a group's labels share theirs), then per window of
+    ``ROWS_PER_CALL`` list positions log L_above into a dense temporary and
+    log L_below minus it added to ``out`` at the listed rows
+    (tpe_joint_score_rows).  The list's length never comes to the host.
+    ``parts``: a (G, >= P) device tensor filled with NaN; row g receives J_g at
+    the rows in which group g is live.  ``tree``: ``prepare_tree``'s result for
+    the same arguments, where the caller has made it already."""
+    t, lib = eng.torch, eng.lib
+    if tree is None:
+        tree = prepare_tree(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
+                            linear_forgetting, bandwidth, cat_smoothing)
+    score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, prior_weight,
+                 linear_forgetting, bandwidth, cat_smoothing, prepared=tree[0][1])
+    if parts is not None:
+        parts[0, :P].copy_(out[:P])
+    if len(tree) == 1 or P == 0:
+        return
+    win = min(P, ROWS_PER_CALL)
+    need = max(lib.tpe_joint_scratch_bytes(win, n) for _, (_, sets, _) in tree[1:]
+               for _, n, _ in sets)
+    scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
+    above = t.empty(win, dtype=t.float64, device=eng.device)
+    rows = t.empty(P, dtype=t.int64, device=eng.device)
+    count = t.empty(1, dtype=t.int64, device=eng.device)
+    cscratch = t.empty(lib.tpe_rows_compact_scratch_bytes(P), dtype=t.uint8, device=eng.device)
+    both = _L.JOINT_OUT_SCATTER | _L.JOINT_OUT_ADD
+    for g, (grp, (dj, sets, sp)) in enumerate(tree[1:], 1):
+        D = len(dj.models)
+        tab = None if dj.tables is None else dj.tables.data_ptr()
+        flags = d_active.data_ptr() + dj.models[0].col * ld
+        _L.check(lib.tpe_rows_compact(flags, P, rows.data_ptr(), count.data_ptr(),
+                                      cscratch.data_ptr(), sp), "tpe_rows_compact")
+
+        def score(which, p0, sub, dst, mode):
+            dset, n, _ = sets[which]
+            _L.check(lib.tpe_joint_score_rows(dj.host.ctypes.data, dj.dev.data_ptr(), D, tab,
+                                              dj.n_tables, dset.data_ptr(), n, d_vals.data_ptr(),
+                                              ld, n_cols, rows.data_ptr(), count.data_ptr(), p0,
+                                              min(win, P - p0), sub, dst, mode,
+                                              scratch.data_ptr(), sp), "tpe_joint_score_rows")
+
+        for p0 in range(0, P, win):
+            score(1, p0, None, above.data_ptr(), 0)
+            if parts is not None:  # (the same call as the one added to S: the same bits)
+                score(0, p0, above.data_ptr(), parts[g].data_ptr(), _L.JOINT_OUT_SCATTER)
+            score(0, p0, above.data_ptr(), out.data_ptr(), both)

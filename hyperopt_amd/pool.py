@@ -52,7 +52,10 @@ builds both sets from the resident history and scores the rows); the fold
 adds the terms of the labels under a ``switch`` onto J.
 ``Pool.sample(joint=True)`` / ``suggest_sampled(joint=True, draw="joint")``
 also draw the always-live labels of every row from the below set's joint
-mixture (csrc/tpe_joint_sample.hip), so the candidates themselves follow an
+mixture (csrc/tpe_joint_sample.hip); ``joint="tree"``, accepted wherever
+``joint=True`` is, gives the labels under a ``switch`` joint mixtures as well,
+one per group of labels that share an activation condition (joint.py
+"Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
 interaction between labels.
 """
 from __future__ import annotations
@@ -319,7 +322,15 @@ class Pool(object):
         joint criterion's S: J of the drawn rows, then the fold of the live
         non-joint labels' own terms onto it -- ``score_configs(joint=True)`` of
         the same pool (bit for bit on a flat space).  ``keep_terms`` leaves NaN
-        in the joint labels' columns."""
+        in the joint labels' columns.
+
+        ``joint="tree"``: every group of labels that share an activation
+        condition (``tpe.joint_groups``) is drawn, for all the rows, from that
+        group's own below mixture (joint.py, "Groups": the root group with the
+        keys and bits of ``joint=True``, every other group under its own
+        component key); the activity follows from the drawn selectors, and
+        the pool is born with ``score_configs(joint="tree")`` of its rows.
+        ``keep_terms`` leaves NaN everywhere: every label is joint."""
         return _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting,
                        keep_terms, joint=_joint_kw(joint, bandwidth, cat_smoothing))
 
@@ -527,7 +538,7 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
         raise ValueError("n_rows=%d" % P)
     jcols = []
     if joint is not None:  # (ValueError on a space without a joint label)
-        jcols = [m.col for m in _J.label_models(domain)]
+        jcols = _joint_cols(domain, joint)
     if P == 0:
         return Pool.from_arrays(domain, np.zeros((0, L)), np.zeros((0, L), bool))
     if joint is not None and hist is None:
@@ -567,7 +578,16 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
     chunks = [todo[c0:c0 + per] for c0 in range(0, len(todo), per)]
     n_active = None
     prepared = None
-    if joint is not None:
+    tree = joint is not None and joint.get("tree")
+    if tree:
+        # every group's columns, for all the rows, from the group's below mixture
+        isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+        prepared = _J.prepare_tree(eng, domain, hist, _seen_rows(eng, hist), isb, isa, L,
+                                   prior_weight, linear_forgetting, joint["bandwidth"],
+                                   joint["cat_smoothing"])
+        _J.sample_tree_device(eng, prepared, seed, prior_weight, linear_forgetting,
+                              joint["cat_smoothing"], d.vals, P, L, 0, P)
+    elif joint is not None:
         # the joint labels' columns: one draw per row from the below set's mixture
         isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
         prepared = _J.prepare_sets(eng, domain, hist, _seen_rows(eng, hist), isb, isa, L,
@@ -588,9 +608,15 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
         if not chunks:
             n_active = _rows_active(eng, domain, labels, d, P, sp)
         # S starts from J of the drawn rows; the fold below adds the other labels
-        _J.score_device(eng, domain, hist, None, None, None, d.vals, P, L, P, d.S, prior_weight,
-                        linear_forgetting, joint["bandwidth"], joint["cat_smoothing"],
-                        prepared=prepared)
+        # (with the groups every label is joint: S is theirs, and nothing is folded)
+        if tree:
+            _J.score_tree_device(eng, domain, hist, None, None, None, d.vals, d.active, P, L, P,
+                                 d.S, prior_weight, linear_forgetting, joint["bandwidth"],
+                                 joint["cat_smoothing"], tree=prepared)
+        else:
+            _J.score_device(eng, domain, hist, None, None, None, d.vals, P, L, P, d.S,
+                            prior_weight, linear_forgetting, joint["bandwidth"],
+                            joint["cat_smoothing"], prepared=prepared)
         init = 0
         if keep_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -940,12 +966,19 @@ GRID_JOINT = ("the joint criterion is not separable over the axes of a GridPool;
 
 def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None):
     """J (joint.py) of every pool row into ``d.S``.  ``parts``: a (3, P) device
-    tensor for log L below, log L above and J."""
+    tensor for log L below, log L above and J.  With ``jkw["tree"]`` it is the
+    groups' S that goes into ``d.S``, and ``parts`` is a (G, P) device tensor
+    filled with NaN for the J_g (``joint.score_tree_device``)."""
     from . import tpe as T
     if hist.tids.size:
         isb, isa = T.split_masks(hist, gamma)
     else:
         isb = isa = np.zeros(0, bool)
+    if jkw.get("tree"):
+        _J.score_tree_device(eng, domain, hist, _seen_rows(eng, hist), isb, isa, d.vals, d.active,
+                             d.vals.shape[1], len(pool.labels), len(pool), d.S, prior_weight, lf,
+                             jkw["bandwidth"], jkw["cat_smoothing"], parts)
+        return
     _J.score_device(eng, domain, hist, _seen_rows(eng, hist), isb, isa, d.vals, d.vals.shape[1],
                     len(pool.labels), len(pool), d.S, prior_weight, lf, jkw["bandwidth"],
                     jkw["cat_smoothing"], parts)
@@ -968,7 +1001,7 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
     if joint is not None:
         from . import tpe as T
         # (ValueError on a space without a joint label)
-        jcols = [m.col for m in _J.label_models(domain)]
+        jcols = _joint_cols(domain, joint)
         if hist is None:
             hist = T.collect_history(trials, pool.labels)
         rest = [j for j in range(len(pool.labels)) if pool.n_active[j] and j not in jcols]
@@ -1134,13 +1167,29 @@ def _topk_device(eng, d, P, k, taken=None):
 
 
 def _joint_kw(joint, bandwidth, cat_smoothing):
-    """``_score_device``'s ``joint``: None, or the criterion's keywords."""
-    if not joint:
+    """``_score_device``'s ``joint``: None, or the criterion's keywords
+    (``tree``: the string ``"tree"`` was given -- one mixture per group of
+    labels, joint.py "Groups"; any other truthy value is ``joint=True``)."""
+    if isinstance(joint, str) and joint == "tree":
+        tree = True
+    elif not joint:
         return None
+    else:
+        tree = False
     if not bandwidth > 0.0 or not cat_smoothing >= 0.0:
         raise ValueError("bandwidth=%r must be > 0, cat_smoothing=%r >= 0"
                          % (bandwidth, cat_smoothing))
-    return dict(bandwidth=float(bandwidth), cat_smoothing=float(cat_smoothing))
+    return dict(bandwidth=float(bandwidth), cat_smoothing=float(cat_smoothing), tree=tree)
+
+
+def _joint_cols(domain, jkw):
+    """The columns the joint criterion of ``jkw`` covers: the joint labels',
+    or with ``tree`` every label's (ValueError on a space without a joint
+    label, or without the groups ``tree`` needs)."""
+    if jkw.get("tree"):
+        labels = list(domain.params)
+        return [labels.index(lab) for grp in _J.joint_groups(domain) for lab in grp.labels]
+    return [m.col for m in _J.label_models(domain)]
 
 
 def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
@@ -1164,7 +1213,18 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     ``domain.params`` order; on a flat space S = J.  ``return_terms`` then
     gives (S, terms, J), ``terms`` NaN in the joint labels' columns.  A
     ``GridPool`` raises ValueError (J is not separable over axes:
-    ``GridPool.to_pool()``), and so does a space without a joint label."""
+    ``GridPool.to_pool()``), and so does a space without a joint label.
+
+    ``joint="tree"``: one such mixture per group of labels that share an
+    activation condition (``tpe.joint_groups``; joint.py, "Groups"), each
+    built from the history rows and scored on the pool rows in which its
+    group is live.  S[r] starts as J_root[r] and the J_g[r] of the other
+    groups live in row r are added in group order; no univariate term is
+    added.  On a flat space S has the bits of ``joint=True``.
+    ``return_terms`` gives (S, terms, J): ``terms`` all NaN, J the (P, G)
+    matrix of J_g, NaN where group g is not live in the row.  A space whose
+    switches are not selected by bare choice / randint(n) labels raises
+    ValueError.  Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
     if isinstance(pool, GridPool):
@@ -1179,13 +1239,19 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     if jkw is not None and return_terms:  # (J is read before the fold adds to it)
         from . import tpe as T
         eng = T.engine()
-        parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
+        if jkw["tree"]:  # (a row per group, NaN where the group is not live)
+            parts = eng.torch.full((len(_J.joint_groups(domain)), max(P, 1)), float("nan"),
+                                   dtype=eng.torch.float64, device=eng.device)
+        else:
+            parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
     eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
                            return_terms, joint=jkw, parts=parts)
     S = d.S[:P].cpu().numpy()
     if not return_terms:
         return S
     terms = np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
+    if jkw is not None and jkw["tree"]:
+        return S, terms, np.ascontiguousarray(parts[:, :P].cpu().numpy().T)
     return (S, terms) if parts is None else (S, terms, parts[2, :P].cpu().numpy())
 
 
@@ -1231,9 +1297,10 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     taken row still counts as the first of its class.  A ``GridPool`` raises
     ValueError: its rows are distinct by construction.
 
-    ``joint=True`` ranks by ``score_configs(joint=True, bandwidth=...,
-    cat_smoothing=...)``: the same selection, ``distinct`` and startup rules,
-    other scores.  A ``GridPool`` raises ValueError."""
+    ``joint=True`` (``joint="tree"``) ranks by ``score_configs(joint=True,
+    bandwidth=..., cat_smoothing=...)`` (``joint="tree"``): the same selection,
+    ``distinct`` and startup rules, other scores.  A ``GridPool`` raises
+    ValueError."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
@@ -1368,7 +1435,10 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     with ``Pool.sample(joint=True)``: the always-live labels of every row are
     one draw from the joint l, and the pool is ranked by the S it is born
     with.  ``keep``, ``distinct``, the k-documents rule and the startup phase
-    are the same for both."""
+    are the same for both.  ``joint="tree"`` is the same with the groups'
+    criterion (``score_configs(joint="tree")``) and, under ``draw="joint"``,
+    ``Pool.sample(joint="tree")``: the labels under a ``switch`` are drawn
+    jointly too."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
@@ -1380,7 +1450,7 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     domain = as_domain(domain)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
     if jkw is not None:
-        _J.label_models(domain)  # (ValueError on a space without a joint label)
+        _joint_cols(domain, jkw)  # (ValueError on a space without a joint label)
     labels = list(domain.params)
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)

@@ -36,7 +36,9 @@ mixture over whole configurations instead of a sum over labels
 (hyperopt_amd/joint.py; ``joint_labels``, ``joint_score_numpy``);
 ``Pool.sample(joint=True)`` / ``suggest_sampled(joint=True, draw="joint")``
 also draw the rows from that mixture (``joint_component_key``: the key of the
-draws' component pick).
+draws' component pick).  ``joint="tree"`` gives the labels under a ``switch``
+joint mixtures too, one per group of labels that share an activation
+condition (``joint_groups``, ``joint_group_component_key``).
 """
 from __future__ import annotations
 
@@ -791,5 +793,6 @@ def _suggest_many(requests, shard_studies=False):
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, score_configs,  # noqa: E402,F401
                    suggest_from_pool, suggest_sampled)
-from .joint import (component_key as joint_component_key, joint_labels,  # noqa: E402,F401
+from .joint import (component_key as joint_component_key,  # noqa: E402,F401
+                    group_component_key as joint_group_component_key, joint_groups, joint_labels,
                     score_numpy as joint_score_numpy)

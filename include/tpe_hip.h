@@ -922,6 +922,54 @@ int tpe_joint_sample(const tpe_joint_label* host_labels, const tpe_joint_label* 
 /* host: TPE_JOINT_SAMPLE_STAGE as the library was built */
 int tpe_joint_sample_stage(void);
 
+/* ---- the joint criterion on a list of rows (tpe.score_configs(joint="tree")) --
+ * A group of labels under a `switch` is live in some pool rows only; its
+ * mixture is scored on those (hyperopt_amd/joint.py, "Groups").
+ *
+ * tpe_rows_compact: out_rows[0, c) (device int64) = the ascending indices
+ * r < n_rows with flags[r] != 0, *out_count (device int64) = c; entries of
+ * out_rows at or past c are not written.  flags: n_rows bytes on the device --
+ * one label's row of a pool's label-major `active` block.  Exact and
+ * independent of block scheduling: a count per block of rows, an integer scan
+ * of the counts, a scatter by the row's rank within its block; no atomics.
+ * scratch: tpe_rows_compact_scratch_bytes(n_rows) bytes (-1: bad arguments),
+ * 8-byte aligned.  n_rows == 0 writes the count 0 and needs neither flags nor
+ * out_rows.  tpe_rows_compact_layout (host): out[0] = the rows one block
+ * handles, out[1] = the rows one pass of the scan's single block covers;
+ * returns 2.
+ *
+ * tpe_joint_score_rows: tpe_joint_score (above) with the dense row window
+ * replaced by a window of a device list.  List position p in [list_begin,
+ * min(list_begin + max_rows, *d_count)) scores pool row rows[p]:
+ *   v = log L(row rows[p]) - (sub ? sub[p - list_begin] : 0)
+ *   out_mode 0                                       out[p - list_begin] = v
+ *   TPE_JOINT_OUT_SCATTER                            out[rows[p]] = v
+ *   TPE_JOINT_OUT_SCATTER | TPE_JOINT_OUT_ADD        out[rows[p]] = out[rows[p]] + v
+ * (any other out_mode: TPE_E_ARG).  rows (device int64) holds at least
+ * *d_count entries; d_count is read on the device only -- the host never
+ * learns it, and max_rows, the host's bound, sizes the grid and the scratch
+ * (tpe_joint_scratch_bytes(max_rows, n) bytes, 16-byte aligned).  Positions at
+ * or past the count write nothing, and a block of 256 positions that starts
+ * there returns at once.  An entry outside [0, ld) is skipped: nothing of that
+ * row is read and nothing is written for it (a device list cannot be checked
+ * by the host, and a bad one must not fault).  A list holds distinct rows:
+ * with a row listed twice the scattering modes write it twice, in no stated
+ * order.  out: max_rows doubles for out_mode 0, ld doubles otherwise.  log L of
+ * a row has the bits tpe_joint_score gives that row under the same prepared
+ * set.  Limits, errors and stream conventions as tpe_joint_score; max_rows ==
+ * 0 and ld == 0 are no-ops. */
+enum { TPE_JOINT_OUT_SCATTER = 1, TPE_JOINT_OUT_ADD = 2 };
+int64_t tpe_rows_compact_scratch_bytes(int64_t n_rows);
+int tpe_rows_compact_layout(int64_t* out, int n);
+int tpe_rows_compact(const uint8_t* flags, int64_t n_rows, int64_t* out_rows, int64_t* out_count,
+                     void* scratch, void* stream);
+int tpe_joint_score_rows(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                         int n_labels, const double* tables, int64_t n_tables, const double* set,
+                         int64_t n, const double* vals, int64_t ld, int n_cols,
+                         const int64_t* rows, const int64_t* d_count, int64_t list_begin,
+                         int64_t max_rows, const double* sub, double* out, int out_mode,
+                         void* scratch, void* stream);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
