@@ -74,6 +74,7 @@ JOINT_CONT, JOINT_QUANT, JOINT_CAT = 0, 1, 2
 JOINT_LOG, JOINT_BOUNDED = 1, 2
 JOINT_MAX_CAT = 65536
 JOINT_OUT_SCATTER, JOINT_OUT_ADD = 1, 2  # tpe_joint_score_rows' out_mode
+GRID_JOINT_STORE, GRID_JOINT_ADD = 0, 1  # tpe_grid_joint_score's out_mode
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
 # tpe_run_ops record codes (tpe_hip.h TPE_OP_*): entry point -> code
@@ -171,6 +172,13 @@ _SIGNATURES = {
     "tpe_pool_distinct": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _I64, _P, _I64, _P, _I, _P, _P,
                                _P, _P, _P]),
     "tpe_grid_fold": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
+    "tpe_grid_fold_onto": (_I, [_P, _P, _P, _P, _I, _I64, _I64, _P, _P]),
+    "tpe_grid_joint_layout": (_I, [_P, _I]),
+    "tpe_grid_joint_scratch_bytes": (_I64, [_I64, _I64]),
+    "tpe_grid_joint_factors": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P,
+                                    _I64, _I64, _I64, _I64, _P]),
+    "tpe_grid_joint_score": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I, _I64, _I64,
+                                  _P, _P, _I, _P, _I, _P]),
     "tpe_joint_set_doubles": (_I64, [_I, _I64]),
     "tpe_joint_scratch_bytes": (_I64, [_I64, _I64]),
     "tpe_joint_prep": (_I, [_P, _P, _I, _P, _P, _I64, _I, _P, _I64, _P, _P]),

@@ -59,6 +59,10 @@ struct GridStage {
   int64_t off, radix, d0;
 };
 
+// Onto: the accumulator starts from S (tpe_grid_fold_onto), and a label with
+// off < 0 takes part in the decode alone: it stages nothing and adds nothing
+// (kind 3)
+template <bool Onto>
 __global__ __launch_bounds__(kGBS) void k_grid_fold(const double* __restrict__ bl,
                                                     const double* __restrict__ al, GridArgs A,
                                                     int64_t row_begin, int64_t n_rows,
@@ -104,6 +108,10 @@ __global__ __launch_bounds__(kGBS) void k_grid_fold(const double* __restrict__ b
         p.a = s - rem < kGTile ? (int32_t)(s - rem) : kGTile;
       }
     }
+    if (Onto && A.off[i] < 0) {
+      p.kind = 3;
+      cnt = 0;
+    }
     sL[i] = p;
     sS[i] = g;
     sBase[i] = cnt;
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(kGBS) void k_grid_fold(const double* __restrict__ b
   for (int k = 0; k < kGPer; ++k) {
     const int row = (int)threadIdx.x + k * kGBS;
     j[k] = row < nv ? row : nv - 1;  // (a row past the tile's end reads a staged entry too)
-    acc[k] = 0.0;
+    acc[k] = Onto ? S[t0 + j[k]] : 0.0;
   }
   for (int i = 0; i < n; ++i) {
     const GridLab p = sL[i];
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(kGBS) void k_grid_fold(const double* __restrict__ b
 #pragma unroll
       for (int k = 0; k < kGPer; ++k)
         acc[k] = acc[k] + sD[base + (int32_t)((uint32_t)(b + j[k]) / (uint32_t)a)];
-    } else {
+    } else if (!Onto || kind == 0) {
 #pragma unroll
       for (int k = 0; k < kGPer; ++k) acc[k] = acc[k] + sD[base + (j[k] >= a ? 1 : 0)];
     }
@@ -178,20 +186,21 @@ __global__ __launch_bounds__(kGBS) void k_grid_fold(const double* __restrict__ b
 
 using namespace tpe;
 
-extern "C" int tpe_grid_fold(const double* bl, const double* al, const int64_t* host_off,
-                             const int64_t* host_radix, int n_labels, int64_t row_begin,
-                             int64_t n_rows, double* S_out, void* stream) {
+namespace {
+template <bool Onto>
+int grid_fold(const char* fn, const double* bl, const double* al, const int64_t* host_off,
+              const int64_t* host_radix, int n_labels, int64_t row_begin, int64_t n_rows,
+              double* S_out, void* stream) {
   if (n_labels < 0 || n_labels > kGridMax) {
-    set_error("tpe_grid_fold: n_labels=%d outside [0, %d]", n_labels, kGridMax);
+    set_error("%s: n_labels=%d outside [0, %d]", fn, n_labels, kGridMax);
     return TPE_E_ARG;
   }
   if (row_begin < 0 || n_rows < 0) {
-    set_error("tpe_grid_fold: row_begin=%lld n_rows=%lld", (long long)row_begin,
-              (long long)n_rows);
+    set_error("%s: row_begin=%lld n_rows=%lld", fn, (long long)row_begin, (long long)n_rows);
     return TPE_E_ARG;
   }
   if (n_labels > 0 && (!host_off || !host_radix)) {
-    set_error("tpe_grid_fold: null pointer (host_off / host_radix)");
+    set_error("%s: null pointer (host_off / host_radix)", fn);
     return TPE_E_ARG;
   }
   GridArgs A;
@@ -201,31 +210,46 @@ extern "C" int tpe_grid_fold(const double* bl, const double* al, const int64_t* 
     A.off[i] = i < n_labels ? host_off[i] : 0;
     A.radix[i] = i < n_labels ? host_radix[i] : 1;
     if (A.radix[i] < 1) {
-      set_error("tpe_grid_fold: label %d has radix %lld < 1", i, (long long)A.radix[i]);
+      set_error("%s: label %d has radix %lld < 1", fn, i, (long long)A.radix[i]);
       return TPE_E_ARG;
     }
     if (rows > INT64_MAX / A.radix[i]) {
-      set_error("tpe_grid_fold: the block's row count overflows int64 at label %d", i);
+      set_error("%s: the block's row count overflows int64 at label %d", fn, i);
       return TPE_E_ARG;
     }
     rows *= A.radix[i];
   }
   if (row_begin > rows || n_rows > rows - row_begin) {
-    set_error("tpe_grid_fold: rows [%lld, %lld + %lld) leave the block of %lld rows",
+    set_error("%s: rows [%lld, %lld + %lld) leave the block of %lld rows", fn,
               (long long)row_begin, (long long)row_begin, (long long)n_rows, (long long)rows);
     return TPE_E_ARG;
   }
   if (n_rows == 0) return TPE_OK;
   if (!S_out || (n_labels > 0 && (!bl || !al))) {
-    set_error("tpe_grid_fold: null pointer");
+    set_error("%s: null pointer", fn);
     return TPE_E_ARG;
   }
   const int64_t tiles = (n_rows + kGTile - 1) / kGTile;
   if (tiles > 2147483647) {
-    set_error("tpe_grid_fold: n_rows=%lld does not fit a launch", (long long)n_rows);
+    set_error("%s: n_rows=%lld does not fit a launch", fn, (long long)n_rows);
     return TPE_E_ARG;
   }
-  hipLaunchKernelGGL(k_grid_fold, dim3((unsigned)tiles), dim3(kGBS), 0, (hipStream_t)stream, bl,
-                     al, A, row_begin, n_rows, S_out);
-  return check_launch("tpe_grid_fold");
+  hipLaunchKernelGGL(k_grid_fold<Onto>, dim3((unsigned)tiles), dim3(kGBS), 0,
+                     (hipStream_t)stream, bl, al, A, row_begin, n_rows, S_out);
+  return check_launch(fn);
+}
+}  // namespace
+
+extern "C" int tpe_grid_fold(const double* bl, const double* al, const int64_t* host_off,
+                             const int64_t* host_radix, int n_labels, int64_t row_begin,
+                             int64_t n_rows, double* S_out, void* stream) {
+  return grid_fold<false>("tpe_grid_fold", bl, al, host_off, host_radix, n_labels, row_begin,
+                          n_rows, S_out, stream);
+}
+
+extern "C" int tpe_grid_fold_onto(const double* bl, const double* al, const int64_t* host_off,
+                                  const int64_t* host_radix, int n_labels, int64_t row_begin,
+                                  int64_t n_rows, double* S, void* stream) {
+  return grid_fold<true>("tpe_grid_fold_onto", bl, al, host_off, host_radix, n_labels, row_begin,
+                         n_rows, S, stream);
 }

@@ -132,6 +132,14 @@ activation condition.
                ``tpe_rows_active`` after all groups gives the activity, and
                the pool is born with the tree S of its own rows.
 
+Grid pools (``GridPool(..., joint=True)``, csrc/tpe_grid_joint.hip, DESIGN
+3.5.7).  J is not separable over a grid's axes, but inside a component the
+factor of label d depends on the label's value alone, and on a grid that is one
+of the axis's values: per set the factors form a table of (sum of the axis
+lengths) x (n + 1) doubles, built once by the factor expressions above, and a
+row's ``a_i`` is ``log w_i`` plus one table entry per label, added in the same
+order -- the bits of the materialised pool (``score_grid_device``).
+
 Not built: a group conditioned on its ancestors' non-selector labels -- the
 chain-rule ratio L(ctx + g) / L(ctx), which would see a root label interact
 with a branch label.  Groups are independent mixtures.
@@ -152,6 +160,11 @@ BANDWIDTH = 0.2
 CAT_SMOOTHING = 1.0
 ROWS_PER_CALL = 1 << 14  # pool rows per tpe_joint_score call: bounds its scratch
 STREAM_JOINT = 0x4A4F494E  # "JOIN": the Philox stream word of the joint draws
+# a grid pool (``score_grid_device``): block rows per tpe_grid_joint_score call,
+# which bounds its scratch, and the bytes of one factor table (a starting
+# value, not a measured one)
+GRID_ROWS_PER_CALL = 1 << 14
+GRID_JOINT_TABLE_BYTES = 256 << 20
 
 _erf = np.vectorize(math.erf, otypes=[np.float64])
 
@@ -647,3 +660,108 @@ def score_tree_device(eng, domain, hist, seen, isb, isa, d_vals, d_active, ld, n
             if parts is not None:  # (the same call as the one added to S: the same bits)
                 score(0, p0, above.data_ptr(), parts[g].data_ptr(), _L.JOINT_OUT_SCATTER)
             score(0, p0, above.data_ptr(), out.data_ptr(), both)
+
+
+# -- a grid pool: factor tables per axis ---------------------------
+def score_grid_device(eng, pool, plan, prepared, d_axes, out, parts=None, tree=False):
+    """The joint criterion of every row of the grid pool ``pool`` into the
+    device vector ``out`` (>= len(pool) doubles), with the bits
+    ``score_device`` / ``score_tree_device`` give the materialised pool.
+
+    ``plan``: ``pool.grid_joint_plan(pool, tree)``; ``prepared``: one
+    ``prepare_sets`` result per group of the plan (``prepare_tree``'s, or the
+    joint labels' alone); ``d_axes``: the pool's concatenated axes on the
+    device.  ``parts`` as the pool path takes it: a (3, >= P) device tensor
+    (log L_below, log L_above, J), or with ``tree`` a (G, >= P) tensor filled
+    with NaN whose row g receives J_g where group g is live.
+
+    Inside a component the factor a label adds depends on the label's value
+    alone, so per set the factors of all axis values form a table F of
+    (sum of the group's axis lengths) x C doubles (tpe_grid_joint_factors), and
+    a row's a_i is log w_i plus one entry per label (tpe_grid_joint_score).
+
+    Loop order.  Groups outermost, in group order (the root group stores S,
+    every other group adds J_g).  Per group, a set whose whole F -- rounded up
+    to whole chunks -- fits ``GRID_JOINT_TABLE_BYTES`` is built once, before
+    any row; then blocks in which the group is live, in block order; then
+    windows of at most ``GRID_ROWS_PER_CALL`` rows of the block; per window
+    the above set into a temporary, then the below set minus it into ``out``.
+    A set whose F is larger goes through one shared table of that many bytes
+    in windows of whole chunks, inside the row window: rebuilt per row window
+    and component window, scored into the scratch, merged after the last.
+    Device memory: at most three tables of ``GRID_JOINT_TABLE_BYTES`` (both
+    sets' and the shared one), 16 bytes of scratch per row of the window and
+    chunk of the larger set, and 8 per row of the window."""
+    t, lib = eng.torch, eng.lib
+    chunk = lib.tpe_joint_chunk()
+    P = len(pool)
+    rows_max = max(b.rows for b in pool.blocks)
+    win = min(rows_max, GRID_ROWS_PER_CALL)
+    above = t.empty(win, dtype=t.float64, device=eng.device)
+    n_axes = int(d_axes.numel())
+    shared = None  # the table of the sets that do not fit one
+    for g, (dj, sets, sp) in enumerate(prepared):
+        D = len(dj.models)
+        cols = plan.groups[g]
+        tab = None if dj.tables is None else dj.tables.data_ptr()
+        axis_off = np.ascontiguousarray([pool.axis_off[j] for j in cols], np.int64)
+        axis_len = np.ascontiguousarray([pool.axes[j].size for j in cols], np.int64)
+        frow0 = np.ascontiguousarray([plan.axis_row[g][j] for j in cols], np.int64)
+        n_frows = int(plan.n_frows[g])
+        per = max(1, GRID_JOINT_TABLE_BYTES // (8 * chunk * n_frows))  # chunks per table
+        need = max(lib.tpe_grid_joint_scratch_bytes(win, n) for _, n, _ in sets)
+        scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
+
+        def factors(which, F, ldF, c0, nc):
+            dset, n, _ = sets[which]
+            _L.check(lib.tpe_grid_joint_factors(
+                dj.host.ctypes.data, dj.dev.data_ptr(), D, tab, dj.n_tables, dset.data_ptr(), n,
+                d_axes.data_ptr(), n_axes, axis_off.ctypes.data, axis_len.ctypes.data,
+                frow0.ctypes.data, F.data_ptr(), ldF, n_frows, c0 * chunk, nc * chunk, sp),
+                "tpe_grid_joint_factors")
+
+        whole = []
+        for which, (_dset, n, _) in enumerate(sets):
+            chunks = (n + 1 + chunk - 1) // chunk
+            F = None
+            if chunks <= per:
+                F = t.empty(n_frows * chunks * chunk, dtype=t.float64, device=eng.device)
+                factors(which, F, chunks * chunk, 0, chunks)
+            elif shared is None or shared.numel() < n_frows * per * chunk:
+                shared = t.empty(n_frows * per * chunk, dtype=t.float64, device=eng.device)
+            whole.append((F, chunks))
+
+        def score(which, blk, r0, k, sub, dst, mode):
+            dset, n, _ = sets[which]
+            F, chunks = whole[which]
+            step = chunks if F is not None else per
+            for c0 in range(0, chunks, step):
+                nc = min(step, chunks - c0)
+                if F is None:
+                    factors(which, shared, step * chunk, c0, nc)
+                _L.check(lib.tpe_grid_joint_score(
+                    (shared if F is None else F).data_ptr(), step * chunk, n_frows, c0 * chunk,
+                    nc * chunk, dset.data_ptr(), n, blk.radix.ctypes.data,
+                    blk.frow[g].ctypes.data, len(blk.radix), r0, k, sub, dst, mode,
+                    scratch.data_ptr(), 1 if c0 + nc >= chunks else 0, sp),
+                    "tpe_grid_joint_score")
+
+        for b, blk in zip(pool.blocks, plan.blocks):
+            if not blk.live[g]:
+                continue
+            for r0 in range(0, b.rows, win):
+                k = min(win, b.rows - r0)
+                at = 8 * (b.offset + r0)
+                la = above.data_ptr()
+                if parts is not None and not tree:
+                    la = parts[1].data_ptr() + at
+                score(1, blk, r0, k, None, la, _L.GRID_JOINT_STORE)
+                if parts is not None and not tree:
+                    score(0, blk, r0, k, None, parts[0].data_ptr() + at, _L.GRID_JOINT_STORE)
+                if parts is not None and tree and g > 0:
+                    # (the same call as the one added to S: the same bits)
+                    score(0, blk, r0, k, la, parts[g].data_ptr() + at, _L.GRID_JOINT_STORE)
+                score(0, blk, r0, k, la, out.data_ptr() + at,
+                      _L.GRID_JOINT_ADD if g else _L.GRID_JOINT_STORE)
+        if g == 0 and parts is not None:  # (J_root: S before anything is added to it)
+            parts[0 if tree else 2, :P].copy_(out[:P])

@@ -694,9 +694,18 @@ class GridPool(object):
     is false are excluded -- never suggested, not counted by ``n_untaken``,
     not drawn in the startup phase.  ``exclude(rows)`` does the same for rows
     given by number.  The rest of the surface is ``Pool``'s.
+
+    ``joint=True`` (any truthy value) marks the grid as carrying the plan of
+    the joint criterion (``grid_joint_plan``): ``score_configs(..., joint=True
+    | "tree")`` and ``suggest_from_pool(pool=grid, joint=...)`` then rank its
+    rows from per-axis factor tables (``joint.score_grid_device``, DESIGN
+    3.5.7), with the bits of the materialised pool and still 9 bytes per row
+    on the device.  A space without a label that is live in every
+    configuration raises ValueError here.  Without it those calls raise
+    ValueError, as they always have.
     """
 
-    def __init__(self, domain, axes, keep=None):
+    def __init__(self, domain, axes, keep=None, joint=False):
         domain = as_domain(domain)
         labels = list(domain.params)
         for lab in axes:
@@ -728,6 +737,10 @@ class GridPool(object):
             self.axis_off[j + 1] = self.axis_off[j] + v.size
         self.domain, self.labels = domain, labels
         self._enumerate()
+        self.joint = bool(joint)
+        # (False: the joint labels' plan; True: the groups' of joint="tree", made
+        # when first asked for -- not every space that has the one has the other)
+        self._joint_plans = {False: grid_joint_plan(self, False)} if self.joint else {}
         P = len(self)
         self.taken = np.zeros(P, np.uint8)
         self.excluded = None
@@ -784,6 +797,16 @@ class GridPool(object):
 
     def __len__(self):
         return int(self.block_off[-1])
+
+    def joint_plan(self, tree=False):
+        """``grid_joint_plan(self, tree)``, made once; ValueError(GRID_JOINT)
+        on a grid built without ``joint=True``."""
+        if not self.joint:
+            raise ValueError(GRID_JOINT)
+        tree = bool(tree)
+        if tree not in self._joint_plans:
+            self._joint_plans[tree] = grid_joint_plan(self, tree)
+        return self._joint_plans[tree]
 
     @property
     def n_untaken(self):
@@ -960,8 +983,152 @@ def _history_inputs(domain, trials, gamma, hist=None):
     return eng, obs
 
 
-GRID_JOINT = ("the joint criterion is not separable over the axes of a GridPool; score its rows "
-              "as a Pool (GridPool.to_pool())")
+GRID_JOINT = ("the joint criterion is not separable over the axes of a GridPool; build the grid "
+              "with GridPool(..., joint=True), which scores it from per-axis factor tables, or "
+              "score its rows as a Pool (GridPool.to_pool())")
+
+
+class GridJointPlan(object):
+    """How the joint criterion reads a grid pool (``grid_joint_plan``).
+
+    ``groups``: per group the label indices (``domain.params`` positions) its
+    mixture covers -- the joint labels alone, or with ``tree`` every group of
+    ``joint_groups(domain)``, the root group first.  ``axis_row[g]``: {label
+    index: the row of group g's factor table F that holds the label's axis
+    position 0}; a group's axes follow one another in label order and
+    ``n_frows[g]`` is their total length.  ``blocks``: one ``GridJointBlock``
+    per block of the pool."""
+    __slots__ = ("groups", "axis_row", "n_frows", "blocks")
+
+
+class GridJointBlock(object):
+    """One block of a ``GridJointPlan``.  ``radix``: the block's radices (its
+    ``_GridBlock``'s).  ``live[g]``: group g is live in the block.
+    ``joint[g]``: the positions among the block's labels of group g's labels
+    (empty where it is not live).  ``frow[g]``: per label of the block the F
+    row of its digit 0 -- ``axis_row[g]`` plus the block's ``pos`` -- or -1 for
+    a label that is not group g's and only takes part in the decode (None
+    where the group is not live)."""
+    __slots__ = ("radix", "live", "joint", "frow")
+
+
+def grid_joint_plan(pool, tree=False):
+    """The ``GridJointPlan`` of the grid pool ``pool`` for ``joint=True``, or
+    with ``tree`` for ``joint="tree"``.  Plain Python, no device.  ValueError
+    as on a ``Pool``: a space without a label live in every configuration, and
+    with ``tree`` switches that are not selected by bare choice / randint
+    labels."""
+    domain = pool.domain
+    index = {lab: j for j, lab in enumerate(pool.labels)}
+    if tree:
+        groups = [grp.labels for grp in _J.joint_groups(domain)]
+    else:
+        groups = [[m.label for m in _J.label_models(domain)]]
+    plan = GridJointPlan()
+    plan.groups = [[index[lab] for lab in labs] for labs in groups]
+    plan.axis_row, plan.n_frows = [], []
+    for cols in plan.groups:
+        rows, at = {}, 0
+        for j in cols:
+            rows[j] = at
+            at += int(pool.axes[j].size)
+        plan.axis_row.append(rows)
+        plan.n_frows.append(at)
+    plan.blocks = []
+    for b in pool.blocks:
+        where = {int(j): i for i, j in enumerate(b.cols)}
+        blk = GridJointBlock()
+        blk.radix = np.ascontiguousarray(b.radix, np.int64)
+        blk.live, blk.joint, blk.frow = [], [], []
+        for g, cols in enumerate(plan.groups):
+            inside = [j in where for j in cols]
+            # a group's labels share their activation: in or out together, and
+            # the root group (the labels live everywhere) always in
+            assert all(inside) or not any(inside), (g, cols, list(b.cols))
+            assert inside[0] or g > 0
+            blk.live.append(inside[0])
+            if not inside[0]:
+                blk.joint.append([])
+                blk.frow.append(None)
+                continue
+            frow = np.full(len(b.cols), -1, np.int64)
+            for j in cols:
+                frow[where[j]] = plan.axis_row[g][j] + int(b.pos[where[j]])
+            blk.joint.append([where[j] for j in cols])
+            blk.frow.append(frow)
+        plan.blocks.append(blk)
+    return plan
+
+
+def _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, jkw, want_terms, hist=None,
+                      parts=None):
+    """S of every row of a grid pool built with ``joint=True`` into its device
+    buffer ``S``, with the bits of the materialised pool: the groups' J from
+    per-axis factor tables (``joint.score_grid_device``); then, for
+    ``joint=True`` on a space with a ``switch``, per block the univariate terms
+    of the block's other labels added onto S in ``domain.params`` order
+    (``tpe_grid_fold_onto``; the joint labels are decoded and add nothing),
+    from one engine run over the axes of those labels alone.  Returns (engine,
+    device grid, {label: T_l} or None) as ``_score_grid``."""
+    from . import tpe as T
+    if list(domain.params) != pool.labels:
+        raise ValueError("the pool was built for another space (labels differ)")
+    tree = bool(jkw.get("tree"))
+    plan = pool.joint_plan(tree)  # (ValueError: no joint plan, or no groups)
+    if hist is None:
+        hist = T.collect_history(trials, pool.labels)
+    covered = set(j for cols in plan.groups for j in cols)
+    rest = [int(j) for j in pool.scored if int(j) not in covered]
+    eng, obs = _history_inputs(domain, trials, gamma, hist) if rest else (T.engine(), None)
+    d = pool.device(eng)
+    t, lib = eng.torch, eng.lib
+    if hist.tids.size:
+        isb, isa = T.split_masks(hist, gamma)
+    else:
+        isb = isa = np.zeros(0, bool)
+    seen = _seen_rows(eng, hist)
+    args = (eng, domain, hist, seen, isb, isa, len(pool.labels), prior_weight, lf,
+            jkw["bandwidth"], jkw["cat_smoothing"])
+    if tree:
+        prepared = [p for _grp, p in _J.prepare_tree(*args)]
+    else:
+        prepared = [_J.prepare_sets(*args)]
+    _J.score_grid_device(eng, pool, plan, prepared, d.axes, d.S, parts, tree)
+    out_off = np.full(len(pool.labels), -1, np.int64)
+    if rest:
+        works = []
+        for j in rest:
+            lab = pool.labels[j]
+            n = pool.axes[j].size
+            w = obs.work(lab, domain.specs[lab], j, n_cand=n, n_total=n)
+            w.cand_dev = (int(pool.axis_off[j]), n, d.ranges[j])
+            works.append(w)
+        res = eng.run(works, prior_weight=prior_weight, lf=lf, precision=64, outputs=True,
+                      cand_ptr=d.axes.data_ptr(), device_outputs=True, **obs.run_kwargs)
+        out_off[rest] = [r.extra["out_off"] for r in res]
+        d_bl, d_al = eng.device_output_ptrs()
+        sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+        for b in pool.blocks:
+            base = out_off[b.cols]
+            if not (base >= 0).any():
+                continue
+            off = np.ascontiguousarray(np.where(base >= 0, base + b.pos, -1))
+            _L.check(lib.tpe_grid_fold_onto(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data,
+                                            len(b.cols), 0, b.rows,
+                                            d.S.data_ptr() + 8 * b.offset, sp),
+                     "tpe_grid_fold_onto")
+    terms = None
+    if want_terms:
+        terms = {lab: np.full(pool.axes[j].size, np.nan) for j, lab in enumerate(pool.labels)}
+        if rest:
+            n = int(sum(pool.axes[j].size for j in rest))
+            bl, al = (eng._bufs[k][:8 * n].cpu().numpy().view(np.float64)
+                      for k in ("out_bl", "out_al"))
+            for j in rest:
+                o, m = int(out_off[j]), pool.axes[j].size
+                with np.errstate(invalid="ignore"):
+                    terms[pool.labels[j]] = bl[o:o + m] - al[o:o + m]
+    return eng, d, terms
 
 
 def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None):
@@ -993,8 +1160,9 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
     None, or the joint criterion's keywords (``bandwidth``, ``cat_smoothing``)
     -- S starts from J and the fold adds the other labels' terms."""
     if isinstance(pool, GridPool):
-        if joint is not None:
-            raise ValueError(GRID_JOINT)
+        if joint is not None:  # (ValueError(GRID_JOINT) on a grid without the plan)
+            return _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, joint, False,
+                                     hist, parts)[:2]
         return _score_grid(domain, trials, pool, prior_weight, gamma, lf, False, hist)[:2]
     if list(domain.params) != pool.labels:
         raise ValueError("the pool was built for another space (labels differ)")
@@ -1211,9 +1379,13 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     place of those labels' terms: S[r] starts from J[r] and the terms of the
     row's other live labels (those under a ``switch``) are added in
     ``domain.params`` order; on a flat space S = J.  ``return_terms`` then
-    gives (S, terms, J), ``terms`` NaN in the joint labels' columns.  A
-    ``GridPool`` raises ValueError (J is not separable over axes:
-    ``GridPool.to_pool()``), and so does a space without a joint label.
+    gives (S, terms, J), ``terms`` NaN in the joint labels' columns.  A space
+    without a joint label raises ValueError.  A ``GridPool`` built with
+    ``joint=True`` is scored from per-axis factor tables, every row with the
+    bits of ``GridPool.to_pool()`` (``terms`` is the grid's per-axis dict, all
+    NaN for the labels the joint covers; J is per row, as for a ``Pool``); one
+    built without it raises ValueError (J is not separable over axes:
+    ``GridPool(..., joint=True)`` or ``GridPool.to_pool()``).
 
     ``joint="tree"``: one such mixture per group of labels that share an
     activation condition (``tpe.joint_groups``; joint.py, "Groups"), each
@@ -1227,13 +1399,13 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     ValueError.  Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
-    if isinstance(pool, GridPool):
-        if jkw is not None:
-            raise ValueError(GRID_JOINT)
+    if isinstance(pool, GridPool) and jkw is None:
         eng, d, terms = _score_grid(domain, trials, pool, prior_weight, gamma,
                                     linear_forgetting, return_terms)
         S = d.S[:len(pool)].cpu().numpy()
         return (S, terms) if return_terms else S
+    if isinstance(pool, GridPool) and not pool.joint:
+        raise ValueError(GRID_JOINT)
     P = len(pool)
     parts = None
     if jkw is not None and return_terms:  # (J is read before the fold adds to it)
@@ -1244,6 +1416,15 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
                                    dtype=eng.torch.float64, device=eng.device)
         else:
             parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
+    if isinstance(pool, GridPool):
+        eng, d, terms = _score_grid_joint(domain, trials, pool, prior_weight, gamma,
+                                          linear_forgetting, jkw, return_terms, parts=parts)
+        S = d.S[:P].cpu().numpy()
+        if not return_terms:
+            return S
+        if jkw["tree"]:
+            return S, terms, np.ascontiguousarray(parts[:, :P].cpu().numpy().T)
+        return S, terms, parts[2, :P].cpu().numpy()
     eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
                            return_terms, joint=jkw, parts=parts)
     S = d.S[:P].cpu().numpy()
@@ -1299,15 +1480,16 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
 
     ``joint=True`` (``joint="tree"``) ranks by ``score_configs(joint=True,
     bandwidth=..., cat_smoothing=...)`` (``joint="tree"``): the same selection,
-    ``distinct`` and startup rules, other scores.  A ``GridPool`` raises
-    ValueError."""
+    ``distinct`` and startup rules, other scores.  A ``GridPool`` needs to
+    have been built with ``joint=True`` (else ValueError); its ``keep``,
+    ``exclude`` and taken rules are unchanged."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
-    if jkw is not None and isinstance(pool, GridPool):
+    if jkw is not None and isinstance(pool, GridPool) and not pool.joint:
         raise ValueError(GRID_JOINT)
     t0 = time.time()
     domain = as_domain(domain)

@@ -39,6 +39,8 @@ also draw the rows from that mixture (``joint_component_key``: the key of the
 draws' component pick).  ``joint="tree"`` gives the labels under a ``switch``
 joint mixtures too, one per group of labels that share an activation
 condition (``joint_groups``, ``joint_group_component_key``).
+``GridPool(..., joint=True)`` is ranked by either criterion from per-axis
+factor tables, again without its rows (``grid_joint_plan``).
 """
 from __future__ import annotations
 
@@ -791,8 +793,8 @@ def _suggest_many(requests, shard_studies=False):
 
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
-from .pool import (GridPool, Pool, SampledPool, distinct_rows, score_configs,  # noqa: E402,F401
-                   suggest_from_pool, suggest_sampled)
+from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan,  # noqa: E402,F401
+                   score_configs, suggest_from_pool, suggest_sampled)
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_groups, joint_labels,
                     score_numpy as joint_score_numpy)

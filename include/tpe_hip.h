@@ -877,6 +877,66 @@ int tpe_joint_chunk(void);
 /* host: writes sizeof(tpe_joint_label) to out[0..n); returns 1 */
 int tpe_joint_struct_sizes(int32_t* out, int n);
 
+/* ---- the joint criterion on a block of a grid pool (tpe.GridPool(joint=True)) -
+ * In tpe_joint_score's sum every joint label d adds to a_i a factor that
+ * depends on the label, the component and the label's value alone.  On a grid
+ * that value is one of the axis's values, so a set's factors form a table F of
+ * (sum of the axis lengths) x C doubles, and a row's a_i is log w_i plus one
+ * entry per joint label, added in label order: the same sequence of roundings.
+ * The results have the bits tpe_joint_score gives the materialised rows under
+ * the same prepared set.
+ *
+ * Components go in windows [comp_begin, comp_begin + n_comp): comp_begin and
+ * n_comp multiples of TPE_JOINT_CHUNK, comp_begin <= n, n_comp <= ldF, ldF
+ * even (places past the set's last component are padding).
+ *
+ * tpe_grid_joint_factors: for label d of a prepared set's n_labels labels and
+ * every value v of its axis -- axes[host_axis_off[d] + v], v in [0,
+ * host_axis_len[d]), stored values as a pool holds them -- and every component
+ * i of the window, F[(host_frow[d] + v) * ldF + (i - comp_begin)] = the factor
+ * of tpe_joint_score's sum (0.0 past the last component).  n_axes: the doubles
+ * of `axes`; n_frows: the rows of F.  One launch per label.
+ *
+ * tpe_grid_joint_score: rows [row_begin, row_begin + n_rows) of one block of a
+ * grid (tpe_grid_fold's decode: n_labels labels of host_radix[j] >= 1 digits,
+ * the last fastest).  host_frow[j] is the F row of label j's digit 0, or < 0
+ * for a label that only takes part in the decode; the joint labels add their
+ * entries in list order.  Each call scores one component window into
+ * `scratch` (tpe_grid_joint_scratch_bytes(n_rows, n) bytes, 16-byte aligned,
+ * kept by the caller from the set's first window to its last, every window
+ * given once).  `last` says that the window holds the set's last component
+ * (checked); that call also merges the row's chunks in chunk order:
+ *   v = log L(row row_begin + i) - (sub ? sub[i] : 0)
+ *   TPE_GRID_JOINT_STORE   out[i] = v
+ *   TPE_GRID_JOINT_ADD     out[i] = out[i] + v
+ * Limits: n_labels <= 128 (else TPE_E_UNSUPPORTED), n_frows < 2^31; bad
+ * arguments return TPE_E_ARG before any launch.  Asynchronous on `stream`, no
+ * allocation, no atomics; a row's bits do not depend on the windows.
+ *
+ * tpe_grid_joint_layout (host): out[0..n) <- the rows of a tile, the chunk,
+ * the components per pass, the label limit; returns the count written.
+ *
+ * tpe_grid_fold_onto: tpe_grid_fold, except that the sum starts from S[i] as
+ * it stands (S[i] = S[i] + term_0 + ...), and that a label with host_off[j] < 0
+ * is decoded but adds nothing. */
+enum { TPE_GRID_JOINT_STORE = 0, TPE_GRID_JOINT_ADD = 1 };
+int tpe_grid_joint_layout(int64_t* out, int n);
+int64_t tpe_grid_joint_scratch_bytes(int64_t n_rows, int64_t n);
+int tpe_grid_joint_factors(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                           int n_labels, const double* tables, int64_t n_tables,
+                           const double* set, int64_t n, const double* axes, int64_t n_axes,
+                           const int64_t* host_axis_off, const int64_t* host_axis_len,
+                           const int64_t* host_frow, double* F, int64_t ldF, int64_t n_frows,
+                           int64_t comp_begin, int64_t n_comp, void* stream);
+int tpe_grid_joint_score(const double* F, int64_t ldF, int64_t n_frows, int64_t comp_begin,
+                         int64_t n_comp, const double* set, int64_t n, const int64_t* host_radix,
+                         const int64_t* host_frow, int n_labels, int64_t row_begin,
+                         int64_t n_rows, const double* sub, double* out, int out_mode,
+                         void* scratch, int last, void* stream);
+int tpe_grid_fold_onto(const double* bl, const double* al, const int64_t* host_off,
+                       const int64_t* host_radix, int n_labels, int64_t row_begin, int64_t n_rows,
+                       double* S, void* stream);
+
 /* ---- rows drawn from a set's joint mixture (tpe.Pool.sample(joint=True)) -----
  * tpe_joint_sample: row g = row_base + r, r in [0, n_rows), is one draw from the
  * mixture of a prepared set (above: n trial components in row order, the prior
