@@ -194,6 +194,10 @@ _SIGNATURES = {
     "tpe_rows_compact": (_I, [_P, _I64, _P, _P, _P, _P]),
     "tpe_joint_score_rows": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64,
                                   _I64, _P, _P, _I, _P, _P]),
+    "tpe_joint_lie_scratch_bytes": (_I64, [_I64]),
+    "tpe_joint_lie_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _I64, _P, _P,
+                                 ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P, _P, _P, _P,
+                                 _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),

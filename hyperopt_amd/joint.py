@@ -140,9 +140,55 @@ lengths) x (n + 1) doubles, built once by the factor expressions above, and a
 row's ``a_i`` is ``log w_i`` plus one table entry per label, added in the same
 order -- the bits of the materialised pool (``score_grid_device``).
 
+Batches (``batch="liar"``, csrc/tpe_joint_lie.hip).  The k rows
+of one call are the k best under one score vector: picked as if each were the
+only one.  Across calls a pending trial sits in the above set and pushes the
+score down around itself; inside a call ``batch="liar"`` does the same: the
+rows are picked one at a time on the device, and each pick joins the above
+mixture as the pending trial it is about to become.  L_above is a sum of
+product kernels, so that is one more component: O(P D) per pick.
+
+  inputs       per pool row r: ``S_0[r]``, the score under ``joint=True`` (J
+               plus the folded terms of the labels under a ``switch``), bits
+               unchanged; ``A_0[r] = log L_above(r)``.  The above set as
+               prepared: n rows, sigma = ``bandwidths(models, n, bandwidth)``
+               (n == 0: ``bandwidths(models, 1, bandwidth)``) and
+               ``W = sum(forgetting_weights(n, lf)) + prior_weight``, the
+               denominator of ``log_weights``.
+  lie          pick p is a trial component of the above set whose observation
+               is row p's stored values: ``c_p(r) = log(lie_weight) + sum_d
+               log k_d(r_d)``, sequentially over the joint labels from
+               ``log(lie_weight)``, ``log k_d`` the "Factors" entry of a trial
+               component with ``mu = t(x_{p,d})`` (the category of p for a
+               discrete label) and the set's sigma_d: the same -log Z,
+               quantized mass, clipping and hit / miss tables -- what
+               ``tpe_joint_prep`` would write for a history row that held p.
+  update       ``U_0[r] = log W + A_0[r]``; after pick j ``U_j[r] = m +
+               log(exp(U_{j-1}[r] - m) + exp(c_{p_j}(r) - m))``, m the larger
+               of the two, U's term first; m = -inf gives -inf, and c = -inf
+               leaves U's bits.
+  score        ``S_j[r] = S_0[r] - (U_j[r] - U_0[r])`` where ``U_0[r]`` is
+               finite, else ``S_0[r]``.  The penalty is >= 0 and unnormalised
+               on purpose: the factor W / (W + j) is the same for every row.
+  picks        p_1 is the first untaken row of S_0 in ``tpe_pool_topk``'s order
+               (larger first, NaN before everything, equal scores to the
+               smaller row); p_{j+1} the first row of S_j among the rows that
+               are untaken, not yet picked, and pass ``distinct``'s mask where
+               one is given.  The run stops when no row is left.  k = 1 is the
+               plain result, bit for bit.
+
+On a conditional space the lie acts through the always-live labels only: two
+rows that differ under a ``switch`` alone get the same penalty.
+``liar_numpy`` is this definition in numpy; ``liar_device`` enqueues all k
+picks in one call (a pick's row is read on the device) and reads back the rows.
+
 Not built: a group conditioned on its ancestors' non-selector labels -- the
 chain-rule ratio L(ctx + g) / L(ctx), which would see a root label interact
-with a branch label.  Groups are independent mixtures.
+with a branch label.  Groups are independent mixtures.  ``batch="liar"`` under
+``joint="tree"`` (it needs log L_above per group, which ``score_tree_device``
+does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
+under the factorised criterion (its adaptive bandwidths depend on the sorted
+neighbours: no component can be added without a refit).
 """
 from __future__ import annotations
 
@@ -333,6 +379,27 @@ def _log_norm(m, mu, sigma):
         return -np.log(_cdf(m.hi, mu, sigma) - _cdf(m.lo, mu, sigma))
 
 
+def _density_terms(m, xd, mu, sigma):
+    """log k of the stored values ``xd`` (P,) of a continuous or quantized
+    label under components (mu, sigma) (C,): (P, C)."""
+    neg_log_z = _log_norm(m, mu, sigma)
+    with np.errstate(all="ignore"):
+        if m.kind == _L.JOINT_CONT:
+            z = (_fit(m, xd)[:, None] - mu[None, :]) / sigma[None, :]
+            return -0.5 * z * z - np.log(sigma * math.sqrt(2.0 * math.pi)) + neg_log_z
+        lb = xd - 0.5 * m.q
+        tu, tl = _fit(m, xd + 0.5 * m.q), _fit(m, lb)
+        if m.bounded:
+            tu, tl = np.clip(tu, m.lo, m.hi), np.clip(tl, m.lo, m.hi)
+        cu = _cdf(tu[:, None], mu[None, :], sigma[None, :])
+        cl = _cdf(tl[:, None], mu[None, :], sigma[None, :])
+        if m.is_log and not m.bounded:
+            cl = np.where((lb <= 0.0)[:, None], 0.0, cl)
+        mass = cu - cl
+        return np.where(mass > 0.0, np.log(np.where(mass > 0.0, mass, 1.0)),
+                        -np.inf) + neg_log_z
+
+
 def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing):
     """log L of the pool values ``x`` (P, D; stored values) under the set of
     history rows ``rows``."""
@@ -351,23 +418,7 @@ def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing):
         else:
             mu = np.concatenate([_fit(m, obs), [m.mu]])
             sigma = np.concatenate([np.full(n, sig[d]), [m.sigma]])
-            neg_log_z = _log_norm(m, mu, sigma)
-            with np.errstate(all="ignore"):
-                if m.kind == _L.JOINT_CONT:
-                    z = (_fit(m, xd)[:, None] - mu[None, :]) / sigma[None, :]
-                    term = -0.5 * z * z - np.log(sigma * math.sqrt(2.0 * math.pi)) + neg_log_z
-                else:
-                    lb = xd - 0.5 * m.q
-                    tu, tl = _fit(m, xd + 0.5 * m.q), _fit(m, lb)
-                    if m.bounded:
-                        tu, tl = np.clip(tu, m.lo, m.hi), np.clip(tl, m.lo, m.hi)
-                    cu = _cdf(tu[:, None], mu[None, :], sigma[None, :])
-                    cl = _cdf(tl[:, None], mu[None, :], sigma[None, :])
-                    if m.is_log and not m.bounded:
-                        cl = np.where((lb <= 0.0)[:, None], 0.0, cl)
-                    mass = cu - cl
-                    term = np.where(mass > 0.0, np.log(np.where(mass > 0.0, mass, 1.0)),
-                                    -np.inf) + neg_log_z
+            term = _density_terms(m, xd, mu, sigma)
         with np.errstate(invalid="ignore"):
             a = a + term
     with np.errstate(all="ignore"):
@@ -437,6 +488,96 @@ def _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma, lf, bandw
             # (S starts as J_root, assigned: the root group is live in every row)
             S = parts[0, :, 0].copy() if g == 0 else np.where(live, S + parts[0, :, g], S)
     return (S, parts[0], parts[1], parts[2]) if return_parts else S
+
+
+# -- batches (module doc, "Batches") ---------------------------------------------
+def lie_sigma(models, n, bandwidth):
+    """The bandwidths a lie takes: the above set's, or a set of one row's
+    where the above set is empty."""
+    return bandwidths(models, n if n else 1, bandwidth)
+
+
+def lie_log_total(n, lf, prior_weight):
+    """log W: W the denominator of ``log_weights(n, lf, prior_weight)``."""
+    return math.log(forgetting_weights(n, lf).sum() + float(prior_weight))
+
+
+def _lie_component(models, x, p, sig, smoothing, log_lie):
+    """c_p(r) for every row r of ``x`` (P, D; stored values)."""
+    c = np.full(x.shape[0], log_lie)
+    for d, m in enumerate(models):
+        xd = x[:, d]
+        if m.kind == _L.JOINT_CAT:
+            hit, miss, _prior = cat_tables(m, smoothing)
+            q = np.rint(xd).astype(np.int64) - m.offset
+            term = np.where(q == q[p], hit[q], miss[q])
+        else:
+            term = _density_terms(m, xd, np.asarray([_fit(m, xd[p])]), np.asarray([sig[d]]))[:, 0]
+        with np.errstate(invalid="ignore"):
+            c = c + term
+    return c
+
+
+def _first_row(S, gone):
+    """The first row of S outside ``gone`` in ``tpe_pool_topk``'s order, or -1."""
+    free = np.flatnonzero(~gone)
+    if not free.size:
+        return -1
+    s = S[free]
+    nan = np.isnan(s)
+    return int(free[np.argmax(nan)] if nan.any() else free[np.argmax(s)])
+
+
+def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0, S0=None, A0=None,
+               prior_weight=1.0, gamma=0.25, linear_forgetting=25, bandwidth=BANDWIDTH,
+               cat_smoothing=CAT_SMOOTHING):
+    """The batch of module doc "Batches" in numpy: (rows, S_at_pick, S_k) --
+    the picks in order (int64, at most k), the score each was picked at, and
+    the score of every row after the last pick.  ``vals``: (P, L) stored values
+    as ``Pool.vals`` holds them; ``taken`` / ``distinct``: row masks (nonzero:
+    not to be picked).  ``S0`` / ``A0``: the score and log L_above to start
+    from where the caller has them (a device's, or S with the folded terms of
+    a conditional space); else ``score_numpy``'s J and log L_above."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
+        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
+    models = label_models(domain)
+    vals = np.asarray(vals, np.float64)
+    P = vals.shape[0]
+    cols = [m.col for m in models]
+    if S0 is None or A0 is None:
+        J, _below, above = score_numpy(domain, hist, vals, None, prior_weight, gamma,
+                                       linear_forgetting, bandwidth, cat_smoothing,
+                                       return_parts=True)
+        S0 = J if S0 is None else S0
+        A0 = above if A0 is None else A0
+    S0, A0 = np.asarray(S0, np.float64), np.asarray(A0, np.float64)
+    isa = T.split_masks(hist, gamma)[1] if hist.tids.size else np.zeros(0, bool)
+    n = int(set_rows(hist, isa, cols).size)
+    sig = lie_sigma(models, n, bandwidth)
+    x = vals[:, cols]
+    gone = np.zeros(P, bool)
+    for mask in (taken, distinct):
+        if mask is not None:
+            gone |= np.asarray(mask)[:P] != 0
+    U0 = lie_log_total(n, linear_forgetting, prior_weight) + A0
+    U, S = U0.copy(), S0.copy()
+    rows, at = [], []
+    for _ in range(min(max(int(k), 0), P)):
+        p = _first_row(S, gone)
+        if p < 0:
+            break
+        rows.append(p)
+        at.append(S[p])
+        gone[p] = True
+        c = _lie_component(models, x, p, sig, cat_smoothing, math.log(lie_weight))
+        with np.errstate(all="ignore"):
+            m = np.where(c > U, c, U)
+            both = m + np.log(np.exp(U - m) + np.exp(c - m))
+            U = np.where(c == -np.inf, U, np.where(m == -np.inf, -np.inf, both))
+            S = np.where(np.isfinite(U0), S0 - (U - U0), S0)
+    return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
 
 
 # -- device path -----------------------------------------------------------------
@@ -582,6 +723,53 @@ def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoo
                                   d_vals.data_ptr(), ld, n_cols,
                                   None if comp_out is None else comp_out.data_ptr(), sp),
              "tpe_joint_sample")
+
+
+def liar_device(eng, prepared, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weight,
+                prior_weight, linear_forgetting, bandwidth, trace=False, rows_out=None):
+    """The batch of module doc "Batches" for rows [0, P) of the label-major
+    device pool ``d_vals``: the picks in order (numpy int64, at most k), all
+    enqueued by one tpe_joint_lie_picks and read back once.  ``prepared``:
+    ``prepare_sets``' result, whose above set lends its bandwidths; ``S0`` /
+    ``A0``: device vectors (>= P doubles) of the score and of log L_above;
+    ``taken`` / ``distinct``: device byte masks (``distinct`` may be None).
+    None of them is written.  ``trace``: (rows, S_at_pick, S_k) as
+    ``liar_numpy`` returns them.  ``rows_out``: a device int64 tensor of more
+    than k entries to receive the rows (and, at entry k, their count) where the
+    caller reads them on the device afterwards."""
+    t, lib = eng.torch, eng.lib
+    dj, sets, sp = prepared
+    dset, n, _ = sets[1]
+    k = min(int(k), P)
+    if k <= 0 or P == 0:
+        none = np.zeros(0, np.int64)
+        return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
+    if n:  # (the prepared set's head: log w (n + 1), then sigma and 1 / (sqrt(2) sigma))
+        sigma, sig_ptr = None, dset.data_ptr() + 8 * (n + 1)
+    else:
+        sig = lie_sigma(dj.models, 0, bandwidth)
+        some = sig > 0.0
+        r = np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)
+        sigma = t.from_numpy(np.concatenate([sig, r])).to(eng.device)
+        sig_ptr = sigma.data_ptr()
+    # the rows, then their count: one readback
+    out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
+    scratch = t.empty(lib.tpe_joint_lie_scratch_bytes(P), dtype=t.uint8, device=eng.device)
+    at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
+    S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
+    _L.check(lib.tpe_joint_lie_picks(
+        dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
+        None if dj.tables is None else dj.tables.data_ptr(), dj.n_tables, sig_ptr,
+        d_vals.data_ptr(), ld, n_cols, P, S0.data_ptr(), A0.data_ptr(),
+        lie_log_total(n, linear_forgetting, prior_weight), math.log(lie_weight),
+        taken.data_ptr(), None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
+        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
+        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp), "tpe_joint_lie_picks")
+    got = out[:k + 1].cpu().numpy()
+    rows = got[:int(got[k])].copy()
+    if not trace:
+        return rows
+    return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
 
 
 # -- groups on the device (module doc, "Groups") ---------------------------------

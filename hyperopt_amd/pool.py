@@ -57,6 +57,13 @@ mixture (csrc/tpe_joint_sample.hip); ``joint="tree"``, accepted wherever
 one per group of labels that share an activation condition (joint.py
 "Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
 interaction between labels.
+
+``batch="liar"`` (``suggest_from_pool``, ``suggest_sampled``, ``pick_batch``;
+with ``joint=True`` on a ``Pool`` / ``SampledPool``) makes the k rows of one
+call see each other: the top-k of one score is replaced by k picks made one
+after the other on the device, each joining the above mixture as the pending
+trial it is about to become (joint.py "Batches"; csrc/tpe_joint_lie.hip).  The
+host still reads back the k rows only, once.
 """
 from __future__ import annotations
 
@@ -526,10 +533,12 @@ def _rows_active(eng, domain, labels, d, P, sp):
 
 
 def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting, keep_terms,
-            hist=None, joint=None):
+            hist=None, joint=None, kept=None):
     """``Pool.sample``.  ``joint``: None, or the joint criterion's keywords
     (``_joint_kw``): the joint labels come from ``tpe_joint_sample`` and S
-    starts from J."""
+    starts from J.  ``kept`` (with ``joint``, not its tree): a dict that
+    receives the prepared sets and the born parts (log L_below, log L_above,
+    unused) as ``_joint_device`` leaves them."""
     from . import tpe as T
     domain = as_domain(domain)
     labels = list(domain.params)
@@ -614,9 +623,13 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
                                  d.S, prior_weight, linear_forgetting, joint["bandwidth"],
                                  joint["cat_smoothing"], tree=prepared)
         else:
+            parts = None
+            if kept is not None:  # (log L_above of the born rows stays, for the batch)
+                parts = t.empty((3, P), dtype=t.float64, device=eng.device)
+                kept.update(prepared=prepared, parts=parts)
             _J.score_device(eng, domain, hist, None, None, None, d.vals, P, L, P, d.S,
                             prior_weight, linear_forgetting, joint["bandwidth"],
-                            joint["cat_smoothing"], prepared=prepared)
+                            joint["cat_smoothing"], parts, prepared)
         init = 0
         if keep_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -1131,11 +1144,14 @@ def _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, jkw, want_t
     return eng, d, terms
 
 
-def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None):
+def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None,
+                  kept=None):
     """J (joint.py) of every pool row into ``d.S``.  ``parts``: a (3, P) device
     tensor for log L below, log L above and J.  With ``jkw["tree"]`` it is the
     groups' S that goes into ``d.S``, and ``parts`` is a (G, P) device tensor
-    filled with NaN for the J_g (``joint.score_tree_device``)."""
+    filled with NaN for the J_g (``joint.score_tree_device``).  ``kept``: a
+    dict that receives the prepared sets (``joint.prepare_sets``) and ``parts``
+    for a caller that goes on with them (``batch="liar"``)."""
     from . import tpe as T
     if hist.tids.size:
         isb, isa = T.split_masks(hist, gamma)
@@ -1146,19 +1162,25 @@ def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, part
                              d.vals.shape[1], len(pool.labels), len(pool), d.S, prior_weight, lf,
                              jkw["bandwidth"], jkw["cat_smoothing"], parts)
         return
-    _J.score_device(eng, domain, hist, _seen_rows(eng, hist), isb, isa, d.vals, d.vals.shape[1],
+    seen, prepared = _seen_rows(eng, hist), None
+    if kept is not None:
+        prepared = _J.prepare_sets(eng, domain, hist, seen, isb, isa, len(pool.labels),
+                                   prior_weight, lf, jkw["bandwidth"], jkw["cat_smoothing"])
+        kept.update(prepared=prepared, parts=parts)
+    _J.score_device(eng, domain, hist, seen, isb, isa, d.vals, d.vals.shape[1],
                     len(pool.labels), len(pool), d.S, prior_weight, lf, jkw["bandwidth"],
-                    jkw["cat_smoothing"], parts)
+                    jkw["cat_smoothing"], parts, prepared)
     if parts is not None:  # (row 2: J itself, before the fold adds to S)
         parts[2, :len(pool)].copy_(d.S[:len(pool)])
 
 
 def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None,
-                  joint=None, parts=None):
+                  joint=None, parts=None, kept=None):
     """S of every pool row into the pool's device buffer ``S`` (and the
     per-label terms into ``terms``); returns (engine, device pool).  ``joint``:
     None, or the joint criterion's keywords (``bandwidth``, ``cat_smoothing``)
-    -- S starts from J and the fold adds the other labels' terms."""
+    -- S starts from J and the fold adds the other labels' terms.  ``parts`` /
+    ``kept``: ``_joint_device``'s."""
     if isinstance(pool, GridPool):
         if joint is not None:  # (ValueError(GRID_JOINT) on a grid without the plan)
             return _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, joint, False,
@@ -1189,7 +1211,7 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
     per = max(1, CHUNK_ELEMS // P)
     init = 1
     if joint is not None:
-        _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, joint, hist, parts)
+        _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, joint, hist, parts, kept)
         todo, init = rest, 0
         if want_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -1360,6 +1382,78 @@ def _joint_cols(domain, jkw):
     return [m.col for m in _J.label_models(domain)]
 
 
+BATCH_LIAR = ("batch='liar' is supported with joint=True on a Pool or a SampledPool "
+              "(suggest_from_pool, suggest_sampled, pick_batch)")
+
+
+def _batch_kw(batch, lie_weight, jkw, pool=None):
+    """None for ``batch=None``; for ``batch="liar"`` the lie's weight, after
+    the checks: ValueError on any other string, on a ``lie_weight`` that is not
+    a finite number > 0, and on what the batch is not built for (joint.py,
+    "Not built")."""
+    if batch is None:
+        return None
+    if batch != "liar":
+        raise ValueError("batch=%r: None or 'liar'" % (batch,))
+    if not lie_weight > 0.0 or not math.isfinite(lie_weight):
+        raise ValueError("lie_weight=%r must be a finite number > 0" % (lie_weight,))
+    if jkw is None:
+        raise ValueError(BATCH_LIAR + "; the factorised criterion (joint=False) has no such "
+                         "update: its bandwidths depend on the sorted neighbours")
+    if jkw["tree"]:
+        raise ValueError(BATCH_LIAR + "; joint='tree' keeps no log L_above per group")
+    if isinstance(pool, GridPool):
+        raise ValueError(BATCH_LIAR + "; a GridPool has no row values to lie with "
+                         "(GridPool.to_pool())")
+    return float(lie_weight)
+
+
+def _liar_device(eng, d, P, k, mask, lie_weight, kept, prior_weight, lf, jkw, trace=False):
+    """``_topk_device`` for ``batch="liar"``: the rows of ``joint.liar_device``
+    on d.S and the log L_above that ``kept`` holds (``_joint_device``); ``mask``:
+    ``distinct``'s device mask or None.  The rows stay in d.rows_out."""
+    t = eng.torch
+    k = min(int(k), P)
+    if d.rows_out is None or d.rows_out.numel() < k + 1:
+        # (with its count, as _topk_device allocates the pair: the count here is
+        # entry k of the rows, read back with them)
+        d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
+        d.count = t.zeros(1, dtype=t.int64, device=eng.device)
+    return _J.liar_device(eng, kept["prepared"], d.vals, d.vals.shape[1], d.vals.shape[0], P, d.S,
+                          kept["parts"][1], d.taken, mask, k, lie_weight, prior_weight, lf,
+                          jkw["bandwidth"], trace, d.rows_out)
+
+
+def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_weight=1.0,
+               prior_weight=1.0, gamma=0.25, linear_forgetting=25, bandwidth=_J.BANDWIDTH,
+               cat_smoothing=_J.CAT_SMOOTHING):
+    """The rows ``suggest_from_pool(joint=True, batch="liar")`` would hand out
+    for k ids past the startup phase, in pick order (numpy int64; joint.py,
+    "Batches"), without marking anything taken.  ``return_trace``: (rows,
+    S_at_pick, S_k) -- the score each row was picked at and every row's score
+    after the last pick.  A ``GridPool`` raises ValueError."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    jkw = _joint_kw(True, bandwidth, cat_smoothing)
+    lie = _batch_kw("liar", lie_weight, jkw, pool)
+    if list(domain.params) != pool.labels:
+        raise ValueError("the pool was built for another space (labels differ)")
+    P = len(pool)
+    eng = T.engine()
+    hist = T.collect_history(trials, pool.labels)
+    kept = {}
+    parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
+    eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
+                           hist=hist, joint=jkw, parts=parts, kept=kept)
+    if P == 0:
+        none = np.zeros(0, np.int64)
+        return (none, np.zeros(0), np.zeros(0)) if return_trace else none
+    if distinct:
+        _distinct_device(eng, pool, d, hist)
+    return _liar_device(eng, d, P, k, d.mask if distinct else None, lie, kept, prior_weight,
+                        linear_forgetting, jkw, return_trace)
+
+
 def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
                   return_terms=False, joint=False, bandwidth=_J.BANDWIDTH,
                   cat_smoothing=_J.CAT_SMOOTHING):
@@ -1458,7 +1552,7 @@ def startup_rows(pool, seed, k, stale=None):
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0,
                       n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True,
                       distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
-                      cat_smoothing=_J.CAT_SMOOTHING):
+                      cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0):
     """An ``algo`` for fmin (``partial(tpe.suggest_from_pool, pool=pool)``): one
     document per id, the first id the best untaken row of ``pool`` by
     ``score_configs``, the second the next best, and so on -- larger S first,
@@ -1482,13 +1576,23 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     bandwidth=..., cat_smoothing=...)`` (``joint="tree"``): the same selection,
     ``distinct`` and startup rules, other scores.  A ``GridPool`` needs to
     have been built with ``joint=True`` (else ValueError); its ``keep``,
-    ``exclude`` and taken rules are unchanged."""
+    ``exclude`` and taken rules are unchanged.
+
+    ``batch="liar"`` (with ``joint=True`` on a ``Pool`` / ``SampledPool``;
+    anything else raises ValueError): the ids' rows are picked one at a time on
+    the device, and every pick joins the above mixture with weight
+    ``lie_weight`` as the pending trial it is about to become, so the next
+    pick keeps away from it (joint.py, "Batches") -- a batch for parallel
+    evaluation that does not crowd one mode.  The first document is the one
+    ``batch=None`` gives; the startup phase, ``distinct`` and the taken rules
+    are unchanged.  ``batch=None``: the k best rows of one score."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
+    lie = _batch_kw(batch, lie_weight, jkw, pool)
     if jkw is not None and isinstance(pool, GridPool) and not pool.joint:
         raise ValueError(GRID_JOINT)
     t0 = time.time()
@@ -1507,12 +1611,21 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
             _distinct_device(eng, pool, d, hist)
             stale = d.first[:len(pool)].cpu().numpy() != np.arange(len(pool))
         rows = startup_rows(pool, seed, k, stale)
-    else:
+    elif lie is None:
         eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
                                False, hist=hist, joint=jkw)
         if distinct:
             _distinct_device(eng, pool, d, hist)
         rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
+    else:
+        eng, kept = T.engine(), {}
+        parts = eng.torch.empty((3, len(pool)), dtype=eng.torch.float64, device=eng.device)
+        eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
+                               False, hist=hist, joint=jkw, parts=parts, kept=kept)
+        if distinct:
+            _distinct_device(eng, pool, d, hist)
+        rows = _liar_device(eng, d, len(pool), k, d.mask if distinct else None, lie, kept,
+                            prior_weight, linear_forgetting, jkw)
     rows = [int(r) for r in rows]
     pool.mark_taken(rows)
     ids = list(new_ids)[:len(rows)]
@@ -1572,7 +1685,8 @@ def take_rows(pool, rows_dev, k):
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
                     verbose=True, distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
-                    cat_smoothing=_J.CAT_SMOOTHING, draw="factorised"):
+                    cat_smoothing=_J.CAT_SMOOTHING, draw="factorised", batch=None,
+                    lie_weight=1.0):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -1620,7 +1734,14 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     are the same for both.  ``joint="tree"`` is the same with the groups'
     criterion (``score_configs(joint="tree")``) and, under ``draw="joint"``,
     ``Pool.sample(joint="tree")``: the labels under a ``switch`` are drawn
-    jointly too."""
+    jointly too.
+
+    ``batch="liar"`` (needs ``joint=True``; ValueError otherwise, and for any
+    other string): the documents' rows are picked one at a time, each pick
+    joining the above mixture with weight ``lie_weight`` (joint.py,
+    "Batches"; ``suggest_from_pool``).  log L_above is the one the scoring
+    leaves: the pool's born parts under ``draw="joint"``.  ``keep``,
+    ``distinct`` and the startup phase are unchanged."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
@@ -1631,6 +1752,8 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
                          "joint=True")
     domain = as_domain(domain)
     jkw = _joint_kw(joint, bandwidth, cat_smoothing)
+    lie = _batch_kw(batch, lie_weight, jkw)
+    kept = None if lie is None else {}
     if jkw is not None:
         _joint_cols(domain, jkw)  # (ValueError on a space without a joint label)
     labels = list(domain.params)
@@ -1655,7 +1778,7 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         configs = [_stored_config(domain, labels, vals[r], active[r]) for r in rows]
         return trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
     pool = _sample(domain, trials, seed, n, prior_weight, gamma, linear_forgetting, False,
-                   hist=hist, joint=jkw if draw == "joint" else None)
+                   hist=hist, joint=jkw if draw == "joint" else None, kept=kept)
     if keep is not None and len(pool):
         pool.mark_taken(np.flatnonzero(~_keep_rows(keep, labels, pool.vals, len(pool))))
     k = min(len(new_ids), pool.n_untaken)
@@ -1663,12 +1786,19 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         return []
     eng = T.engine()
     if jkw is not None and draw != "joint":  # S: the joint criterion in place of the born scores
+        parts = None
+        if lie is not None:
+            parts = eng.torch.empty((3, len(pool)), dtype=eng.torch.float64, device=eng.device)
         _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
-                      hist=hist, joint=jkw)
+                      hist=hist, joint=jkw, parts=parts, kept=kept)
     d = _mirror(pool, eng)
     if distinct:
         _distinct_device(eng, pool, d, hist)
-    rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
+    if lie is None:
+        rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
+    else:
+        rows = _liar_device(eng, d, len(pool), k, d.mask if distinct else None, lie, kept,
+                            prior_weight, linear_forgetting, jkw)
     if not len(rows):
         return []
     vals, active = take_rows(pool, d.rows_out, len(rows))

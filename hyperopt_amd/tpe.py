@@ -41,6 +41,10 @@ joint mixtures too, one per group of labels that share an activation
 condition (``joint_groups``, ``joint_group_component_key``).
 ``GridPool(..., joint=True)`` is ranked by either criterion from per-axis
 factor tables, again without its rows (``grid_joint_plan``).
+``batch="liar"`` (with ``joint=True``) picks the k rows of a call one at a
+time on the device, each pick joining the above mixture as the pending trial
+it is about to become, so a batch for parallel evaluation spreads out
+(``pick_batch``: the rows alone; ``joint_liar_numpy``).
 """
 from __future__ import annotations
 
@@ -794,7 +798,7 @@ def _suggest_many(requests, shard_studies=False):
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan,  # noqa: E402,F401
-                   score_configs, suggest_from_pool, suggest_sampled)
+                   pick_batch, score_configs, suggest_from_pool, suggest_sampled)
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_groups, joint_labels,
-                    score_numpy as joint_score_numpy)
+                    liar_numpy as joint_liar_numpy, score_numpy as joint_score_numpy)

@@ -1030,6 +1030,50 @@ int tpe_joint_score_rows(const tpe_joint_label* host_labels, const tpe_joint_lab
                          int64_t max_rows, const double* sub, double* out, int out_mode,
                          void* scratch, void* stream);
 
+/* ---- a batch picked one at a time under the joint criterion -------------------
+ * (tpe.suggest_from_pool(joint=True, batch="liar"); hyperopt_amd/joint.py,
+ * "Batches".)  Pick j enters the above mixture as one more trial component
+ * whose observation is its own row p of the pool -- mu and the constant as
+ * tpe_joint_prep forms them, the factors as tpe_joint_score's -- of weight
+ * exp(log_lie):
+ *   c_p(r) = log_lie + sum_d log k_d(r_d)              (d in list order)
+ *   U_0[r] = log_w + A0[r]
+ *   U_j[r] = m + log(exp(U_{j-1}[r] - m) + exp(c_p(r) - m)), m = max of the two
+ *            (c_p(r) = -inf leaves U's bits; m = -inf gives -inf)
+ *   S_j[r] = S0[r] - (U_j[r] - U_0[r]) where U_0[r] is finite, else S0[r].
+ * Pick j + 1 is the first row of S_j in tpe_pool_topk's order (larger first, NaN
+ * before everything, equal scores to the smaller row) among the rows r with
+ * taken[r] == 0, (distinct ? distinct[r] == 0 : true) and not picked before;
+ * the run stops when no row is left.
+ *
+ * labels / tables as tpe_joint_score takes them.  sigma (device): the above
+ * set's D bandwidths, then the D values 1 / (sqrt(2) sigma) -- a prepared set's
+ * head from element n + 1 on (may be NULL when every label is discrete).
+ * vals, ld, n_cols: the label-major pool, rows [0, n_rows).  S0, A0 (n_rows
+ * doubles), taken and distinct (n_rows bytes; distinct may be NULL) are read
+ * only.  out_rows: k device int64, entries [0, *out_count) written in pick
+ * order; out_count: device int64.  S_at_pick (k doubles, optional): entry j =
+ * S_j of pick j + 1, the score it was picked at.  S_k (n_rows doubles,
+ * optional): the score after the last pick made.  scratch:
+ * tpe_joint_lie_scratch_bytes(n_rows) bytes (-1: bad arguments), 16-byte
+ * aligned; it holds the working copies.  k > n_rows counts as n_rows.
+ *
+ * All picks are enqueued by the one call: a pick's row is read on the device,
+ * the host learns nothing before it reads out_count / out_rows.  A row's bits
+ * depend on the row, the labels and the pick sequence only -- not on n_rows,
+ * the block a row falls in or block scheduling; no floating-point atomics.
+ * Limits as tpe_joint_score (TPE_E_UNSUPPORTED); bad arguments return TPE_E_ARG
+ * before any launch; k <= 0 or n_rows == 0 writes the count 0 (and S0 to S_k
+ * where given).  Asynchronous on `stream`, no allocation. */
+int64_t tpe_joint_lie_scratch_bytes(int64_t n_rows);
+int tpe_joint_lie_picks(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                        int n_labels, const double* tables, int64_t n_tables,
+                        const double* sigma, const double* vals, int64_t ld, int n_cols,
+                        int64_t n_rows, const double* S0, const double* A0, double log_w,
+                        double log_lie, const uint8_t* taken, const uint8_t* distinct,
+                        int64_t k, int64_t* out_rows, int64_t* out_count, double* S_at_pick,
+                        double* S_k, void* scratch, void* stream);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
