@@ -353,6 +353,13 @@ def set_rows(hist, mask, cols):
     return np.flatnonzero(mask & np.asarray(hist.active, bool)[:, cols].all(1))
 
 
+def split_sets(hist, gamma):
+    """The below / above row masks of ``hist`` (``tpe.split_masks``); two empty
+    masks for an empty history."""
+    from . import tpe as T
+    return T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+
+
 def bandwidths(models, n, bandwidth):
     """sigma of the trial components of a set of n rows, per joint label (0
     for a discrete label, and for n == 0: there is no such component)."""
@@ -445,7 +452,6 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
     where ``vals`` is not NaN) says where a group is live.  ``return_parts``:
     (S, J, log L_below, log L_above), the last three (P, G) matrices, NaN
     where the group is not live."""
-    from . import tpe as T
     domain = as_domain(domain)
     if tree:
         return _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma,
@@ -455,7 +461,7 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
     cols = [m.col for m in models]
     if active is not None and not np.asarray(active, bool)[:, cols].all():
         raise ValueError("a joint label is not active in some row")
-    isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+    isb, isa = split_sets(hist, gamma)
     x = vals[:, cols]
     out = [_set_log_l(models, hist, set_rows(hist, mask, cols), x, linear_forgetting,
                       prior_weight, bandwidth, cat_smoothing) for mask in (isb, isa)]
@@ -466,12 +472,11 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
 
 def _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma, lf, bandwidth, smoothing,
                       return_parts):
-    from . import tpe as T
     groups = joint_groups(domain)
     vals = np.asarray(vals, np.float64)
     active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
     P, G = vals.shape[0], len(groups)
-    isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
+    isb, isa = split_sets(hist, gamma)
     parts = np.full((3, P, G), np.nan)  # J, log L_below, log L_above
     S = None
     for g, grp in enumerate(groups):
@@ -538,7 +543,6 @@ def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0,
     not to be picked).  ``S0`` / ``A0``: the score and log L_above to start
     from where the caller has them (a device's, or S with the folded terms of
     a conditional space); else ``score_numpy``'s J and log L_above."""
-    from . import tpe as T
     domain = as_domain(domain)
     if not lie_weight > 0.0 or not np.isfinite(lie_weight):
         raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
@@ -553,8 +557,7 @@ def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0,
         S0 = J if S0 is None else S0
         A0 = above if A0 is None else A0
     S0, A0 = np.asarray(S0, np.float64), np.asarray(A0, np.float64)
-    isa = T.split_masks(hist, gamma)[1] if hist.tids.size else np.zeros(0, bool)
-    n = int(set_rows(hist, isa, cols).size)
+    n = int(set_rows(hist, split_sets(hist, gamma)[1], cols).size)
     sig = lie_sigma(models, n, bandwidth)
     x = vals[:, cols]
     gone = np.zeros(P, bool)
@@ -613,9 +616,14 @@ def _device_labels(eng, models, smoothing):
     return dj
 
 
+def stream_ptr(eng):
+    """The current stream of ``eng``'s device as the C entries take it."""
+    return ctypes.c_void_p(eng.torch.cuda.current_stream(eng.device).cuda_stream)
+
+
 def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp):
-    """One set on the device: (set tensor, n).  ``seen``: pool._seen_rows'
-    view of the history; ``rows``: the set's rows as positions of that view."""
+    """One set on the device: (set tensor, n, row list).  ``seen``: the history
+    on the device (``fit``); ``rows``: the set's rows as rows of that mirror."""
     t, lib = eng.torch, eng.lib
     _alive, sv, sa, sld, _srows, _n = seen
     D, n = len(dj.models), int(rows.size)
@@ -634,42 +642,60 @@ def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp
     return dset, n, drows
 
 
-def prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight, linear_forgetting,
-                 bandwidth, cat_smoothing, group=None):
-    """The space's label records and both sets on the device: (dj, [below,
-    above], stream pointer), a set as ``_prepare_set`` returns it.  ``seen``:
-    ``pool._seen_rows(eng, hist)``; ``n_cols``: the columns of the history
-    (and of the pool: both are in ``domain.params`` order); ``group``: the
-    labels of one group of ``joint_groups`` in place of the joint labels."""
-    t = eng.torch
-    models = label_models(domain, group)
-    dj = _device_labels(eng, models, cat_smoothing)
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
-    cols = [m.col for m in models]
+class JointFit(object):
+    """One mixture pair fitted to a history, on the device (``fit``): the
+    engine, the label records ``dj``, ``sets`` = [below, above] as
+    ``_prepare_set`` returns them, the stream pointer ``sp``, ``group`` (the
+    labels of its group of ``joint_groups``; None: the joint labels) and the
+    settings it was made with."""
+    __slots__ = ("eng", "dj", "sets", "sp", "group", "prior_weight", "linear_forgetting",
+                 "bandwidth", "cat_smoothing")
+
+
+def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting, bandwidth,
+        cat_smoothing, tree=False):
+    """The joint model of the history ``hist`` under the split of ``gamma``:
+    [JointFit] -- the joint labels' alone, or with ``tree`` one per group of
+    ``joint_groups(domain)``, the root group first.  Per fit the label records
+    go up, then both sets are built there (tpe_joint_prep).
+
+    ``seen``: the history on the device, the tuple (keep-alive tensors, values
+    pointer, activity pointer, leading dimension, rows pointer or None, T) --
+    label-major fp64 values and activity bytes in ``domain.params`` column
+    order, and T the number of history rows; where the two are a longer
+    mirror of which ``hist`` is a view, the int32 device list of its rows
+    (``hist.rows``), else None: position t is history row t.  ``n_cols``: the
+    columns of the history (and of the pool: the same order)."""
+    isb, isa = split_sets(hist, gamma)
     view = hist.rows if (seen[4] is not None) else None  # (positions -> rows of the mirror)
-    sets = []
-    for mask in (isb, isa):
-        rows = set_rows(hist, mask, cols)
-        if view is not None:
-            rows = np.asarray(view)[rows]
-        sets.append(_prepare_set(eng, dj, seen, n_cols, rows, linear_forgetting, prior_weight,
-                                 bandwidth, sp))
-    return dj, sets, sp
+    fits = []
+    for group in ([grp.labels for grp in joint_groups(domain)] if tree else [None]):
+        f = JointFit()
+        f.eng, f.group = eng, group
+        f.prior_weight, f.linear_forgetting = prior_weight, linear_forgetting
+        f.bandwidth, f.cat_smoothing = bandwidth, cat_smoothing
+        models = label_models(domain, group)
+        f.dj = _device_labels(eng, models, cat_smoothing)
+        f.sp = stream_ptr(eng)
+        cols = [m.col for m in models]
+        f.sets = []
+        for mask in (isb, isa):
+            rows = set_rows(hist, mask, cols)
+            if view is not None:
+                rows = np.asarray(view)[rows]
+            f.sets.append(_prepare_set(eng, f.dj, seen, n_cols, rows, linear_forgetting,
+                                       prior_weight, bandwidth, f.sp))
+        fits.append(f)
+    return fits
 
 
-def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, prior_weight,
-                 linear_forgetting, bandwidth, cat_smoothing, parts=None, prepared=None):
+def score_device(fit, d_vals, ld, n_cols, P, out, parts=None):
     """J of rows [0, P) of the label-major device pool ``d_vals`` (leading
-    dimension ``ld``, ``n_cols`` columns) into the device vector ``out``.
-    ``seen``: ``pool._seen_rows(eng, hist)``; ``parts``: a device tensor whose
-    rows 0 and 1 (>= P long) receive log L_below and log L_above;
-    ``prepared``: ``prepare_sets``' result for the same arguments, where the
-    caller has made it already."""
+    dimension ``ld``, ``n_cols`` columns) under ``fit`` into the device vector
+    ``out``.  ``parts``: a device tensor whose rows 0 and 1 (>= P long) receive
+    log L_below and log L_above."""
+    eng, dj, sets, sp = fit.eng, fit.dj, fit.sets, fit.sp
     t, lib = eng.torch, eng.lib
-    if prepared is None:
-        prepared = prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
-                                linear_forgetting, bandwidth, cat_smoothing)
-    dj, sets, sp = prepared
     D = len(dj.models)
     tab = None if dj.tables is None else dj.tables.data_ptr()
     win = min(max(P, 1), ROWS_PER_CALL)
@@ -696,20 +722,19 @@ def score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, 
         score(0, r0, k, la, out.data_ptr() + 8 * r0)
 
 
-def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals, ld,
-                  n_cols, row_base, n_rows, comp_out=None, comp_key=None):
+def sample_device(fit, seed, d_vals, ld, n_cols, row_base, n_rows, comp_out=None, comp_key=None):
     """Rows [row_base, row_base + n_rows) of the joint draw (module doc) from
-    the below set of ``prepared`` (``prepare_sets``) into rows [0, n_rows) of
-    the joint labels' columns of the label-major device block ``d_vals``
-    (tpe_joint_sample).  ``comp_out``: a device int32 tensor for the rows'
-    components; ``comp_key``: the component pick's key where it is not
-    ``component_key(seed)`` (a group that is not the root's).  Three small
-    uploads: the component cdf, the discrete labels' cdf table and the keys."""
+    the below set of ``fit`` into rows [0, n_rows) of its labels' columns of
+    the label-major device block ``d_vals`` (tpe_joint_sample).  ``comp_out``:
+    a device int32 tensor for the rows' components; ``comp_key``: the component
+    pick's key where it is not ``component_key(seed)`` (a group that is not
+    the root's).  Three small uploads: the component cdf, the discrete labels'
+    cdf table and the keys."""
     from . import tpe as T
+    eng, dj, sp = fit.eng, fit.dj, fit.sp
     t, lib = eng.torch, eng.lib
-    dj, sets, sp = prepared
-    dset, n, _ = sets[0]
-    cdf = t.from_numpy(sample_cdf(n, linear_forgetting, prior_weight)).to(eng.device)
+    dset, n, _ = fit.sets[0]
+    cdf = t.from_numpy(sample_cdf(n, fit.linear_forgetting, fit.prior_weight)).to(eng.device)
     cats = [np.cumsum(m.p) for m in dj.models if m.kind == _L.JOINT_CAT]
     cat_cdf = t.from_numpy(np.concatenate(cats)).to(eng.device) if cats else None
     keys = np.asarray([T.label_key(seed, m.label) for m in dj.models] +
@@ -719,27 +744,27 @@ def sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoo
                                   dset.data_ptr(), n, cdf.data_ptr(),
                                   None if cat_cdf is None else cat_cdf.data_ptr(),
                                   0 if cat_cdf is None else cat_cdf.numel(), d_keys.data_ptr(),
-                                  1.0 + float(cat_smoothing), row_base, n_rows,
+                                  1.0 + float(fit.cat_smoothing), row_base, n_rows,
                                   d_vals.data_ptr(), ld, n_cols,
                                   None if comp_out is None else comp_out.data_ptr(), sp),
              "tpe_joint_sample")
 
 
-def liar_device(eng, prepared, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weight,
-                prior_weight, linear_forgetting, bandwidth, trace=False, rows_out=None):
+def liar_device(fit, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weight, trace=False,
+                rows_out=None):
     """The batch of module doc "Batches" for rows [0, P) of the label-major
     device pool ``d_vals``: the picks in order (numpy int64, at most k), all
-    enqueued by one tpe_joint_lie_picks and read back once.  ``prepared``:
-    ``prepare_sets``' result, whose above set lends its bandwidths; ``S0`` /
+    enqueued by one tpe_joint_lie_picks and read back once.  ``fit``: the
+    joint labels' fit, whose above set lends its bandwidths; ``S0`` /
     ``A0``: device vectors (>= P doubles) of the score and of log L_above;
     ``taken`` / ``distinct``: device byte masks (``distinct`` may be None).
     None of them is written.  ``trace``: (rows, S_at_pick, S_k) as
     ``liar_numpy`` returns them.  ``rows_out``: a device int64 tensor of more
     than k entries to receive the rows (and, at entry k, their count) where the
     caller reads them on the device afterwards."""
+    eng, dj, sp = fit.eng, fit.dj, fit.sp
     t, lib = eng.torch, eng.lib
-    dj, sets, sp = prepared
-    dset, n, _ = sets[1]
+    dset, n, _ = fit.sets[1]
     k = min(int(k), P)
     if k <= 0 or P == 0:
         none = np.zeros(0, np.int64)
@@ -747,7 +772,7 @@ def liar_device(eng, prepared, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k
     if n:  # (the prepared set's head: log w (n + 1), then sigma and 1 / (sqrt(2) sigma))
         sigma, sig_ptr = None, dset.data_ptr() + 8 * (n + 1)
     else:
-        sig = lie_sigma(dj.models, 0, bandwidth)
+        sig = lie_sigma(dj.models, 0, fit.bandwidth)
         some = sig > 0.0
         r = np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)
         sigma = t.from_numpy(np.concatenate([sig, r])).to(eng.device)
@@ -761,7 +786,7 @@ def liar_device(eng, prepared, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k
         dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
         None if dj.tables is None else dj.tables.data_ptr(), dj.n_tables, sig_ptr,
         d_vals.data_ptr(), ld, n_cols, P, S0.data_ptr(), A0.data_ptr(),
-        lie_log_total(n, linear_forgetting, prior_weight), math.log(lie_weight),
+        lie_log_total(n, fit.linear_forgetting, fit.prior_weight), math.log(lie_weight),
         taken.data_ptr(), None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
         out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
         None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp), "tpe_joint_lie_picks")
@@ -773,62 +798,45 @@ def liar_device(eng, prepared, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k
 
 
 # -- groups on the device (module doc, "Groups") ---------------------------------
-def prepare_tree(eng, domain, hist, seen, isb, isa, n_cols, prior_weight, linear_forgetting,
-                 bandwidth, cat_smoothing):
-    """``prepare_sets`` per group of ``joint_groups(domain)``: [(group,
-    prepared)], the root group (the joint labels) first."""
-    return [(grp, prepare_sets(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
-                               linear_forgetting, bandwidth, cat_smoothing, group=grp.labels))
-            for grp in joint_groups(domain)]
+def sample_tree_device(fits, seed, d_vals, ld, n_cols, row_base, n_rows):
+    """``sample_device`` per fit of ``fits`` (``fit(..., tree=True)``): every
+    group's columns for all the rows, the root group under
+    ``component_key(seed)``, the others under their ``group_component_key``."""
+    for g, f in enumerate(fits):
+        key = None if g == 0 else group_component_key(seed, f.group[0])
+        sample_device(f, seed, d_vals, ld, n_cols, row_base, n_rows, comp_key=key)
 
 
-def sample_tree_device(eng, tree, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals, ld,
-                       n_cols, row_base, n_rows):
-    """``sample_device`` per group of ``tree`` (``prepare_tree``): every group's
-    columns for all the rows, the root group under ``component_key(seed)``,
-    the others under their ``group_component_key``."""
-    for g, (grp, prepared) in enumerate(tree):
-        key = None if g == 0 else group_component_key(seed, grp.labels[0])
-        sample_device(eng, prepared, seed, prior_weight, linear_forgetting, cat_smoothing, d_vals,
-                      ld, n_cols, row_base, n_rows, comp_key=key)
-
-
-def score_tree_device(eng, domain, hist, seen, isb, isa, d_vals, d_active, ld, n_cols, P, out,
-                      prior_weight, linear_forgetting, bandwidth, cat_smoothing, parts=None,
-                      tree=None):
+def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
     """S of ``joint="tree"`` for rows [0, P) of the label-major device pool
-    ``d_vals`` / ``d_active`` (bytes; leading dimension ``ld``) into the device
-    vector ``out``.  The root group goes through ``score_device`` (out = J_root:
-    the flat case is that code alone).  Every other group, in order: both sets
-    prepared from the group's rows of the history, the pool's rows in which the
-    group is live compacted once into a device list (tpe_rows_compact on the
-    first label's activity: a group's labels share theirs), then per window of
+    ``d_vals`` / ``d_active`` (bytes; leading dimension ``ld``) under ``fits``
+    (``fit(..., tree=True)``) into the device vector ``out``.  The root group
+    goes through ``score_device`` (out = J_root: the flat case is that code
+    alone).  Every other group, in order: the pool's rows in which the group is
+    live compacted once into a device list (tpe_rows_compact on the first
+    label's activity: a group's labels share theirs), then per window of
     ``ROWS_PER_CALL`` list positions log L_above into a dense temporary and
     log L_below minus it added to ``out`` at the listed rows
     (tpe_joint_score_rows).  The list's length never comes to the host.
     ``parts``: a (G, >= P) device tensor filled with NaN; row g receives J_g at
-    the rows in which group g is live.  ``tree``: ``prepare_tree``'s result for
-    the same arguments, where the caller has made it already."""
+    the rows in which group g is live."""
+    eng = fits[0].eng
     t, lib = eng.torch, eng.lib
-    if tree is None:
-        tree = prepare_tree(eng, domain, hist, seen, isb, isa, n_cols, prior_weight,
-                            linear_forgetting, bandwidth, cat_smoothing)
-    score_device(eng, domain, hist, seen, isb, isa, d_vals, ld, n_cols, P, out, prior_weight,
-                 linear_forgetting, bandwidth, cat_smoothing, prepared=tree[0][1])
+    score_device(fits[0], d_vals, ld, n_cols, P, out)
     if parts is not None:
         parts[0, :P].copy_(out[:P])
-    if len(tree) == 1 or P == 0:
+    if len(fits) == 1 or P == 0:
         return
     win = min(P, ROWS_PER_CALL)
-    need = max(lib.tpe_joint_scratch_bytes(win, n) for _, (_, sets, _) in tree[1:]
-               for _, n, _ in sets)
+    need = max(lib.tpe_joint_scratch_bytes(win, n) for f in fits[1:] for _, n, _ in f.sets)
     scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
     above = t.empty(win, dtype=t.float64, device=eng.device)
     rows = t.empty(P, dtype=t.int64, device=eng.device)
     count = t.empty(1, dtype=t.int64, device=eng.device)
     cscratch = t.empty(lib.tpe_rows_compact_scratch_bytes(P), dtype=t.uint8, device=eng.device)
     both = _L.JOINT_OUT_SCATTER | _L.JOINT_OUT_ADD
-    for g, (grp, (dj, sets, sp)) in enumerate(tree[1:], 1):
+    for g, f in enumerate(fits[1:], 1):
+        dj, sets, sp = f.dj, f.sets, f.sp
         D = len(dj.models)
         tab = None if dj.tables is None else dj.tables.data_ptr()
         flags = d_active.data_ptr() + dj.models[0].col * ld
@@ -851,15 +859,14 @@ def score_tree_device(eng, domain, hist, seen, isb, isa, d_vals, d_active, ld, n
 
 
 # -- a grid pool: factor tables per axis ---------------------------
-def score_grid_device(eng, pool, plan, prepared, d_axes, out, parts=None, tree=False):
+def score_grid_device(fits, pool, plan, d_axes, out, parts=None, tree=False):
     """The joint criterion of every row of the grid pool ``pool`` into the
     device vector ``out`` (>= len(pool) doubles), with the bits
     ``score_device`` / ``score_tree_device`` give the materialised pool.
 
-    ``plan``: ``pool.grid_joint_plan(pool, tree)``; ``prepared``: one
-    ``prepare_sets`` result per group of the plan (``prepare_tree``'s, or the
-    joint labels' alone); ``d_axes``: the pool's concatenated axes on the
-    device.  ``parts`` as the pool path takes it: a (3, >= P) device tensor
+    ``fits``: ``fit``'s result, one per group of the plan; ``plan``:
+    ``pool.grid_joint_plan(pool, tree)``; ``d_axes``: the pool's concatenated
+    axes on the device.  ``parts`` as the pool path takes it: a (3, >= P) tensor
     (log L_below, log L_above, J), or with ``tree`` a (G, >= P) tensor filled
     with NaN whose row g receives J_g where group g is live.
 
@@ -880,6 +887,7 @@ def score_grid_device(eng, pool, plan, prepared, d_axes, out, parts=None, tree=F
     Device memory: at most three tables of ``GRID_JOINT_TABLE_BYTES`` (both
     sets' and the shared one), 16 bytes of scratch per row of the window and
     chunk of the larger set, and 8 per row of the window."""
+    eng = fits[0].eng
     t, lib = eng.torch, eng.lib
     chunk = lib.tpe_joint_chunk()
     P = len(pool)
@@ -888,7 +896,8 @@ def score_grid_device(eng, pool, plan, prepared, d_axes, out, parts=None, tree=F
     above = t.empty(win, dtype=t.float64, device=eng.device)
     n_axes = int(d_axes.numel())
     shared = None  # the table of the sets that do not fit one
-    for g, (dj, sets, sp) in enumerate(prepared):
+    for g, f in enumerate(fits):
+        dj, sets, sp = f.dj, f.sets, f.sp
         D = len(dj.models)
         cols = plan.groups[g]
         tab = None if dj.tables is None else dj.tables.data_ptr()

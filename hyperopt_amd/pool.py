@@ -67,7 +67,6 @@ host still reads back the k rows only, once.
 """
 from __future__ import annotations
 
-import ctypes
 import logging
 import math
 import time
@@ -85,6 +84,11 @@ logger = logging.getLogger(__name__)
 # log-densities kept on the device per engine run: a chunk holds as many labels
 # as fit (at least one), so the scratch is 2 x 8 x max(P, CHUNK_ELEMS) bytes
 CHUNK_ELEMS = 1 << 24
+
+
+def _same_space(domain, pool):
+    if list(domain.params) != pool.labels:
+        raise ValueError("the pool was built for another space (labels differ)")
 
 
 def _bounds(spec):
@@ -248,7 +252,16 @@ class _DevicePool(object):
     them --, activity (L, P) bytes, the taken mask, and per label the
     (min, max) of its live values in the scoring coordinate."""
     __slots__ = ("vals", "active", "taken", "taken_current", "ranges", "S", "terms", "rows_out",
-                 "count", "scratch", "first", "mask", "distinct_scratch")
+                 "count", "scratch", "first", "mask", "distinct_scratch", "fits", "parts")
+
+    def __init__(self, vals, active, taken, taken_current, ranges, S, terms=None):
+        self.vals, self.active, self.ranges, self.S, self.terms = vals, active, ranges, S, terms
+        self.taken, self.taken_current = taken, taken_current
+        # made when first needed: the top-k's buffers, ``distinct``'s, and what
+        # the last joint scoring left (``_joint_device``)
+        self.rows_out = self.count = self.scratch = None
+        self.first = self.mask = self.distinct_scratch = None
+        self.fits = self.parts = None
 
 
 class Pool(object):
@@ -338,8 +351,8 @@ class Pool(object):
         component key); the activity follows from the drawn selectors, and
         the pool is born with ``score_configs(joint="tree")`` of its rows.
         ``keep_terms`` leaves NaN everywhere: every label is joint."""
-        return _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting,
-                       keep_terms, joint=_joint_kw(joint, bandwidth, cat_smoothing))
+        st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
+        return _sample(domain, trials, seed, n_rows, st, keep_terms)
 
     def _setup(self, domain, labels, vals, active):
         _validate(domain, labels, vals, active)
@@ -407,18 +420,12 @@ class Pool(object):
                 # holds a value the scorer accepts)
                 cols[j, :P] = np.where(a, c, live[0] if live.size else 0.0)
                 ranges.append(_scoring_range(spec, live))
-            d = _DevicePool()
-            d.vals = t.from_numpy(cols).to(eng.device)
-            d.active = t.from_numpy(np.ascontiguousarray(self.active.T).view(np.uint8)
-                                    if P else np.zeros((nl, 1), np.uint8)).to(eng.device)
-            d.taken = t.zeros(max(P, 1), dtype=t.uint8, device=eng.device)
-            d.taken_current = False
-            d.ranges = ranges
-            d.S = t.empty(max(P, 1), dtype=t.float64, device=eng.device)
-            d.terms = None
-            d.rows_out = d.count = d.scratch = None
-            d.first = d.mask = d.distinct_scratch = None
-            self._device[eng.device] = d
+            d = self._device[eng.device] = _DevicePool(
+                t.from_numpy(cols).to(eng.device),
+                t.from_numpy(np.ascontiguousarray(self.active.T).view(np.uint8)
+                             if P else np.zeros((nl, 1), np.uint8)).to(eng.device),
+                t.zeros(max(P, 1), dtype=t.uint8, device=eng.device), False, ranges,
+                t.empty(max(P, 1), dtype=t.float64, device=eng.device))
         if not d.taken_current:
             d.taken[:len(self)].copy_(t.from_numpy(self.taken))
             d.taken_current = True
@@ -488,7 +495,7 @@ class SampledPool(Pool):
                                    _params(s.kind, s.args)["family"] == _L.LGMM1
                                    for s in specs], np.uint8)
             out = t.empty(2 * max(L, 1), dtype=t.float64, device=eng.device)
-            sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+            sp = _J.stream_ptr(eng)
             P = self._n_rows
             _L.check(eng.lib.tpe_pool_ranges(d.vals.data_ptr(), d.active.data_ptr(), P, P, L,
                                              positive.ctypes.data, out.data_ptr(), sp),
@@ -532,12 +539,10 @@ def _rows_active(eng, domain, labels, d, P, sp):
     return n_active
 
 
-def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting, keep_terms,
-            hist=None, joint=None, kept=None):
-    """``Pool.sample``.  ``joint``: None, or the joint criterion's keywords
-    (``_joint_kw``): the joint labels come from ``tpe_joint_sample`` and S
-    starts from J.  ``kept`` (with ``joint``, not its tree): a dict that
-    receives the prepared sets and the born parts (log L_below, log L_above,
+def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
+    """``Pool.sample`` under the settings ``st``.  With ``st.joint`` the joint
+    labels come from ``tpe_joint_sample`` and S starts from J; with ``st.lie``
+    too the mirror keeps the fit and the born parts (log L_below, log L_above,
     unused) as ``_joint_device`` leaves them."""
     from . import tpe as T
     domain = as_domain(domain)
@@ -545,6 +550,7 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
     P, L = int(n_rows), len(labels)
     if P < 0:
         raise ValueError("n_rows=%d" % P)
+    joint = st.joint
     jcols = []
     if joint is not None:  # (ValueError on a space without a joint label)
         jcols = _joint_cols(domain, joint)
@@ -555,19 +561,15 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
     if joint is not None and len(jcols) == L:
         eng, obs = T.engine(), None  # (a flat space: no label is left to the engine)
     else:
-        eng, obs = _history_inputs(domain, trials, gamma, hist)
+        eng, obs = _history_inputs(domain, trials, st.gamma, hist)
     t, lib = eng.torch, eng.lib
-    d = _DevicePool()
-    d.vals = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device)
-    d.active = t.zeros((max(L, 1), P), dtype=t.uint8, device=eng.device)
-    d.taken = t.zeros(P, dtype=t.uint8, device=eng.device)
-    d.taken_current = True
-    d.ranges = None
-    d.S = t.empty(P, dtype=t.float64, device=eng.device)
-    d.terms = t.empty((max(L, 1), P), dtype=t.float64, device=eng.device) if keep_terms else None
-    d.rows_out = d.count = d.scratch = None
-    d.first = d.mask = d.distinct_scratch = None
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    d = _DevicePool(
+        t.empty((max(L, 1), P), dtype=t.float64, device=eng.device),
+        t.zeros((max(L, 1), P), dtype=t.uint8, device=eng.device),
+        t.zeros(P, dtype=t.uint8, device=eng.device), True, None,
+        t.empty(P, dtype=t.float64, device=eng.device),
+        t.empty((max(L, 1), P), dtype=t.float64, device=eng.device) if keep_terms else None)
+    sp = _J.stream_ptr(eng)
     per = max(1, CHUNK_ELEMS // P)
     xbuf = t.empty(min(per, max(L, 1)) * P, dtype=t.float64, device=eng.device)
 
@@ -576,7 +578,7 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
         log-densities left in the engine's buffers at the returned offsets."""
         works = [obs.work(labels[j], domain.specs[labels[j]], j, n_cand=P, n_total=P,
                           key=T.label_key(seed, labels[j]), cand_base=0) for j in js]
-        res = eng.run(works, prior_weight=prior_weight, lf=linear_forgetting, precision=64,
+        res = eng.run(works, prior_weight=st.prior_weight, lf=st.lf, precision=64,
                       outputs=True, device_outputs=True, x_ptr=xbuf.data_ptr(), **obs.run_kwargs)
         off = np.asarray([r.extra["out_off"] for r in res], np.int64)
         for j, o in zip(js, off):  # (device to device)
@@ -586,24 +588,11 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
     todo = [j for j in range(L) if j not in jcols]
     chunks = [todo[c0:c0 + per] for c0 in range(0, len(todo), per)]
     n_active = None
-    prepared = None
-    tree = joint is not None and joint.get("tree")
-    if tree:
-        # every group's columns, for all the rows, from the group's below mixture
-        isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
-        prepared = _J.prepare_tree(eng, domain, hist, _seen_rows(eng, hist), isb, isa, L,
-                                   prior_weight, linear_forgetting, joint["bandwidth"],
-                                   joint["cat_smoothing"])
-        _J.sample_tree_device(eng, prepared, seed, prior_weight, linear_forgetting,
-                              joint["cat_smoothing"], d.vals, P, L, 0, P)
-    elif joint is not None:
-        # the joint labels' columns: one draw per row from the below set's mixture
-        isb, isa = T.split_masks(hist, gamma) if hist.tids.size else (np.zeros(0, bool),) * 2
-        prepared = _J.prepare_sets(eng, domain, hist, _seen_rows(eng, hist), isb, isa, L,
-                                   prior_weight, linear_forgetting, joint["bandwidth"],
-                                   joint["cat_smoothing"])
-        _J.sample_device(eng, prepared, seed, prior_weight, linear_forgetting,
-                         joint["cat_smoothing"], d.vals, P, L, 0, P)
+    if joint is not None:
+        # the joint labels' columns (with the groups: every group's), for all the
+        # rows: one draw per row from the below set's mixture
+        fits = _fit(eng, domain, hist, L, st)
+        _J.sample_tree_device(fits, seed, d.vals, P, L, 0, P)
     if len(chunks) > 1:
         # the fold runs in label order and needs every row's activity: the
         # selectors' columns first (their draws do not depend on the chunking)
@@ -618,18 +607,12 @@ def _sample(domain, trials, seed, n_rows, prior_weight, gamma, linear_forgetting
             n_active = _rows_active(eng, domain, labels, d, P, sp)
         # S starts from J of the drawn rows; the fold below adds the other labels
         # (with the groups every label is joint: S is theirs, and nothing is folded)
-        if tree:
-            _J.score_tree_device(eng, domain, hist, None, None, None, d.vals, d.active, P, L, P,
-                                 d.S, prior_weight, linear_forgetting, joint["bandwidth"],
-                                 joint["cat_smoothing"], tree=prepared)
+        if joint["tree"]:
+            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S)
         else:
-            parts = None
-            if kept is not None:  # (log L_above of the born rows stays, for the batch)
-                parts = t.empty((3, P), dtype=t.float64, device=eng.device)
-                kept.update(prepared=prepared, parts=parts)
-            _J.score_device(eng, domain, hist, None, None, None, d.vals, P, L, P, d.S,
-                            prior_weight, linear_forgetting, joint["bandwidth"],
-                            joint["cat_smoothing"], parts, prepared)
+            if st.lie is not None:  # (log L_above of the born rows stays, for the batch)
+                d.fits, d.parts = fits, _parts(eng, domain, st, P)
+            _J.score_device(fits[0], d.vals, P, L, P, d.S, d.parts)
         init = 0
         if keep_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -673,7 +656,8 @@ class _DeviceGrid(object):
     randint(low, high) values offset-free), the (min, max) of every axis in the
     scoring coordinate, S (8 bytes per row) and the mask ``tpe_pool_topk``
     reads (taken or excluded, one byte per row)."""
-    __slots__ = ("axes", "taken", "taken_current", "ranges", "S", "rows_out", "count", "scratch")
+    __slots__ = ("axes", "taken", "taken_current", "ranges", "S", "rows_out", "count", "scratch",
+                 "parts")
 
 
 KEEP_CHUNK = 1 << 20   # rows per call of a grid pool's ``keep``
@@ -926,7 +910,7 @@ class GridPool(object):
             d.taken = t.zeros(max(P, 1), dtype=t.uint8, device=eng.device)
             d.taken_current = False
             d.S = t.empty(max(P, 1), dtype=t.float64, device=eng.device)
-            d.rows_out = d.count = d.scratch = None
+            d.rows_out = d.count = d.scratch = d.parts = None
             self._device[eng.device] = d
         if not d.taken_current:
             gone = self.taken if self.excluded is None else self.taken | self.excluded
@@ -935,49 +919,57 @@ class GridPool(object):
         return d
 
 
-def _score_grid(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None):
-    """S of every row of a grid pool into its device buffer ``S``: one engine
-    run over the axes of the scored labels, one ``tpe_grid_fold`` per block.
-    Returns (engine, device grid, {label index: T_l} or None)."""
-    if list(domain.params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
-    eng, obs = _history_inputs(domain, trials, gamma, hist)
-    d = pool.device(eng)
-    t, lib = eng.torch, eng.lib
-    works = []
-    for j in pool.scored:
-        lab = pool.labels[j]
-        n = pool.axes[j].size
-        w = obs.work(lab, domain.specs[lab], int(j), n_cand=n, n_total=n)
-        w.cand_dev = (int(pool.axis_off[j]), n, d.ranges[j])
-        works.append(w)
-    out_off = np.zeros(len(pool.labels), np.int64)
+def _grid_run(eng, obs, domain, pool, d, js, st, want_terms):
+    """One engine run over the axis values of the labels ``js`` (label
+    indices) of a grid pool: (below pointer, above pointer, out_off, terms) --
+    the device log-densities (None without a label), per label of the space
+    the offset of its axis position 0 in them (-1: not in the run), and with
+    ``want_terms`` {label: T_l}, all NaN for a label that was not in the run."""
+    out_off = np.full(len(pool.labels), -1, np.int64)
     d_bl = d_al = None
-    if works:
-        res = eng.run(works, prior_weight=prior_weight, lf=lf, precision=64, outputs=True,
+    if len(js):
+        works = []
+        for j in js:
+            lab = pool.labels[j]
+            n = pool.axes[j].size
+            w = obs.work(lab, domain.specs[lab], int(j), n_cand=n, n_total=n)
+            w.cand_dev = (int(pool.axis_off[j]), n, d.ranges[j])
+            works.append(w)
+        res = eng.run(works, prior_weight=st.prior_weight, lf=st.lf, precision=64, outputs=True,
                       cand_ptr=d.axes.data_ptr(), device_outputs=True, **obs.run_kwargs)
-        out_off[pool.scored] = [r.extra["out_off"] for r in res]
+        out_off[js] = [r.extra["out_off"] for r in res]
         d_bl, d_al = eng.device_output_ptrs()
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
-    for b in pool.blocks:
-        off = np.ascontiguousarray(out_off[b.cols] + b.pos)
-        _L.check(lib.tpe_grid_fold(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data, len(b.cols),
-                                   0, b.rows, d.S.data_ptr() + 8 * b.offset, sp),
-                 "tpe_grid_fold")
     terms = None
     if want_terms:
-        terms = {}
-        n = int(sum(pool.axes[j].size for j in pool.scored))
-        if works:
+        terms = {lab: np.full(pool.axes[j].size, np.nan) for j, lab in enumerate(pool.labels)}
+        if len(js):
+            n = int(sum(pool.axes[j].size for j in js))
             bl, al = (eng._bufs[k][:8 * n].cpu().numpy().view(np.float64)
                       for k in ("out_bl", "out_al"))
-        for j, lab in enumerate(pool.labels):
-            if j in pool.scored:
-                o = int(out_off[j])
-                with np.errstate(invalid="ignore"):
-                    terms[lab] = bl[o:o + pool.axes[j].size] - al[o:o + pool.axes[j].size]
-            else:  # live in no block: never scored
-                terms[lab] = np.full(pool.axes[j].size, np.nan)
+        for j in js:
+            o, m = int(out_off[j]), pool.axes[j].size
+            with np.errstate(invalid="ignore"):
+                terms[pool.labels[j]] = bl[o:o + m] - al[o:o + m]
+    return d_bl, d_al, out_off, terms
+
+
+def _score_grid(domain, trials, pool, st, want_terms, hist=None, want_parts=False):
+    """S of every row of a grid pool into its device buffer ``S``: one engine
+    run over the axes of the scored labels, one ``tpe_grid_fold`` per block
+    (with ``st.joint``: ``_score_grid_joint``).  Returns (engine, device grid,
+    {label: T_l} or None)."""
+    _same_space(domain, pool)
+    if st.joint is not None:
+        return _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts)
+    eng, obs = _history_inputs(domain, trials, st.gamma, hist)
+    d = pool.device(eng)
+    d_bl, d_al, out_off, terms = _grid_run(eng, obs, domain, pool, d, pool.scored, st, want_terms)
+    sp = _J.stream_ptr(eng)
+    for b in pool.blocks:
+        off = np.ascontiguousarray(out_off[b.cols] + b.pos)
+        _L.check(eng.lib.tpe_grid_fold(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data,
+                                       len(b.cols), 0, b.rows, d.S.data_ptr() + 8 * b.offset, sp),
+                 "tpe_grid_fold")
     return eng, d, terms
 
 
@@ -1073,121 +1065,83 @@ def grid_joint_plan(pool, tree=False):
     return plan
 
 
-def _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, jkw, want_terms, hist=None,
-                      parts=None):
-    """S of every row of a grid pool built with ``joint=True`` into its device
-    buffer ``S``, with the bits of the materialised pool: the groups' J from
-    per-axis factor tables (``joint.score_grid_device``); then, for
-    ``joint=True`` on a space with a ``switch``, per block the univariate terms
-    of the block's other labels added onto S in ``domain.params`` order
-    (``tpe_grid_fold_onto``; the joint labels are decoded and add nothing),
-    from one engine run over the axes of those labels alone.  Returns (engine,
-    device grid, {label: T_l} or None) as ``_score_grid``."""
+def _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts):
+    """``_score_grid`` for a grid pool built with ``joint=True``, with the bits
+    of the materialised pool: the groups' J from per-axis factor tables
+    (``joint.score_grid_device``); then, for ``joint=True`` on a space with a
+    ``switch``, per block the univariate terms of the block's other labels
+    added onto S in ``domain.params`` order (``tpe_grid_fold_onto``; the joint
+    labels are decoded and add nothing), from one engine run over the axes of
+    those labels alone.  ``want_parts``: the device grid's ``parts`` receives
+    what ``_parts`` describes."""
     from . import tpe as T
-    if list(domain.params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
-    tree = bool(jkw.get("tree"))
+    tree = st.joint["tree"]
     plan = pool.joint_plan(tree)  # (ValueError: no joint plan, or no groups)
     if hist is None:
         hist = T.collect_history(trials, pool.labels)
     covered = set(j for cols in plan.groups for j in cols)
     rest = [int(j) for j in pool.scored if int(j) not in covered]
-    eng, obs = _history_inputs(domain, trials, gamma, hist) if rest else (T.engine(), None)
+    eng, obs = _history_inputs(domain, trials, st.gamma, hist) if rest else (T.engine(), None)
     d = pool.device(eng)
-    t, lib = eng.torch, eng.lib
-    if hist.tids.size:
-        isb, isa = T.split_masks(hist, gamma)
-    else:
-        isb = isa = np.zeros(0, bool)
-    seen = _seen_rows(eng, hist)
-    args = (eng, domain, hist, seen, isb, isa, len(pool.labels), prior_weight, lf,
-            jkw["bandwidth"], jkw["cat_smoothing"])
-    if tree:
-        prepared = [p for _grp, p in _J.prepare_tree(*args)]
-    else:
-        prepared = [_J.prepare_sets(*args)]
-    _J.score_grid_device(eng, pool, plan, prepared, d.axes, d.S, parts, tree)
-    out_off = np.full(len(pool.labels), -1, np.int64)
-    if rest:
-        works = []
-        for j in rest:
-            lab = pool.labels[j]
-            n = pool.axes[j].size
-            w = obs.work(lab, domain.specs[lab], j, n_cand=n, n_total=n)
-            w.cand_dev = (int(pool.axis_off[j]), n, d.ranges[j])
-            works.append(w)
-        res = eng.run(works, prior_weight=prior_weight, lf=lf, precision=64, outputs=True,
-                      cand_ptr=d.axes.data_ptr(), device_outputs=True, **obs.run_kwargs)
-        out_off[rest] = [r.extra["out_off"] for r in res]
-        d_bl, d_al = eng.device_output_ptrs()
-        sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
-        for b in pool.blocks:
-            base = out_off[b.cols]
-            if not (base >= 0).any():
-                continue
-            off = np.ascontiguousarray(np.where(base >= 0, base + b.pos, -1))
-            _L.check(lib.tpe_grid_fold_onto(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data,
+    d.parts = _parts(eng, domain, st, len(pool)) if want_parts else None
+    fits = _fit(eng, domain, hist, len(pool.labels), st)
+    _J.score_grid_device(fits, pool, plan, d.axes, d.S, d.parts, tree)
+    d_bl, d_al, out_off, terms = _grid_run(eng, obs, domain, pool, d, rest, st, want_terms)
+    sp = _J.stream_ptr(eng)
+    for b in pool.blocks:
+        base = out_off[b.cols]
+        if not (base >= 0).any():
+            continue
+        off = np.ascontiguousarray(np.where(base >= 0, base + b.pos, -1))
+        _L.check(eng.lib.tpe_grid_fold_onto(d_bl, d_al, off.ctypes.data, b.radix.ctypes.data,
                                             len(b.cols), 0, b.rows,
                                             d.S.data_ptr() + 8 * b.offset, sp),
-                     "tpe_grid_fold_onto")
-    terms = None
-    if want_terms:
-        terms = {lab: np.full(pool.axes[j].size, np.nan) for j, lab in enumerate(pool.labels)}
-        if rest:
-            n = int(sum(pool.axes[j].size for j in rest))
-            bl, al = (eng._bufs[k][:8 * n].cpu().numpy().view(np.float64)
-                      for k in ("out_bl", "out_al"))
-            for j in rest:
-                o, m = int(out_off[j]), pool.axes[j].size
-                with np.errstate(invalid="ignore"):
-                    terms[pool.labels[j]] = bl[o:o + m] - al[o:o + m]
+                 "tpe_grid_fold_onto")
     return eng, d, terms
 
 
-def _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, jkw, hist, parts=None,
-                  kept=None):
-    """J (joint.py) of every pool row into ``d.S``.  ``parts``: a (3, P) device
-    tensor for log L below, log L above and J.  With ``jkw["tree"]`` it is the
-    groups' S that goes into ``d.S``, and ``parts`` is a (G, P) device tensor
-    filled with NaN for the J_g (``joint.score_tree_device``).  ``kept``: a
-    dict that receives the prepared sets (``joint.prepare_sets``) and ``parts``
-    for a caller that goes on with them (``batch="liar"``)."""
-    from . import tpe as T
-    if hist.tids.size:
-        isb, isa = T.split_masks(hist, gamma)
-    else:
-        isb = isa = np.zeros(0, bool)
-    if jkw.get("tree"):
-        _J.score_tree_device(eng, domain, hist, _seen_rows(eng, hist), isb, isa, d.vals, d.active,
-                             d.vals.shape[1], len(pool.labels), len(pool), d.S, prior_weight, lf,
-                             jkw["bandwidth"], jkw["cat_smoothing"], parts)
+def _fit(eng, domain, hist, n_cols, st):
+    """``joint.fit`` of the history under the settings ``st``."""
+    return _J.fit(eng, domain, hist, _seen_rows(eng, hist), st.gamma, n_cols, st.prior_weight,
+                  st.lf, st.joint["bandwidth"], st.joint["cat_smoothing"], st.joint["tree"])
+
+
+def _parts(eng, domain, st, P):
+    """The device tensor a joint scoring leaves its parts in: (3, P) for log
+    L_below, log L_above and J; with ``tree`` (G, P) filled with NaN for the
+    J_g (at least one column)."""
+    t = eng.torch
+    if st.joint["tree"]:
+        return t.full((len(_J.joint_groups(domain)), max(P, 1)), float("nan"), dtype=t.float64,
+                      device=eng.device)
+    return t.empty((3, max(P, 1)), dtype=t.float64, device=eng.device)
+
+
+def _joint_device(eng, domain, pool, d, st, hist):
+    """J (joint.py) of every pool row into ``d.S`` -- with ``tree`` the groups'
+    S (``joint.score_tree_device``) -- and its parts into ``d.parts`` where
+    that is a tensor (``_parts``).  The mirror keeps the fit in ``d.fits``."""
+    P, L, ld = len(pool), len(pool.labels), d.vals.shape[1]
+    d.fits = _fit(eng, domain, hist, L, st)
+    if st.joint["tree"]:
+        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts)
         return
-    seen, prepared = _seen_rows(eng, hist), None
-    if kept is not None:
-        prepared = _J.prepare_sets(eng, domain, hist, seen, isb, isa, len(pool.labels),
-                                   prior_weight, lf, jkw["bandwidth"], jkw["cat_smoothing"])
-        kept.update(prepared=prepared, parts=parts)
-    _J.score_device(eng, domain, hist, seen, isb, isa, d.vals, d.vals.shape[1],
-                    len(pool.labels), len(pool), d.S, prior_weight, lf, jkw["bandwidth"],
-                    jkw["cat_smoothing"], parts, prepared)
-    if parts is not None:  # (row 2: J itself, before the fold adds to S)
-        parts[2, :len(pool)].copy_(d.S[:len(pool)])
+    _J.score_device(d.fits[0], d.vals, ld, L, P, d.S, d.parts)
+    if d.parts is not None:  # (row 2: J itself, before the fold adds to S)
+        d.parts[2, :P].copy_(d.S[:P])
 
 
-def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, hist=None,
-                  joint=None, parts=None, kept=None):
+def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=False):
     """S of every pool row into the pool's device buffer ``S`` (and the
-    per-label terms into ``terms``); returns (engine, device pool).  ``joint``:
-    None, or the joint criterion's keywords (``bandwidth``, ``cat_smoothing``)
-    -- S starts from J and the fold adds the other labels' terms.  ``parts`` /
-    ``kept``: ``_joint_device``'s."""
-    if isinstance(pool, GridPool):
-        if joint is not None:  # (ValueError(GRID_JOINT) on a grid without the plan)
-            return _score_grid_joint(domain, trials, pool, prior_weight, gamma, lf, joint, False,
-                                     hist, parts)[:2]
-        return _score_grid(domain, trials, pool, prior_weight, gamma, lf, False, hist)[:2]
-    if list(domain.params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
+    per-label terms into ``terms``) under the settings ``st``; returns (engine,
+    device pool).  With ``st.joint`` S starts from J and the fold adds the
+    other labels' terms, and the mirror keeps the fit in ``fits`` and -- with
+    ``want_parts``, and for ``batch="liar"`` -- the parts in ``parts``
+    (``_parts``); both are None otherwise."""
+    if isinstance(pool, GridPool):  # (ValueError(GRID_JOINT) on a grid without the plan)
+        return _score_grid(domain, trials, pool, st, False, hist)[:2]
+    _same_space(domain, pool)
+    joint = st.joint
     if joint is not None:
         from . import tpe as T
         # (ValueError on a space without a joint label)
@@ -1196,22 +1150,25 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
             hist = T.collect_history(trials, pool.labels)
         rest = [j for j in range(len(pool.labels)) if pool.n_active[j] and j not in jcols]
         # (a flat space has no other label: no observation inputs, no fold)
-        eng, obs = _history_inputs(domain, trials, gamma, hist) if rest else (T.engine(), None)
+        eng, obs = _history_inputs(domain, trials, st.gamma, hist) if rest else (T.engine(), None)
     else:
-        eng, obs = _history_inputs(domain, trials, gamma, hist)
+        eng, obs = _history_inputs(domain, trials, st.gamma, hist)
     d = pool.device(eng)
     t, lib = eng.torch, eng.lib
     P = len(pool)
     if want_terms and d.terms is None:
         d.terms = t.empty((len(pool.labels), max(P, 1)), dtype=t.float64, device=eng.device)
+    d.fits = d.parts = None
+    if joint is not None and (want_parts or st.lie is not None):
+        d.parts = _parts(eng, domain, st, P)
     if P == 0:
         return eng, d
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    sp = _J.stream_ptr(eng)
     todo = [j for j in range(len(pool.labels)) if pool.n_active[j]]
     per = max(1, CHUNK_ELEMS // P)
     init = 1
     if joint is not None:
-        _joint_device(eng, domain, pool, d, prior_weight, gamma, lf, joint, hist, parts, kept)
+        _joint_device(eng, domain, pool, d, st, hist)
         todo, init = rest, 0
         if want_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -1227,8 +1184,9 @@ def _score_device(domain, trials, pool, prior_weight, gamma, lf, want_terms, his
                 w = obs.work(lab, domain.specs[lab], j, n_cand=P, n_total=P)
                 w.cand_dev = (j * P, P, d.ranges[j])
                 works.append(w)
-            res = eng.run(works, prior_weight=prior_weight, lf=lf, precision=64, outputs=True,
-                          cand_ptr=d.vals.data_ptr(), device_outputs=True, **obs.run_kwargs)
+            res = eng.run(works, prior_weight=st.prior_weight, lf=st.lf, precision=64,
+                          outputs=True, cand_ptr=d.vals.data_ptr(), device_outputs=True,
+                          **obs.run_kwargs)
             off[:] = [r.extra["out_off"] for r in res]
             d_bl, d_al = eng.device_output_ptrs()
         cols = np.asarray(js if js else [0], np.int64)
@@ -1297,7 +1255,7 @@ def _distinct_device(eng, pool, d, hist):
     # a history holds randint(low, high) with ``low`` included, a pool without
     shift = np.asarray([int_offset(pool.domain.specs[lab]) or 0 for lab in pool.labels],
                        np.float64)
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    sp = _J.stream_ptr(eng)
     _L.check(lib.tpe_pool_distinct(d.vals.data_ptr() if L else None,
                                    d.active.data_ptr() if L else None, d.vals.shape[1], P, L,
                                    sv, sa, sld, srows, n_seen,
@@ -1324,8 +1282,8 @@ def distinct_rows(pool, trials=None, domain=None):
     from . import tpe as T
     if isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
-    if domain is not None and list(as_domain(domain).params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
+    if domain is not None:
+        _same_space(as_domain(domain), pool)
     if len(pool) == 0:
         return np.zeros(0, np.int64)
     eng = T.engine()
@@ -1349,7 +1307,7 @@ def _topk_device(eng, d, P, k, taken=None):
     if d.rows_out is None or d.rows_out.numel() < k:
         d.rows_out = t.empty(k, dtype=t.int64, device=eng.device)
         d.count = t.zeros(1, dtype=t.int64, device=eng.device)
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    sp = _J.stream_ptr(eng)
     _L.check(lib.tpe_pool_topk(d.S.data_ptr(), taken.data_ptr(), P, k, d.rows_out.data_ptr(),
                                d.count.data_ptr(), d.scratch.data_ptr(), sp), "tpe_pool_topk")
     n = int(d.count.item())
@@ -1357,7 +1315,7 @@ def _topk_device(eng, d, P, k, taken=None):
 
 
 def _joint_kw(joint, bandwidth, cat_smoothing):
-    """``_score_device``'s ``joint``: None, or the criterion's keywords
+    """``_Settings.joint``: None, or the criterion's keywords
     (``tree``: the string ``"tree"`` was given -- one mixture per group of
     labels, joint.py "Groups"; any other truthy value is ``joint=True``)."""
     if isinstance(joint, str) and joint == "tree":
@@ -1386,32 +1344,48 @@ BATCH_LIAR = ("batch='liar' is supported with joint=True on a Pool or a SampledP
               "(suggest_from_pool, suggest_sampled, pick_batch)")
 
 
-def _batch_kw(batch, lie_weight, jkw, pool=None):
-    """None for ``batch=None``; for ``batch="liar"`` the lie's weight, after
-    the checks: ValueError on any other string, on a ``lie_weight`` that is not
-    a finite number > 0, and on what the batch is not built for (joint.py,
-    "Not built")."""
+class _Settings(object):
+    """What a scoring and the picks after it run under: ``prior_weight``,
+    ``gamma``, ``lf`` (linear forgetting), ``joint`` (``_joint_kw``) and
+    ``lie`` (None, or the lie's weight of ``batch="liar"``)."""
+    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie")
+
+    def __init__(self, prior_weight, gamma, lf, joint=None, lie=None):
+        self.prior_weight, self.gamma, self.lf, self.joint, self.lie = \
+            prior_weight, gamma, lf, joint, lie
+
+
+def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
+              cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, pool=None):
+    """The ``_Settings`` of a public call's keywords, after the checks:
+    ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
+    ``"liar"``, on a ``lie_weight`` that is not a finite number > 0, and on
+    what the batch is not built for (joint.py, "Not built"; ``pool``: the
+    call's pool, where it has one)."""
+    st = _Settings(prior_weight, gamma, lf, _joint_kw(joint, bandwidth, cat_smoothing))
     if batch is None:
-        return None
+        return st
     if batch != "liar":
         raise ValueError("batch=%r: None or 'liar'" % (batch,))
     if not lie_weight > 0.0 or not math.isfinite(lie_weight):
         raise ValueError("lie_weight=%r must be a finite number > 0" % (lie_weight,))
-    if jkw is None:
+    if st.joint is None:
         raise ValueError(BATCH_LIAR + "; the factorised criterion (joint=False) has no such "
                          "update: its bandwidths depend on the sorted neighbours")
-    if jkw["tree"]:
+    if st.joint["tree"]:
         raise ValueError(BATCH_LIAR + "; joint='tree' keeps no log L_above per group")
     if isinstance(pool, GridPool):
         raise ValueError(BATCH_LIAR + "; a GridPool has no row values to lie with "
                          "(GridPool.to_pool())")
-    return float(lie_weight)
+    st.lie = float(lie_weight)
+    return st
 
 
-def _liar_device(eng, d, P, k, mask, lie_weight, kept, prior_weight, lf, jkw, trace=False):
+def _liar_device(eng, d, P, k, mask, lie_weight, trace=False):
     """``_topk_device`` for ``batch="liar"``: the rows of ``joint.liar_device``
-    on d.S and the log L_above that ``kept`` holds (``_joint_device``); ``mask``:
-    ``distinct``'s device mask or None.  The rows stay in d.rows_out."""
+    on d.S, with the fit and the log L_above the scoring left in the mirror
+    (``_joint_device``); ``mask``: ``distinct``'s device mask or None.  The rows
+    stay in d.rows_out."""
     t = eng.torch
     k = min(int(k), P)
     if d.rows_out is None or d.rows_out.numel() < k + 1:
@@ -1419,9 +1393,22 @@ def _liar_device(eng, d, P, k, mask, lie_weight, kept, prior_weight, lf, jkw, tr
         # entry k of the rows, read back with them)
         d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
         d.count = t.zeros(1, dtype=t.int64, device=eng.device)
-    return _J.liar_device(eng, kept["prepared"], d.vals, d.vals.shape[1], d.vals.shape[0], P, d.S,
-                          kept["parts"][1], d.taken, mask, k, lie_weight, prior_weight, lf,
-                          jkw["bandwidth"], trace, d.rows_out)
+    return _J.liar_device(d.fits[0], d.vals, d.vals.shape[1], d.vals.shape[0], P, d.S, d.parts[1],
+                          d.taken, mask, k, lie_weight, trace, d.rows_out)
+
+
+def _pick(eng, pool, d, k, hist, distinct, st, trace=False):
+    """The k rows to hand out, by the scores in the mirror ``d``: the first k
+    untaken rows by d.S (``_topk_device``), or with ``st.lie`` the liar batch
+    (``_liar_device``; ``trace``: its (rows, S_at_pick, S_k)).  ``distinct``:
+    fresh rows only (``_distinct_device`` against ``hist``).  The rows stay in
+    d.rows_out."""
+    if distinct:
+        _distinct_device(eng, pool, d, hist)
+    mask = d.mask if distinct else None
+    if st.lie is None:
+        return _topk_device(eng, d, len(pool), k, mask)
+    return _liar_device(eng, d, len(pool), k, mask, st.lie, trace)
 
 
 def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_weight=1.0,
@@ -1434,24 +1421,15 @@ def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_
     after the last pick.  A ``GridPool`` raises ValueError."""
     from . import tpe as T
     domain = as_domain(domain)
-    jkw = _joint_kw(True, bandwidth, cat_smoothing)
-    lie = _batch_kw("liar", lie_weight, jkw, pool)
-    if list(domain.params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
-    P = len(pool)
-    eng = T.engine()
+    st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing, "liar",
+                   lie_weight, pool)
+    _same_space(domain, pool)
     hist = T.collect_history(trials, pool.labels)
-    kept = {}
-    parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
-    eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
-                           hist=hist, joint=jkw, parts=parts, kept=kept)
-    if P == 0:
+    eng, d = _score_device(domain, trials, pool, st, False, hist=hist)
+    if len(pool) == 0:
         none = np.zeros(0, np.int64)
         return (none, np.zeros(0), np.zeros(0)) if return_trace else none
-    if distinct:
-        _distinct_device(eng, pool, d, hist)
-    return _liar_device(eng, d, P, k, d.mask if distinct else None, lie, kept, prior_weight,
-                        linear_forgetting, jkw, return_trace)
+    return _pick(eng, pool, d, k, hist, distinct, st, return_trace)
 
 
 def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
@@ -1492,42 +1470,29 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     switches are not selected by bare choice / randint(n) labels raises
     ValueError.  Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
-    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
-    if isinstance(pool, GridPool) and jkw is None:
-        eng, d, terms = _score_grid(domain, trials, pool, prior_weight, gamma,
-                                    linear_forgetting, return_terms)
-        S = d.S[:len(pool)].cpu().numpy()
-        return (S, terms) if return_terms else S
-    if isinstance(pool, GridPool) and not pool.joint:
+    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
+    grid, tree = isinstance(pool, GridPool), st.joint is not None and st.joint["tree"]
+    if grid and st.joint is not None and not pool.joint:
         raise ValueError(GRID_JOINT)
     P = len(pool)
-    parts = None
-    if jkw is not None and return_terms:  # (J is read before the fold adds to it)
-        from . import tpe as T
-        eng = T.engine()
-        if jkw["tree"]:  # (a row per group, NaN where the group is not live)
-            parts = eng.torch.full((len(_J.joint_groups(domain)), max(P, 1)), float("nan"),
-                                   dtype=eng.torch.float64, device=eng.device)
-        else:
-            parts = eng.torch.empty((3, max(P, 1)), dtype=eng.torch.float64, device=eng.device)
-    if isinstance(pool, GridPool):
-        eng, d, terms = _score_grid_joint(domain, trials, pool, prior_weight, gamma,
-                                          linear_forgetting, jkw, return_terms, parts=parts)
-        S = d.S[:P].cpu().numpy()
-        if not return_terms:
-            return S
-        if jkw["tree"]:
-            return S, terms, np.ascontiguousarray(parts[:, :P].cpu().numpy().T)
-        return S, terms, parts[2, :P].cpu().numpy()
-    eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
-                           return_terms, joint=jkw, parts=parts)
+    if tree and return_terms:  # (ValueError on a space without the groups, before any other)
+        _J.joint_groups(domain)
+    if grid:  # (J is read before the fold adds to it: the parts)
+        eng, d, terms = _score_grid(domain, trials, pool, st, return_terms,
+                                    want_parts=return_terms)
+    else:
+        eng, d = _score_device(domain, trials, pool, st, return_terms, want_parts=return_terms)
     S = d.S[:P].cpu().numpy()
     if not return_terms:
         return S
-    terms = np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
-    if jkw is not None and jkw["tree"]:
+    if not grid:
+        terms = np.ascontiguousarray(d.terms[:, :P].cpu().numpy().T)
+    if st.joint is None:
+        return S, terms
+    parts, d.parts = d.parts, None
+    if tree:
         return S, terms, np.ascontiguousarray(parts[:, :P].cpu().numpy().T)
-    return (S, terms) if parts is None else (S, terms, parts[2, :P].cpu().numpy())
+    return S, terms, parts[2, :P].cpu().numpy()
 
 
 def startup_rows(pool, seed, k, stale=None):
@@ -1591,14 +1556,13 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
-    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
-    lie = _batch_kw(batch, lie_weight, jkw, pool)
-    if jkw is not None and isinstance(pool, GridPool) and not pool.joint:
+    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
+                   lie_weight, pool)
+    if st.joint is not None and isinstance(pool, GridPool) and not pool.joint:
         raise ValueError(GRID_JOINT)
     t0 = time.time()
     domain = as_domain(domain)
-    if list(domain.params) != pool.labels:
-        raise ValueError("the pool was built for another space (labels differ)")
+    _same_space(domain, pool)
     k = min(len(new_ids), pool.n_untaken)
     if k == 0:
         return []
@@ -1611,21 +1575,9 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
             _distinct_device(eng, pool, d, hist)
             stale = d.first[:len(pool)].cpu().numpy() != np.arange(len(pool))
         rows = startup_rows(pool, seed, k, stale)
-    elif lie is None:
-        eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
-                               False, hist=hist, joint=jkw)
-        if distinct:
-            _distinct_device(eng, pool, d, hist)
-        rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
     else:
-        eng, kept = T.engine(), {}
-        parts = eng.torch.empty((3, len(pool)), dtype=eng.torch.float64, device=eng.device)
-        eng, d = _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting,
-                               False, hist=hist, joint=jkw, parts=parts, kept=kept)
-        if distinct:
-            _distinct_device(eng, pool, d, hist)
-        rows = _liar_device(eng, d, len(pool), k, d.mask if distinct else None, lie, kept,
-                            prior_weight, linear_forgetting, jkw)
+        eng, d = _score_device(domain, trials, pool, st, False, hist=hist)
+        rows = _pick(eng, pool, d, k, hist, distinct, st)
     rows = [int(r) for r in rows]
     pool.mark_taken(rows)
     ids = list(new_ids)[:len(rows)]
@@ -1669,7 +1621,7 @@ def take_rows(pool, rows_dev, k):
     d, t, L = pool._born(), eng.torch, len(pool.labels)
     out_v = t.empty((k, max(L, 1)), dtype=t.float64, device=eng.device)
     out_a = t.empty((k, max(L, 1)), dtype=t.uint8, device=eng.device)
-    sp = ctypes.c_void_p(t.cuda.current_stream(eng.device).cuda_stream)
+    sp = _J.stream_ptr(eng)
     _L.check(eng.lib.tpe_pool_take(d.vals.data_ptr(), d.active.data_ptr(), len(pool), L,
                                    rows_dev.data_ptr(), k, out_v.data_ptr(), out_a.data_ptr(),
                                    sp), "tpe_pool_take")
@@ -1751,11 +1703,10 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         raise ValueError("draw='joint' draws from the joint criterion's below mixture: it needs "
                          "joint=True")
     domain = as_domain(domain)
-    jkw = _joint_kw(joint, bandwidth, cat_smoothing)
-    lie = _batch_kw(batch, lie_weight, jkw)
-    kept = None if lie is None else {}
-    if jkw is not None:
-        _joint_cols(domain, jkw)  # (ValueError on a space without a joint label)
+    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
+                   lie_weight)
+    if st.joint is not None:
+        _joint_cols(domain, st.joint)  # (ValueError on a space without a joint label)
     labels = list(domain.params)
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)
@@ -1777,28 +1728,18 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         rows = np.flatnonzero(ok)[:len(new_ids)]
         configs = [_stored_config(domain, labels, vals[r], active[r]) for r in rows]
         return trial_docs(list(new_ids)[:len(rows)], domain, trials, configs)
-    pool = _sample(domain, trials, seed, n, prior_weight, gamma, linear_forgetting, False,
-                   hist=hist, joint=jkw if draw == "joint" else None, kept=kept)
+    born = st if draw == "joint" else _Settings(prior_weight, gamma, linear_forgetting)
+    pool = _sample(domain, trials, seed, n, born, False, hist=hist)
     if keep is not None and len(pool):
         pool.mark_taken(np.flatnonzero(~_keep_rows(keep, labels, pool.vals, len(pool))))
     k = min(len(new_ids), pool.n_untaken)
     if k == 0:
         return []
     eng = T.engine()
-    if jkw is not None and draw != "joint":  # S: the joint criterion in place of the born scores
-        parts = None
-        if lie is not None:
-            parts = eng.torch.empty((3, len(pool)), dtype=eng.torch.float64, device=eng.device)
-        _score_device(domain, trials, pool, prior_weight, gamma, linear_forgetting, False,
-                      hist=hist, joint=jkw, parts=parts, kept=kept)
+    if st.joint is not None and draw != "joint":  # S: the joint criterion, not the born scores
+        _score_device(domain, trials, pool, st, False, hist=hist)
     d = _mirror(pool, eng)
-    if distinct:
-        _distinct_device(eng, pool, d, hist)
-    if lie is None:
-        rows = _topk_device(eng, d, len(pool), k, d.mask if distinct else None)
-    else:
-        rows = _liar_device(eng, d, len(pool), k, d.mask if distinct else None, lie, kept,
-                            prior_weight, linear_forgetting, jkw)
+    rows = _pick(eng, pool, d, k, hist, distinct, st)
     if not len(rows):
         return []
     vals, active = take_rows(pool, d.rows_out, len(rows))

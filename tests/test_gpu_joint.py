@@ -73,14 +73,10 @@ def test_values_match_scalar_restatement():
     assert np.isnan(terms).all()  # a flat space: every label is joint
     assert _same_bits(S, Jd)
     # log L of each set by itself (an error common to both would cancel in J)
-    import torch
-    eng = tpe.engine()
-    parts = torch.empty((3, P_ROWS), dtype=torch.float64, device=eng.device)
-    pool_mod._score_device(domain, trials, pool, KW["prior_weight"], KW["gamma"],
-                           KW["linear_forgetting"], False,
-                           joint=dict(bandwidth=KW["bandwidth"],
-                                      cat_smoothing=KW["cat_smoothing"]), parts=parts)
-    lb, la, j2 = parts.cpu().numpy()
+    st = pool_mod._settings(KW["prior_weight"], KW["gamma"], KW["linear_forgetting"], True,
+                            KW["bandwidth"], KW["cat_smoothing"])
+    _eng, d = pool_mod._score_device(domain, trials, pool, st, False, want_parts=True)
+    lb, la, j2 = d.parts[:, :P_ROWS].cpu().numpy()
     assert _same_bits(j2, Jd)
     for got, ref in ((lb, ref_b), (la, ref_a)):
         np.testing.assert_array_equal(np.isneginf(got), np.isneginf(ref))
@@ -270,12 +266,11 @@ def test_limits_are_unsupported_and_bad_arguments_are_refused():
 
 # -- 7. a set without rows ---------------------------------------------------------
 @pytest.mark.parametrize("name", ["empty", "one", "foreign_below"])
-def test_a_set_without_rows_is_the_prior_alone(name):
+def test_a_set_without_rows_is_the_prior_alone(name, monkeypatch):
     """No trial, one trial (no above row) and a below set emptied by a foreign
     row, on pool rows whose fit coordinate is exactly 0 (x == 0.0, x == 1.0 on
     a log kind): the places of a pass past the last component must count for
     nothing, whatever their arithmetic gives."""
-    import torch
     domain = Domain(lambda x: 0, U.zero_coordinate_space(hp))
     configs, losses = U.small_histories()[name]
     trials = U.make_trials(domain, configs, losses)
@@ -284,12 +279,11 @@ def test_a_set_without_rows_is_the_prior_alone(name):
     ref_j, ref_b, ref_a, nb, na = U.joint_reference(domain, trials, pool.vals)
     assert (nb, na) == {"empty": (0, 0), "one": (1, 0), "foreign_below": (0, 2)}[name]
     assert np.isfinite(ref_j).all()
-    eng = tpe.engine()
-    parts = torch.full((3, P), float("nan"), dtype=torch.float64, device=eng.device)
-    pool_mod._score_device(domain, trials, pool, 1.0, 0.25, 25, False,
-                           joint=dict(bandwidth=J.BANDWIDTH, cat_smoothing=J.CAT_SMOOTHING),
-                           parts=parts)
-    lb, la, jd = parts.cpu().numpy()
+    st = pool_mod._settings(1.0, 0.25, 25, True, J.BANDWIDTH, J.CAT_SMOOTHING)
+    make = pool_mod._parts  # (NaN wherever the scoring writes nothing)
+    monkeypatch.setattr(pool_mod, "_parts", lambda *a: make(*a).fill_(float("nan")))
+    _eng, d = pool_mod._score_device(domain, trials, pool, st, False, want_parts=True)
+    lb, la, jd = d.parts[:, :P].cpu().numpy()
     for got, ref in ((lb, ref_b), (la, ref_a)):
         print(name, "max |log L - ref| = %.3g" % np.abs(got - ref).max())
         assert (np.abs(got - ref) <= 1e-6 * np.abs(ref)).all()

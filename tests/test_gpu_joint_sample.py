@@ -116,16 +116,14 @@ def test_all_kinds_through_the_prepared_set():
     domain, trials, hist = _all_kinds()
     eng = tpe.engine()
     t = eng.torch
-    isb, isa = tpe.split_masks(hist, KW["gamma"])
     nl = len(domain.params)
-    prepared = J.prepare_sets(eng, domain, hist, pool_mod._seen_rows(eng, hist), isb, isa, nl,
-                              KW["prior_weight"], KW["linear_forgetting"], KW["bandwidth"],
-                              KW["cat_smoothing"])
+    fit, = J.fit(eng, domain, hist, pool_mod._seen_rows(eng, hist), KW["gamma"], nl,
+                 KW["prior_weight"], KW["linear_forgetting"], KW["bandwidth"],
+                 KW["cat_smoothing"])
     n_rows, base = 300, 2 ** 32 - 3
     vals = t.full((nl, n_rows), float("nan"), dtype=t.float64, device=eng.device)
     comp = t.full((n_rows,), -7, dtype=t.int32, device=eng.device)
-    J.sample_device(eng, prepared, SEED, KW["prior_weight"], KW["linear_forgetting"],
-                    KW["cat_smoothing"], vals, n_rows, nl, base, n_rows, comp_out=comp)
+    J.sample_device(fit, SEED, vals, n_rows, nl, base, n_rows, comp_out=comp)
     models, rcomp, out = R.replay(domain, hist, SEED, base + np.arange(n_rows), **KW)
     np.testing.assert_array_equal(comp.cpu().numpy(), rcomp)
     got = vals.cpu().numpy()

@@ -282,19 +282,15 @@ def test_windows_keep_the_bits_and_stay_inside_their_buffers():
 # -- 4. the public path ------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(JC.PUBLIC))
 def test_public_path(name):
-    import torch
     c = JC.load()[name]
     domain, trials, rows, kw = JC.public_problem(c)
     pool = tpe.Pool(domain, rows)
     S, terms, Jd = tpe.score_configs(domain, trials, pool, joint=True, return_terms=True, **kw)
     assert _same_bits(S, Jd) and np.isnan(terms).all()
-    eng = tpe.engine()
-    parts = torch.empty((3, JC.P), dtype=torch.float64, device=eng.device)
-    pool_mod._score_device(domain, trials, pool, kw["prior_weight"], kw["gamma"],
-                           kw["linear_forgetting"], False,
-                           joint=dict(bandwidth=kw["bandwidth"], cat_smoothing=kw["cat_smoothing"]),
-                           parts=parts)
-    lb, la, j2 = parts.cpu().numpy()
+    st = pool_mod._settings(kw["prior_weight"], kw["gamma"], kw["linear_forgetting"], True,
+                            kw["bandwidth"], kw["cat_smoothing"])
+    _eng, d = pool_mod._score_device(domain, trials, pool, st, False, want_parts=True)
+    lb, la, j2 = d.parts[:, :JC.P].cpu().numpy()
     assert _same_bits(j2, Jd) and _same_bits(lb - la, Jd)
     _check(name, [("below", lb, c["logl"][0], c["cond"][0]),
                   ("above", la, c["logl"][1], c["cond"][1]),
@@ -306,7 +302,6 @@ def test_public_path(name):
 
 # -- 5. the all-kinds case of test_gpu_joint.py --------------------------------------
 def test_all_kinds_case_against_50_digits():
-    import torch
     from tests.test_gpu_joint import KW, P_ROWS, _all_kinds
     c = JC.load()["all_kinds"]
     domain, trials, pool, _ = _all_kinds()
@@ -317,12 +312,9 @@ def test_all_kinds_case_against_50_digits():
     shift = np.zeros(pool.vals.shape[1])
     shift[c["labels"]["col"]] = c["labels"]["shift"]
     assert _same_bits(np.asarray(pool.vals, np.float64)[ids] - shift[None, :], c["pool"])
-    eng = tpe.engine()
-    parts = torch.empty((3, P_ROWS), dtype=torch.float64, device=eng.device)
-    pool_mod._score_device(domain, trials, pool, KW["prior_weight"], KW["gamma"],
-                           KW["linear_forgetting"], False,
-                           joint=dict(bandwidth=KW["bandwidth"],
-                                      cat_smoothing=KW["cat_smoothing"]), parts=parts)
-    lb, la, _ = parts.cpu().numpy()
+    st = pool_mod._settings(KW["prior_weight"], KW["gamma"], KW["linear_forgetting"], True,
+                            KW["bandwidth"], KW["cat_smoothing"])
+    _eng, d = pool_mod._score_device(domain, trials, pool, st, False, want_parts=True)
+    lb, la, _ = d.parts[:, :P_ROWS].cpu().numpy()
     _check("all kinds", [("below", lb[ids], c["logl"][0], c["cond"][0]),
                          ("above", la[ids], c["logl"][1], c["cond"][1])])

@@ -128,11 +128,11 @@ class _Scorer(object):
         domain, trials, pool, _ = _all_kinds()
         eng = tpe.engine()
         hist = tpe.collect_history(trials, pool.labels)
-        isb, isa = tpe.split_masks(hist, KW["gamma"])
         self.n_cols = len(pool.labels)
-        self.dj, self.sets, self.sp = J.prepare_sets(
-            eng, domain, hist, pool_mod._seen_rows(eng, hist), isb, isa, self.n_cols,
-            KW["prior_weight"], KW["linear_forgetting"], KW["bandwidth"], KW["cat_smoothing"])
+        fit, = J.fit(eng, domain, hist, pool_mod._seen_rows(eng, hist), KW["gamma"], self.n_cols,
+                     KW["prior_weight"], KW["linear_forgetting"], KW["bandwidth"],
+                     KW["cat_smoothing"])
+        self.dj, self.sets, self.sp = fit.dj, fit.sets, fit.sp
         assert [n for _, n, _ in self.sets] == [7, 613]
         self.P = P_ROWS
         self.vals = pool.device(eng).vals

@@ -188,8 +188,8 @@ def test_argument_errors():
 
 def test_batch_none_builds_the_call_it_always_built(monkeypatch):
     """``batch=None`` goes through ``_score_device`` and ``_topk_device`` with
-    the arguments of the code before ``batch`` existed: no parts buffer, no
-    kept sets, the same mask."""
+    the arguments of the code before ``batch`` existed: no parts asked for,
+    settings without a lie, the same mask."""
     domain, trials, _hist, vals, _S0, _A0 = _all_kinds()
     labels = list(domain.params)
     pool = tpe.Pool.from_arrays(domain, vals[:8], np.ones((8, len(labels)), bool))
@@ -223,7 +223,9 @@ def test_batch_none_builds_the_call_it_always_built(monkeypatch):
         assert [c[0] for c in calls] == ["score", "distinct", "topk"]
         _, args, skw = calls[0]
         assert args[:2] == (domain, trials) and args[2] is pool
-        assert args[3:] == (0.7, 0.3, 25, False)
-        assert set(skw) == {"hist", "joint"}
-        assert skw["joint"] == dict(bandwidth=0.25, cat_smoothing=0.5, tree=False)
+        st = args[3]
+        assert (st.prior_weight, st.gamma, st.lf, st.lie) == (0.7, 0.3, 25, None)
+        assert args[4:] == (False,)
+        assert set(skw) == {"hist"}
+        assert st.joint == dict(bandwidth=0.25, cat_smoothing=0.5, tree=False)
         assert calls[2][1] == ("eng", _Dev, 8, 2, "the distinct mask")

@@ -64,6 +64,7 @@ def main():
     vals, losses = bench.c3_history(SPACE)
     domain, trials = bench.c3_trials(SPACE, vals, losses)
     pw, gamma, lf = 1.0, 0.25, 25
+    st = pool_mod._Settings(pw, gamma, lf)
     results = []
     for lg in args.log2:
         P = 1 << lg
@@ -72,14 +73,14 @@ def main():
         pool = grid.to_pool() if args.only in ("both", "pool") else None
 
         def run_grid():
-            eng, d = pool_mod._score_device(domain, trials, grid, pw, gamma, lf, False)
+            eng, d = pool_mod._score_device(domain, trials, grid, st, False)
             return pool_mod._topk_device(eng, d, P, K), d  # (the row copy synchronises)
 
         def run_grid_score():
-            return pool_mod._score_device(domain, trials, grid, pw, gamma, lf, False)
+            return pool_mod._score_device(domain, trials, grid, st, False)
 
         def run_pool():
-            eng, d = pool_mod._score_device(domain, trials, pool, pw, gamma, lf, False)
+            eng, d = pool_mod._score_device(domain, trials, pool, st, False)
             return pool_mod._topk_device(eng, d, P, K), d
 
         fns = {"grid": run_grid, "grid_score": run_grid_score, "pool": run_pool}

@@ -56,7 +56,6 @@ def main():
     kw = dict(prior_weight=1.0, gamma=0.25, linear_forgetting=25)
     eng = tpe.engine()
     hist = tpe.collect_history(trials, labels)
-    isb, isa = tpe.split_masks(hist, kw["gamma"])
     results = []
     for lg in args.log2:
         P = 1 << lg
@@ -75,24 +74,22 @@ def main():
                 if rep >= args.warmup:
                     times[name].append(time.perf_counter() - t0)
         # the sampler kernel alone
-        prepared = J.prepare_sets(eng, domain, hist, pool_mod._seen_rows(eng, hist), isb, isa,
-                                  len(labels), kw["prior_weight"], kw["linear_forgetting"],
-                                  J.BANDWIDTH, J.CAT_SMOOTHING)
+        fit, = J.fit(eng, domain, hist, pool_mod._seen_rows(eng, hist), kw["gamma"], len(labels),
+                     kw["prior_weight"], kw["linear_forgetting"], J.BANDWIDTH, J.CAT_SMOOTHING)
         out = torch.empty((len(labels), P), dtype=torch.float64, device=eng.device)
         kern = []
         for rep in range(args.warmup + args.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             e0.record()
-            J.sample_device(eng, prepared, SEED, kw["prior_weight"], kw["linear_forgetting"],
-                            J.CAT_SMOOTHING, out, P, len(labels), 0, P)
+            J.sample_device(fit, SEED, out, P, len(labels), 0, P)
             e1.record()
             torch.cuda.synchronize()
             if rep >= args.warmup:
                 kern.append(1e-3 * e0.elapsed_time(e1))
         times["sampler"] = kern  # (its three small uploads included)
         rec = {"P": P, "labels": len(labels), "joint_labels": len(J.joint_labels(domain)),
-               "history": int(losses.size), "n_below": int(prepared[1][0][1]), "reps": args.reps}
+               "history": int(losses.size), "n_below": int(fit.sets[0][1]), "reps": args.reps}
         for name, ts in times.items():
             ts = np.sort(ts)
             rec[name + "_p50_ms"] = 1e3 * float(np.median(ts))

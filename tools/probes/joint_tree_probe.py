@@ -161,11 +161,11 @@ def main():
 
         # (b) the list scorer by itself, on dense draws of the first branch's group
         hist = tpe.collect_history(trials, labels)
-        isb, isa = tpe.split_masks(hist, kw["gamma"])
         grp = groups[1]
-        dj, sets, sp = J.prepare_sets(eng, domain, hist, pool_mod._seen_rows(eng, hist), isb, isa,
-                                      len(labels), 1.0, 25, J.BANDWIDTH, J.CAT_SMOOTHING,
-                                      group=grp.labels)
+        fit = J.fit(eng, domain, hist, pool_mod._seen_rows(eng, hist), kw["gamma"], len(labels),
+                    1.0, 25, J.BANDWIDTH, J.CAT_SMOOTHING, tree=True)[1]
+        assert fit.group == grp.labels
+        dj, sets, sp = fit.dj, fit.sets, fit.sp
         dset, n, _ = sets[1]
         rec["b_labels"], rec["b_components"] = len(grp.labels), n + 1
         dev = eng.device

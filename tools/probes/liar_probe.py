@@ -78,27 +78,31 @@ def main():
     domain, trials = bench.c3_trials(space, vals, losses)
     models = J.label_models(domain)
     kw = dict(prior_weight=1.0, gamma=0.25, linear_forgetting=25)
-    jkw = pool_mod._joint_kw(True, J.BANDWIDTH, J.CAT_SMOOTHING)
+    st = pool_mod._settings(1.0, 0.25, 25, True, J.BANDWIDTH, J.CAT_SMOOTHING, "liar", 1.0)
     k = args.k
     results = []
     for lg, source in [(lg, s) for lg in args.log2 for s in args.pools]:
         P = 1 << lg
-        eng, kept = tpe.engine(), {}
+        eng = tpe.engine()
         if source == "prior":  # prior draws, scored
             pool = c3_pool(domain, space, P)
-            parts = torch.empty((3, P), dtype=torch.float64, device=eng.device)
-            eng, d = pool_mod._score_device(domain, trials, pool, 1.0, 0.25, 25, False,
-                                            joint=jkw, parts=parts, kept=kept)
+            eng, d = pool_mod._score_device(domain, trials, pool, st, False)
         else:  # rows drawn from the joint below mixture, born scored (draw="joint")
-            pool = pool_mod._sample(domain, trials, 7, P, 1.0, 0.25, 25, False, joint=jkw,
-                                    kept=kept)
+            pool = pool_mod._sample(domain, trials, 7, P, st, False)
             d = pool._born()
         S0 = d.S[:P].cpu().numpy()
-        A0 = kept["parts"][1, :P].cpu().numpy()
+        A0 = d.parts[1, :P].cpu().numpy()
+        left = d.fits, d.parts  # (what the liar scoring left)
+
+        def score():
+            S = tpe.score_configs(domain, trials, pool, joint=True, **kw)
+            d.fits, d.parts = left  # (a scoring without the batch clears them)
+            return S
+
         fns = {
             "topk": lambda: pool_mod._topk_device(eng, d, P, k),
-            "liar": lambda: pool_mod._liar_device(eng, d, P, k, None, 1.0, kept, 1.0, 25, jkw),
-            "score": lambda: tpe.score_configs(domain, trials, pool, joint=True, **kw),
+            "liar": lambda: pool_mod._liar_device(eng, d, P, k, None, st.lie),
+            "score": score,
         }
         times = {n: [] for n in fns}
         last = {}

@@ -87,8 +87,8 @@ def main():
         pool = c3_pool(domain, space, P)
 
         def run_pool():
-            eng, d = pool_mod._score_device(domain, trials, pool, kw["prior_weight"],
-                                            kw["gamma"], 25, False)
+            st = pool_mod._Settings(kw["prior_weight"], kw["gamma"], 25)
+            eng, d = pool_mod._score_device(domain, trials, pool, st, False)
             return pool_mod._topk_device(eng, d, P, K), d  # (the row copy synchronises)
 
         def run_baseline():

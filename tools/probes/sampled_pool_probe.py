@@ -84,7 +84,8 @@ def main():
                         for (j, _), r in zip(part, res):
                             cols[:, j] = r.cand
             pool = tpe.Pool.from_arrays(domain, cols, np.ones(cols.shape, bool))
-            eng, d = pool_mod._score_device(domain, trials, pool, 1.0, 0.25, 25, False)
+            eng, d = pool_mod._score_device(domain, trials, pool,
+                                            pool_mod._Settings(1.0, 0.25, 25), False)
             rows = pool_mod._topk_device(eng, d, P, K)
             return rows, cols[rows], d.S[:P].cpu().numpy()
 
