@@ -135,6 +135,7 @@ _SIGNATURES = {
     "tpe_history_order_scratch_bytes": (_I64, [_I, _I64]),
     "tpe_history_order": (_I, [_P, _I64, _P, _P, _I, _I64, _I64, _P, _P, _P]),
     "tpe_fit_sorted_scratch_bytes": (_I64, [_I, _I64]),
+    "tpe_fit_sorted_layout": (_I, [_I, _I64, _P, _I]),
     "tpe_fit_sorted": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P]),
     "tpe_pruned64_partials": (_I64, [_P, _I]),

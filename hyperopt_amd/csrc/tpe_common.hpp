@@ -250,10 +250,17 @@ __device__ __forceinline__ double obs_transform(double v, int transform, double 
   return v;
 }
 
+// the history gather (tpe_history.hip): one block per descriptor, kGatherTiles
+// tiles of kGatherBS positions per pass (tpe_fit_sorted_layout reports the pass)
+constexpr int kGatherBS = 1024;
+constexpr int kGatherTiles = 16;
+constexpr int kGatherPass = kGatherBS * kGatherTiles;
+
 // the fit's bandwidth / coefficient launches (tpe_parzen.hip), shared by
 // tpe_parzen_fit and tpe_fit_sorted
 int64_t fit_part_doubles(int max_obs);
 void fit_tail(tpe_seg* segs, int n_seg, int max_obs, double* part, double* w, const double* mu,
-              double* sigma, double* wcdf, double* coef64, float* coef32, hipStream_t st);
+              double* sigma, double* wcdf, double* coef64, float* coef32, hipStream_t st,
+              const int32_t* skip = nullptr);
 
 }  // namespace tpe

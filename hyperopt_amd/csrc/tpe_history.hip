@@ -15,9 +15,9 @@
 
 namespace tpe {
 namespace {
-constexpr int kGBS = 1024;
+constexpr int kGBS = kGatherBS;
 constexpr int kGWaves = kGBS / kWave;
-constexpr int kGT = 16;                 // 1024-row tiles per pass (16 384 rows)
+constexpr int kGT = kGatherTiles;       // 1024-row tiles per pass (16 384 rows)
 constexpr int kGSlots = kGT * kGWaves;  // (tile, wave) counts scanned per pass
 
 // Compacts one descriptor's rows (block-wide, in position order).  A pass

@@ -48,7 +48,7 @@ __host__ __device__ __forceinline__ int64_t align_up(int64_t x, int64_t a) {
   return (x + a - 1) / a * a;
 }
 __host__ __device__ __forceinline__ int64_t comp_tiles(int max_obs) {
-  return (max_obs + 1 + kFitBS - 1) / kFitBS;
+  return ((int64_t)max_obs + 1 + kFitBS - 1) / kFitBS;  // (64-bit: max_obs up to INT32_MAX)
 }
 __host__ __device__ __forceinline__ FitScratch carve(void* base, int n_seg, int max_obs,
                                                      int64_t n_obs_total) {
@@ -232,11 +232,13 @@ __global__ __launch_bounds__(kFitBS) void k_fit_rank(tpe_seg* __restrict__ segs,
 __global__ __launch_bounds__(kFitBS) void k_fit_comp(const tpe_seg* __restrict__ segs,
                                                      FitScratch sc, const double* __restrict__ w,
                                                      const double* __restrict__ mu,
-                                                     double* __restrict__ sigma) {
+                                                     double* __restrict__ sigma,
+                                                     const int32_t* __restrict__ skip) {
   __shared__ double red[kFitBS / kWave];
   const tpe_seg& S = segs[blockIdx.y];
   const int n = S.n_obs, nc = n + 1, pos = S.prior_pos;
   if (blockIdx.x * kFitBS >= nc) return;  // block-uniform
+  if (skip && skip[blockIdx.y]) return;  // tpe_fit_sorted found another count: nothing written
   const int k = blockIdx.x * kFitBS + threadIdx.x;
   const int64_t off = S.comp_off;
   const double ps = S.prior_sigma;
@@ -283,13 +285,15 @@ __global__ __launch_bounds__(kFitBS) void k_fit_coef(tpe_seg* __restrict__ segs,
                                                      const double* __restrict__ mu,
                                                      const double* __restrict__ sigma,
                                                      double* __restrict__ wcdf,
-                                                     double* __restrict__ coef64) {
+                                                     double* __restrict__ coef64,
+                                                     const int32_t* __restrict__ skip) {
   __shared__ double red[kFitBS / kWave];
   __shared__ double wscan[kFitBS / kWave];
   tpe_seg* S = segs + blockIdx.y;
   const int nc = S->n_obs + 1;
   const int tiles = (nc + kFitBS - 1) / kFitBS;
   if ((int)blockIdx.x >= tiles) return;  // block-uniform
+  if (skip && skip[blockIdx.y]) return;  // (see k_fit_comp)
   const double* P = sc.part + (int64_t)blockIdx.y * gridDim.x * kPartStride;
   // every block re-reduces the (few) tile partials in the same order
   double a = 0.0, b = 0.0, before = 0.0;
@@ -351,12 +355,14 @@ __global__ __launch_bounds__(kFitBS) void k_fit_coef(tpe_seg* __restrict__ segs,
 //     t = xc*a + b,  v = c - t^2,  term = 2^v  (v <= 0, offset cmax)
 __global__ __launch_bounds__(kFitBS) void k_fit_coef32(tpe_seg* __restrict__ segs, FitScratch sc,
                                                        const double* __restrict__ coef64,
-                                                       float* __restrict__ coef32) {
+                                                       float* __restrict__ coef32,
+                                                       const int32_t* __restrict__ skip) {
   __shared__ double red[kFitBS / kWave];
   tpe_seg* S = segs + blockIdx.y;
   const int nc = S->n_obs + 1;
   const int tiles = (nc + kFitBS - 1) / kFitBS;
   if ((int)blockIdx.x >= tiles) return;
+  if (skip && skip[blockIdx.y]) return;  // (see k_fit_comp)
   const double* P = sc.part + (int64_t)blockIdx.y * gridDim.x * kPartStride;
   double mx = -INFINITY;
   for (int t = threadIdx.x; t < tiles; t += kFitBS) mx = fmax(mx, P[t * kPartStride + 2]);
@@ -494,15 +500,18 @@ __global__ __launch_bounds__(kFitBS) void k_fit_prune(tpe_seg* __restrict__ segs
 // set): shared with tpe_fit_sorted (tpe_sorted.hip), whose compaction
 // replaces K1-K2.  part: n_seg * fit_part_doubles(max_obs) doubles.
 int64_t fit_part_doubles(int max_obs) { return comp_tiles(max_obs) * kPartStride; }
+// skip (nullable): one int32 per segment, nonzero = leave the segment alone.
 void fit_tail(tpe_seg* segs, int n_seg, int max_obs, double* part, double* w, const double* mu,
-              double* sigma, double* wcdf, double* coef64, float* coef32, hipStream_t st) {
+              double* sigma, double* wcdf, double* coef64, float* coef32, hipStream_t st,
+              const int32_t* skip) {
   const FitScratch sc{nullptr, nullptr, nullptr, part};
   const int gc = (int)comp_tiles(max_obs);
-  hipLaunchKernelGGL(k_fit_comp, dim3(gc, n_seg), dim3(kFitBS), 0, st, segs, sc, w, mu, sigma);
+  hipLaunchKernelGGL(k_fit_comp, dim3(gc, n_seg), dim3(kFitBS), 0, st, segs, sc, w, mu, sigma,
+                     skip);
   hipLaunchKernelGGL(k_fit_coef, dim3(gc, n_seg), dim3(kFitBS), 0, st, segs, sc, w, mu, sigma,
-                     wcdf, coef64);
+                     wcdf, coef64, skip);
   hipLaunchKernelGGL(k_fit_coef32, dim3(gc, n_seg), dim3(kFitBS), 0, st, segs, sc, coef64,
-                     coef32);
+                     coef32, skip);
 }
 }  // namespace tpe
 

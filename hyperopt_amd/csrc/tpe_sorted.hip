@@ -285,14 +285,16 @@ __global__ __launch_bounds__(kCB) void k_fit_globalize(int64_t n_rows,
 // K3: sorted-order emit -- means and ramp weights in sorted order, the prior
 // at its slot: searchsorted(obs, prior_mu, 'left') (tpe.py:427), or the
 // len == 1 rule (tpe.py:414-421).  A count other than gathers[sg].count sets
-// bit 4 of *err and writes nothing.
+// bit 4 of *err and skip[sg] (on which the fit's tail returns) and writes
+// nothing to the pools or the segment.
 template <bool LOCAL>  // LOCAL: the words are chunk-local ranks (K2 skipped)
 __global__ __launch_bounds__(kCB) void k_fit_emit_sorted(
     const double* __restrict__ vals, const uint8_t* __restrict__ active, int64_t ld,
     const int32_t* __restrict__ order, int64_t n_rows, const uint8_t* __restrict__ is_below,
     const tpe_gather* __restrict__ gathers, tpe_seg* __restrict__ segs,
     const int32_t* __restrict__ cnt, const int32_t* __restrict__ gi_scr,
-    double* __restrict__ w, double* __restrict__ mu, int32_t* __restrict__ err) {
+    double* __restrict__ w, double* __restrict__ mu, int32_t* __restrict__ err,
+    int32_t* __restrict__ skip) {
   __shared__ int sh[kCR * (kCB / kWave)];
   __shared__ int64_t sh64[kCB / kWave];
   __shared__ int32_t s_pre[LOCAL ? kPreChunks : 1];  // tid chunks' member bases
@@ -303,6 +305,8 @@ __global__ __launch_bounds__(kCB) void k_fit_emit_sorted(
   const int nch = gridDim.x;
   const int32_t* C = cnt + (int64_t)sg * nch * kCnt;
   const int64_t n = chunks_before(C, nch, 0, sh64);
+  // skip[sg]: the fit's tail leaves a segment of another count alone
+  if (blockIdx.x == 0 && threadIdx.x == 0) skip[sg] = n != G.count ? 1 : 0;
   if (n != G.count) {  // the segment was sized for another count: nothing written
     if (blockIdx.x == 0 && threadIdx.x == 0 && err) atomicOr(err, 4);
     return;
@@ -413,7 +417,8 @@ extern "C" int tpe_history_order(const double* vals, int64_t ld, const tpe_colsp
 }
 
 // scratch: the per-row list positions (int32 per segment and row), the chunk
-// counts, then the fit tail's tile partials (counts are <= n_rows)
+// counts, the fit tail's tile partials (counts are <= n_rows), then one
+// int32 per segment: 1 where the compaction found another count
 static int64_t gi_bytes(int n_seg, int64_t n_rows) {
   return (4 * (int64_t)std::max(n_seg, 1) * std::max<int64_t>(n_rows, 1) + 255) / 256 * 256;
 }
@@ -421,10 +426,35 @@ static int64_t n_chunks(int64_t n_rows) { return std::max<int64_t>(1, (n_rows + 
 static int64_t cnt_bytes(int n_seg, int64_t n_rows) {
   return (4 * kCnt * (int64_t)std::max(n_seg, 1) * n_chunks(n_rows) + 255) / 256 * 256;
 }
+// byte offsets of the three regions and the total: tpe_fit_sorted,
+// tpe_fit_sorted_scratch_bytes and tpe_fit_sorted_layout all read them here
+struct FitSortedLayout {
+  int64_t gi, cnt, part, skip, total;  // skip: one int32 per segment, after the partials
+};
+static FitSortedLayout fit_sorted_layout(int n_seg, int64_t n_rows) {
+  FitSortedLayout p;
+  p.gi = 0;
+  p.cnt = p.gi + gi_bytes(n_seg, n_rows);
+  p.part = p.cnt + cnt_bytes(n_seg, n_rows);
+  p.skip = p.part + 8 * (int64_t)std::max(n_seg, 1) * fit_part_doubles((int)n_rows);
+  p.total = p.skip + (4 * (int64_t)std::max(n_seg, 1) + 255) / 256 * 256;
+  return p;
+}
 extern "C" int64_t tpe_fit_sorted_scratch_bytes(int n_seg, int64_t n_rows) {
   if (n_seg < 0 || n_rows < 0 || n_rows > INT32_MAX) return -1;
-  return gi_bytes(n_seg, n_rows) + cnt_bytes(n_seg, n_rows) +
-         8 * (int64_t)std::max(n_seg, 1) * fit_part_doubles((int)n_rows);
+  return fit_sorted_layout(n_seg, n_rows).total;
+}
+
+extern "C" int tpe_fit_sorted_layout(int n_seg, int64_t n_rows, int64_t* out, int n) {
+  if (n_seg < 0 || n_rows < 0 || n_rows > INT32_MAX || n < 0 || (n > 0 && !out)) {
+    set_error("tpe_fit_sorted_layout: n_seg=%d n_rows=%lld n=%d", n_seg, (long long)n_rows, n);
+    return -1;
+  }
+  const FitSortedLayout p = fit_sorted_layout(n_seg, n_rows);
+  const int64_t v[9] = {p.gi, p.cnt, p.part, p.total, kChunk, kCnt, kPreChunks, kGatherPass, kNew};
+  const int m = n < 9 ? n : 9;
+  for (int i = 0; i < m; ++i) out[i] = v[i];
+  return m;
 }
 
 extern "C" int tpe_fit_sorted(const double* vals, const uint8_t* active, int64_t ld,
@@ -456,9 +486,11 @@ extern "C" int tpe_fit_sorted(const double* vals, const uint8_t* active, int64_t
   for (int i = 0; i < n_seg; ++i) max_obs = std::max(max_obs, (int)host_gathers[i].count);
   hipStream_t st = (hipStream_t)stream;
   char* p = static_cast<char*>(scratch);
-  int32_t* gi = reinterpret_cast<int32_t*>(p);
-  int32_t* cnt = reinterpret_cast<int32_t*>(p + gi_bytes(n_seg, n_rows));
-  double* part = reinterpret_cast<double*>(p + gi_bytes(n_seg, n_rows) + cnt_bytes(n_seg, n_rows));
+  const FitSortedLayout lay = fit_sorted_layout(n_seg, n_rows);
+  int32_t* gi = reinterpret_cast<int32_t*>(p + lay.gi);
+  int32_t* cnt = reinterpret_cast<int32_t*>(p + lay.cnt);
+  double* part = reinterpret_cast<double*>(p + lay.part);
+  int32_t* skip = reinterpret_cast<int32_t*>(p + lay.skip);
   const dim3 grid((unsigned)n_chunks(n_rows), (unsigned)n_seg);
   hipLaunchKernelGGL(k_fit_count, grid, dim3(kCB), 0, st, vals, active, ld, order, n_rows,
                      is_below, gathers, segs, cnt, gi);
@@ -466,12 +498,12 @@ extern "C" int tpe_fit_sorted(const double* vals, const uint8_t* active, int64_t
   const char* gl = getenv("TPE_FIT_GLOBALIZE");
   if (n_chunks(n_rows) <= kPreChunks && !(gl && gl[0] == '1')) {
     hipLaunchKernelGGL(k_fit_emit_sorted<true>, grid, dim3(kCB), 0, st, vals, active, ld, order,
-                       n_rows, is_below, gathers, segs, cnt, gi, w, mu, err);
+                       n_rows, is_below, gathers, segs, cnt, gi, w, mu, err, skip);
   } else {
     hipLaunchKernelGGL(k_fit_globalize, grid, dim3(kCB), 0, st, n_rows, cnt, gi);
     hipLaunchKernelGGL(k_fit_emit_sorted<false>, grid, dim3(kCB), 0, st, vals, active, ld, order,
-                       n_rows, is_below, gathers, segs, cnt, gi, w, mu, err);
+                       n_rows, is_below, gathers, segs, cnt, gi, w, mu, err, skip);
   }
-  fit_tail(segs, n_seg, max_obs, part, w, mu, sigma, wcdf, coef64, coef32, st);
+  fit_tail(segs, n_seg, max_obs, part, w, mu, sigma, wcdf, coef64, coef32, st, skip);
   return check_launch("tpe_fit_sorted");
 }

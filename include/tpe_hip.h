@@ -237,17 +237,46 @@ int tpe_history_order(const double* vals, int64_t ld, const tpe_colspec* specs,
 /* The fit of segment i (segs[i]) from the sorted history: gathers[i] names its
  * column, side (below: 1) and observation count (identity row list: row r of
  * the history is position r, is_below[r] its split flag, n_rows of them).
- * One compaction block per segment: the segment's rows in tid order
- * (linear-forgetting positions, the prior's searchsorted slot), then the
- * column's order compacted to the segment (means and weights in sorted
- * order); then tpe_parzen_fit's own bandwidth / coefficient launches (same
- * bits).  A count other than gathers[i].count sets bit 4 of *err (the
- * segment's means are not written; the call's results are void).
+ * A chunked compaction, one block per (chunk of rows, segment), in two
+ * launches (three for very long columns): first the rows in tid order -- per
+ * chunk the member count, how many members lie below the prior mean (its
+ * searchsorted slot), the first member row, and every row's rank among its
+ * chunk's members (the linear-forgetting positions once the chunk bases are
+ * added) --, then the column's order compacted to the segment (means and
+ * weights in sorted order); then tpe_parzen_fit's own bandwidth /
+ * coefficient launches (same bits).  A count other than gathers[i].count
+ * sets bit 4 of *err: nothing of that segment is written, neither to the
+ * pools nor to segs[i] (the bandwidth / coefficient launches skip it), and
+ * the call's results are void.
  * Precondition: `order` holds, per column, a permutation of the rows
  * [0, n_rows) -- n_rows must be the history's row count (tpe_history_order's
  * n_rows), so is_below must hold exactly one flag per history row.
- * scratch: tpe_fit_sorted_scratch_bytes(n_seg, n_rows) bytes. */
+ * scratch: tpe_fit_sorted_scratch_bytes(n_seg, n_rows) bytes.
+ *
+ * tpe_fit_sorted_layout (host only, no GPU call): where a call with these
+ * (n_seg, n_rows) keeps its intermediate state in `scratch`, which is still
+ * there when the call has ended, and the sizes the history kernels cut their
+ * work by.  Writes up to n of these nine numbers to out and returns how many
+ * it wrote (-1: bad arguments):
+ *   [0] byte offset of the rank words, one int32 per (segment, row) at
+ *       segment * n_rows + row: -1 for a row that is not a member, else the
+ *       row's rank among the members of its chunk of out[4] rows (its
+ *       position in the segment's whole tid-ordered list where the globalize
+ *       path ran),
+ *   [1] byte offset of the chunk counts, out[5] int32 per (segment, chunk) at
+ *       segment * chunks + chunk: members in the chunk of rows, how many of
+ *       them have a key below the prior mean's, the first member row
+ *       (INT32_MAX: none), members in the same chunk of the sorted order,
+ *   [2] byte offset of the fit tail's partials (after them, up to the total,
+ *       one int32 per segment: 1 where the count differed),
+ *   [3] the total, tpe_fit_sorted_scratch_bytes(n_seg, n_rows),
+ *   [4] rows per chunk, [5] ints per count record,
+ *   [6] the chunk count above which the ranks are globalized in a launch of
+ *       their own,
+ *   [7] positions per pass of tpe_gather_obs / tpe_gather_obs_multi,
+ *   [8] the most new rows one tpe_history_order call takes. */
 int64_t tpe_fit_sorted_scratch_bytes(int n_seg, int64_t n_rows);
+int tpe_fit_sorted_layout(int n_seg, int64_t n_rows, int64_t* out, int n);
 int tpe_fit_sorted(const double* vals, const uint8_t* active, int64_t ld, const int32_t* order,
                    int64_t n_rows, const uint8_t* is_below, const tpe_gather* gathers,
                    const tpe_gather* host_gathers, tpe_seg* segs, int n_seg, void* scratch,
