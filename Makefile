@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := hyperopt_amd/csrc
-SRCS := $(CSRC)/tpe_fit.hip $(CSRC)/tpe_parzen.hip $(CSRC)/tpe_score.hip $(CSRC)/tpe_quantized.hip $(CSRC)/tpe_categorical.hip $(CSRC)/tpe_table.hip $(CSRC)/tpe_table_score.hip $(CSRC)/tpe_band.hip $(CSRC)/tpe_pruned64.hip $(CSRC)/tpe_history.hip $(CSRC)/tpe_sorted.hip $(CSRC)/tpe_prior.hip $(CSRC)/tpe_anneal.hip $(CSRC)/tpe_pool.hip $(CSRC)/tpe_sampled.hip $(CSRC)/tpe_distinct.hip $(CSRC)/tpe_grid.hip $(CSRC)/tpe_grid_joint.hip $(CSRC)/tpe_joint.hip $(CSRC)/tpe_joint_sample.hip $(CSRC)/tpe_joint_tree.hip $(CSRC)/tpe_joint_lie.hip $(CSRC)/tpe_dist.hip $(CSRC)/tpe_util.hip $(CSRC)/tpe_ops.hip
+SRCS := $(CSRC)/tpe_fit.hip $(CSRC)/tpe_parzen.hip $(CSRC)/tpe_score.hip $(CSRC)/tpe_quantized.hip $(CSRC)/tpe_categorical.hip $(CSRC)/tpe_table.hip $(CSRC)/tpe_table_score.hip $(CSRC)/tpe_band.hip $(CSRC)/tpe_pruned64.hip $(CSRC)/tpe_history.hip $(CSRC)/tpe_sorted.hip $(CSRC)/tpe_prior.hip $(CSRC)/tpe_anneal.hip $(CSRC)/tpe_pool.hip $(CSRC)/tpe_sampled.hip $(CSRC)/tpe_distinct.hip $(CSRC)/tpe_grid.hip $(CSRC)/tpe_grid_joint.hip $(CSRC)/tpe_joint.hip $(CSRC)/tpe_joint_sample.hip $(CSRC)/tpe_joint_tree.hip $(CSRC)/tpe_joint_chain.hip $(CSRC)/tpe_joint_lie.hip $(CSRC)/tpe_dist.hip $(CSRC)/tpe_util.hip $(CSRC)/tpe_ops.hip
 OBJS := $(SRCS:.hip=.o)
 LIB := hyperopt_amd/libtpe_hip.so
 # -ffp-contract=off: no implicit FMA fusion, so expressions written to

@@ -195,6 +195,9 @@ _SIGNATURES = {
     "tpe_rows_compact": (_I, [_P, _I64, _P, _P, _P, _P]),
     "tpe_joint_score_rows": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64,
                                   _I64, _P, _P, _I, _P, _P]),
+    "tpe_joint_chain_scratch_bytes": (_I64, [_I64, _I64]),
+    "tpe_joint_chain_rows": (_I, [_P, _P, _I, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64,
+                                  _I64, _P, _P, _I, _P, _P]),
     "tpe_joint_lie_scratch_bytes": (_I64, [_I64]),
     "tpe_joint_lie_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _I64, _P, _P,
                                  ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P, _P, _P, _P,

@@ -14,6 +14,10 @@
 //      chunk's first component), tile (kJMaxD * kJPer JComp of LDS)
 // out: m, s -- the running maximum and sum of the chunk's a_i.  Every thread
 //      of the kJBS block walks it (it syncs on `tile`).
+// With TPE_JOINT_PASS_CTX defined (k_joint_chain_rows in tpe_joint_chain.hip,
+// which undefines it again) also in: n_ctx in (0, n_labels), and m_ctx = -inf,
+// s_ctx = 0 declared by the kernel; out: m_ctx, s_ctx -- the same running pair
+// over the a_i cut off after the first n_ctx labels.
   double m = kNegInf, s = 0.0;
   for (int64_t i0 = i_first; i0 < i_first + kJChunk && i0 < C; i0 += kJPer) {
     __syncthreads();  // (the previous pass has read the tile)
@@ -27,6 +31,32 @@
     for (int k = 0; k < kJPer; ++k) a[k] = i0 + k < C ? logw[i0 + k] : kNegInf;
     const int k_prior = n - i0 < kJPer ? (int)(n - i0) : -1;  // the prior's place in this pass
     for (int d = 0; d < n_labels; ++d) {
+#if defined(TPE_JOINT_PASS_CTX)
+      // (k_joint_chain_rows alone defines it: the two scorers' text is unchanged)
+      // at the label boundary a[] holds the a_i of the first n_ctx labels: it
+      // joins a second running (m_ctx, s_ctx) by the pass's join below, word
+      // for word, and the walk goes on to the full a_i in the same registers
+      if (d == n_ctx) {
+#pragma unroll
+        for (int k = 0; k < kJPer; ++k)
+          if (i0 + k >= C) a[k] = kNegInf;
+        double pm = a[0];
+#pragma unroll
+        for (int k = 1; k < kJPer; ++k) pm = a[k] > pm ? a[k] : pm;
+        if (pm > m_ctx) {
+          s_ctx = s_ctx * exp(m_ctx - pm);
+          m_ctx = pm;
+        }
+#pragma unroll 1
+        for (int k = 0; k < kJPer; ++k) {
+          const double head = a[0];
+          s_ctx = s_ctx + (head == kNegInf ? 0.0 : exp(head - m_ctx));
+#pragma unroll
+          for (int j = 0; j + 1 < kJPer; ++j) a[j] = a[j + 1];
+          a[kJPer - 1] = head;
+        }
+      }
+#endif
       const tpe_joint_label lab = labels[d];
       const double x = vals[(int64_t)lab.col * ld + row];
       const JComp* __restrict__ t = tile + d * kJPer;

@@ -182,10 +182,66 @@ rows that differ under a ``switch`` alone get the same penalty.
 ``liar_numpy`` is this definition in numpy; ``liar_device`` enqueues all k
 picks in one call (a pick's row is read on the device) and reads back the rows.
 
-Not built: a group conditioned on its ancestors' non-selector labels -- the
-chain-rule ratio L(ctx + g) / L(ctx), which would see a root label interact
-with a branch label.  Groups are independent mixtures.  ``batch="liar"`` under
-``joint="tree"`` (it needs log L_above per group, which ``score_tree_device``
+Chains (``joint="chain"``, csrc/tpe_joint_chain.hip).  The
+groups above are independent mixtures: a label at the root (a tile size) that
+is good only together with a label inside one branch (that variant's unroll
+factor) is ranked by two separate terms.  ``joint="chain"`` conditions every
+group on the labels around it by the chain rule: group g contributes the ratio
+L(ctx + g) / L(ctx).
+
+  groups       those of ``joint_groups(domain)``: the same groups, the same
+               order, the same global split.
+  context      ``ctx(g)`` of a group g that is not the root: the labels l
+               outside g, in ``domain.params`` order, with both properties
+               (``prog`` = ``domain.live_program()``): (1) l is live whenever g
+               is -- for every clause c of g some clause of ``prog[l]`` is a
+               subset of c; (2) l is not a selector that every clause of g
+               names with one and the same branch index (such a selector is
+               constant on g's rows).  So ctx of a group under one branch of a
+               root switch is the root group without that switch's selector;
+               ctx of a nested group also holds its ancestor groups' labels
+               without the fixed selectors; ctx of a group reachable from two
+               branches keeps the selector, because it varies.  ``ctx(root)``
+               is empty (``joint_contexts``).
+  sets         group g's below (above) set is the rows of that side in which
+               every label of ``ctx(g) + g`` is active (``set_rows`` with those
+               columns).  The mixture's label list is ``ctx(g)`` first, then
+               g's labels, each in ``domain.params`` order: D = D_ctx + D_g.
+               Weights, the prior component, -log Z, quantized masses, hit /
+               miss tables and ``cat_smoothing`` are those of "Factors" /
+               "Mixture"; ``sigma = bandwidth * sigma_p * n ** (-1 / (D + 4))``
+               with this D and this n.  D <= ``TPE_COND_MAX_LABELS`` and K <=
+               ``TPE_JOINT_MAX_CAT``, else ValueError.
+  term         for one set ``a_i^ctx = log w_i + sum over the D_ctx context
+               labels`` (sequential), and ``a_i`` continues the same sum over
+               g's labels.  ``log L_ctx`` and ``log L`` are the two
+               log-sum-exps by the "Mixture" rule.  The marginal is the same
+               mixture with g's factors dropped -- the same components, weights
+               and sigmas -- not a refit with D_ctx.  ``C_g(c) = (log L_below -
+               log L_ctx,below) - (log L_above - log L_ctx,above)``, in that
+               order of operations.  NaN from -inf - -inf propagates and ranks
+               first.
+  criterion    S = J_root, assigned (``score_device`` on the root group); then
+               S = S + C_g in group order over the groups live in the row.  A
+               group with an empty context has C_g = J_g and is scored exactly
+               as under ``"tree"``: a flat space has the bits of
+               ``joint=True``, a space whose groups all have empty contexts the
+               bits of ``joint="tree"``.  ``score_configs(joint="chain",
+               return_terms=True)`` gives (S, terms, C): ``terms`` all NaN, C
+               the (P, G) matrix with J_root in column 0 and C_g in column g,
+               NaN where g is not live; S is exactly the fold of C's live
+               columns.
+  drawing      ``Pool.sample(joint="chain")`` draws its rows exactly as
+               ``joint="tree"`` does, from the tree fits (the columns are bit
+               for bit the same for one seed): the draw is a proposal, the
+               ranking is this criterion, and the pool is born with the chain S
+               of its rows.
+
+Not built: a draw conditioned on the row's context (component weights ``w_i *
+prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
+on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
+the context's as well).  ``batch="liar"`` under ``joint="tree"`` and
+``joint="chain"`` (it needs log L_above per group, which ``score_tree_device``
 does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
 under the factorised criterion (its adaptive bandwidths depend on the sorted
 neighbours: no component can be added without a refit).
@@ -257,6 +313,31 @@ def joint_groups(domain):
     # the walk that orders ``domain.params`` meets a switch's selector before
     # its branches, so the first label is always live: the root group leads
     assert out[0].clauses == ((),) and out[0].labels == root
+    return out
+
+
+def joint_contexts(domain):
+    """``ctx(g)`` of ``joint="chain"`` (module doc, "Chains"): one label list
+    per group of ``joint_groups(domain)``, in ``domain.params`` order; empty
+    for the root group."""
+    domain = as_domain(domain)
+    groups = joint_groups(domain)
+    prog = domain.live_program()
+    out = [[]]
+    for grp in groups[1:]:
+        clauses = [dict(c) for c in grp.clauses]
+        ctx = []
+        for lab in domain.params:
+            if lab in grp.labels:
+                continue
+            # (1) live whenever the group is
+            if not all(any(set(lc) <= set(c.items()) for lc in prog[lab]) for c in clauses):
+                continue
+            # (2) not a selector held at one branch on all the group's rows
+            if all(lab in c for c in clauses) and len(set(c[lab] for c in clauses)) == 1:
+                continue
+            ctx.append(lab)
+        out.append(ctx)
     return out
 
 
@@ -407,13 +488,27 @@ def _density_terms(m, xd, mu, sigma):
                         -np.inf) + neg_log_z
 
 
-def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing):
+def _log_sum_exp(a):
+    """The "Mixture" rule over the (P, C) matrix of a_i, in component order."""
+    with np.errstate(all="ignore"):
+        mx = a.max(1)
+        s = np.zeros(a.shape[0])
+        for i in range(a.shape[1]):  # (component order)
+            s = s + np.where(a[:, i] == -np.inf, 0.0, np.exp(a[:, i] - mx))
+        return np.where(mx == -np.inf, -np.inf, mx + np.log(s))
+
+
+def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing, n_ctx=0):
     """log L of the pool values ``x`` (P, D; stored values) under the set of
-    history rows ``rows``."""
+    history rows ``rows``.  ``n_ctx`` > 0: (log L, log L_ctx), the second the
+    same mixture cut off after its first ``n_ctx`` labels ("Chains")."""
     n, P = rows.size, x.shape[0]
     a = np.broadcast_to(log_weights(n, lf, prior_weight), (P, n + 1)).copy()
     sig = bandwidths(models, n, bandwidth)
+    ctx = None
     for d, m in enumerate(models):
+        if n_ctx and d == n_ctx:
+            ctx = _log_sum_exp(a)
         obs = np.asarray(hist.vals)[rows, m.col] if n else np.zeros(0)
         xd = x[:, d]
         if m.kind == _L.JOINT_CAT:
@@ -428,12 +523,7 @@ def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing):
             term = _density_terms(m, xd, mu, sigma)
         with np.errstate(invalid="ignore"):
             a = a + term
-    with np.errstate(all="ignore"):
-        mx = a.max(1)
-        s = np.zeros(P)
-        for i in range(n + 1):  # (component order)
-            s = s + np.where(a[:, i] == -np.inf, 0.0, np.exp(a[:, i] - mx))
-        return np.where(mx == -np.inf, -np.inf, mx + np.log(s))
+    return (_log_sum_exp(a), ctx) if n_ctx else _log_sum_exp(a)
 
 
 def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
@@ -451,11 +541,18 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
     criterion on any space with a liveness program.  ``active`` ((P, L); None:
     where ``vals`` is not NaN) says where a group is live.  ``return_parts``:
     (S, J, log L_below, log L_above), the last three (P, G) matrices, NaN
-    where the group is not live."""
+    where the group is not live.
+
+    ``tree="chain"``: S of ``joint="chain"`` (module doc, "Chains").
+    ``return_parts``: (S, C, log L_below, log L_above, log L_ctx,below, log
+    L_ctx,above), the last five (P, G) matrices, NaN where the group is not
+    live; the two marginals also NaN in the columns of the groups with an empty
+    context (the root's among them), whose C_g is J_g."""
     domain = as_domain(domain)
     if tree:
         return _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma,
-                                 linear_forgetting, bandwidth, cat_smoothing, return_parts)
+                                 linear_forgetting, bandwidth, cat_smoothing, return_parts,
+                                 tree == "chain")
     models = label_models(domain)
     vals = np.asarray(vals, np.float64)
     cols = [m.col for m in models]
@@ -471,28 +568,42 @@ def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
 
 
 def _score_numpy_tree(domain, hist, vals, active, prior_weight, gamma, lf, bandwidth, smoothing,
-                      return_parts):
+                      return_parts, chain=False):
     groups = joint_groups(domain)
+    contexts = joint_contexts(domain) if chain else [[]] * len(groups)
     vals = np.asarray(vals, np.float64)
     active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
     P, G = vals.shape[0], len(groups)
     isb, isa = split_sets(hist, gamma)
-    parts = np.full((3, P, G), np.nan)  # J, log L_below, log L_above
+    # J (with ``chain``: C), log L_below, log L_above, and the context marginals
+    parts = np.full((5, P, G), np.nan)
     S = None
-    for g, grp in enumerate(groups):
-        models = label_models(domain, grp.labels)
-        cols = [m.col for m in models]
-        live = active[:, cols].all(1)
-        if (active[:, cols].any(1) != live).any() or (g == 0 and not live.all()):
+    for g, (grp, ctx) in enumerate(zip(groups, contexts)):
+        own = [m.col for m in label_models(domain, grp.labels)]
+        live = active[:, own].all(1)
+        if (active[:, own].any(1) != live).any() or (g == 0 and not live.all()):
             raise ValueError("a group's labels are not active together in some row")
+        models = label_models(domain, ctx + grp.labels)
+        cols = [m.col for m in models]
+        if not active[live][:, cols].all():
+            raise ValueError("a context label is not active in a row in which its group is live")
         x = vals[live][:, cols]
-        lb, la = (_set_log_l(models, hist, set_rows(hist, mask, cols), x, lf, prior_weight,
-                             bandwidth, smoothing) for mask in (isb, isa))
+        out = [_set_log_l(models, hist, set_rows(hist, mask, cols), x, lf, prior_weight,
+                          bandwidth, smoothing, len(ctx)) for mask in (isb, isa)]
         with np.errstate(invalid="ignore"):
-            parts[0, live, g], parts[1, live, g], parts[2, live, g] = lb - la, lb, la
+            if ctx:
+                (lb, cb), (la, ca) = out
+                parts[3, live, g], parts[4, live, g] = cb, ca
+                parts[0, live, g] = (lb - cb) - (la - ca)
+            else:
+                lb, la = out
+                parts[0, live, g] = lb - la
+            parts[1, live, g], parts[2, live, g] = lb, la
             # (S starts as J_root, assigned: the root group is live in every row)
             S = parts[0, :, 0].copy() if g == 0 else np.where(live, S + parts[0, :, g], S)
-    return (S, parts[0], parts[1], parts[2]) if return_parts else S
+    if not return_parts:
+        return S
+    return (S,) + tuple(parts) if chain else (S, parts[0], parts[1], parts[2])
 
 
 # -- batches (module doc, "Batches") ---------------------------------------------
@@ -646,10 +757,11 @@ class JointFit(object):
     """One mixture pair fitted to a history, on the device (``fit``): the
     engine, the label records ``dj``, ``sets`` = [below, above] as
     ``_prepare_set`` returns them, the stream pointer ``sp``, ``group`` (the
-    labels of its group of ``joint_groups``; None: the joint labels) and the
-    settings it was made with."""
-    __slots__ = ("eng", "dj", "sets", "sp", "group", "prior_weight", "linear_forgetting",
-                 "bandwidth", "cat_smoothing")
+    labels of its group of ``joint_groups``; None: the joint labels), ``n_ctx``
+    (with ``tree="chain"`` the number of context labels that lead ``dj``'s
+    list, before the group's own; else 0) and the settings it was made with."""
+    __slots__ = ("eng", "dj", "sets", "sp", "group", "n_ctx", "prior_weight",
+                 "linear_forgetting", "bandwidth", "cat_smoothing")
 
 
 def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting, bandwidth,
@@ -657,7 +769,10 @@ def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting,
     """The joint model of the history ``hist`` under the split of ``gamma``:
     [JointFit] -- the joint labels' alone, or with ``tree`` one per group of
     ``joint_groups(domain)``, the root group first.  Per fit the label records
-    go up, then both sets are built there (tpe_joint_prep).
+    go up, then both sets are built there (tpe_joint_prep).  ``tree="chain"``:
+    a group with a context is fitted over ``ctx + g`` (module doc, "Chains")
+    and records ``n_ctx``; the root's fit, and that of any group with an empty
+    context, is the one ``tree=True`` makes.
 
     ``seen``: the history on the device, the tuple (keep-alive tensors, values
     pointer, activity pointer, leading dimension, rows pointer or None, T) --
@@ -669,12 +784,20 @@ def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting,
     isb, isa = split_sets(hist, gamma)
     view = hist.rows if (seen[4] is not None) else None  # (positions -> rows of the mirror)
     fits = []
-    for group in ([grp.labels for grp in joint_groups(domain)] if tree else [None]):
+    groups = [grp.labels for grp in joint_groups(domain)] if tree else [None]
+    contexts = joint_contexts(domain) if tree == "chain" else [[]] * len(groups)
+    for group, ctx in zip(groups, contexts):
         f = JointFit()
-        f.eng, f.group = eng, group
+        f.eng, f.group, f.n_ctx = eng, group, len(ctx)
         f.prior_weight, f.linear_forgetting = prior_weight, linear_forgetting
         f.bandwidth, f.cat_smoothing = bandwidth, cat_smoothing
-        models = label_models(domain, group)
+        models = label_models(domain, ctx + group if ctx else group)
+        if ctx and (len(models) > _L.COND_MAX_LABELS or
+                    max(m.n_cat for m in models) > _L.JOINT_MAX_CAT):
+            raise ValueError("joint='chain': the group of %r with its context has %d labels (at "
+                             "most %d) / a label of %d options (at most %d)"
+                             % (group[0], len(models), _L.COND_MAX_LABELS,
+                                max(m.n_cat for m in models), _L.JOINT_MAX_CAT))
         f.dj = _device_labels(eng, models, cat_smoothing)
         f.sp = stream_ptr(eng)
         cols = [m.col for m in models]
@@ -819,7 +942,13 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
     log L_below minus it added to ``out`` at the listed rows
     (tpe_joint_score_rows).  The list's length never comes to the host.
     ``parts``: a (G, >= P) device tensor filled with NaN; row g receives J_g at
-    the rows in which group g is live."""
+    the rows in which group g is live.
+
+    ``fits`` of ``fit(..., tree="chain")``: S of ``joint="chain"``.  A fit with
+    a context (``n_ctx`` > 0) takes tpe_joint_chain_rows in the same loop --
+    log L - log L_ctx of the above set into the temporary, the below set's
+    minus it added -- so row g of ``parts`` receives C_g; the list is still
+    compacted on the group's first own label, not the context's."""
     eng = fits[0].eng
     t, lib = eng.torch, eng.lib
     score_device(fits[0], d_vals, ld, n_cols, P, out)
@@ -828,7 +957,8 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
     if len(fits) == 1 or P == 0:
         return
     win = min(P, ROWS_PER_CALL)
-    need = max(lib.tpe_joint_scratch_bytes(win, n) for f in fits[1:] for _, n, _ in f.sets)
+    need = max((lib.tpe_joint_chain_scratch_bytes if f.n_ctx else lib.tpe_joint_scratch_bytes)
+               (win, n) for f in fits[1:] for _, n, _ in f.sets)
     scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
     above = t.empty(win, dtype=t.float64, device=eng.device)
     rows = t.empty(P, dtype=t.int64, device=eng.device)
@@ -839,17 +969,22 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
         dj, sets, sp = f.dj, f.sets, f.sp
         D = len(dj.models)
         tab = None if dj.tables is None else dj.tables.data_ptr()
-        flags = d_active.data_ptr() + dj.models[0].col * ld
+        n_ctx = f.n_ctx
+        flags = d_active.data_ptr() + dj.models[n_ctx].col * ld
         _L.check(lib.tpe_rows_compact(flags, P, rows.data_ptr(), count.data_ptr(),
                                       cscratch.data_ptr(), sp), "tpe_rows_compact")
 
         def score(which, p0, sub, dst, mode):
             dset, n, _ = sets[which]
-            _L.check(lib.tpe_joint_score_rows(dj.host.ctypes.data, dj.dev.data_ptr(), D, tab,
-                                              dj.n_tables, dset.data_ptr(), n, d_vals.data_ptr(),
-                                              ld, n_cols, rows.data_ptr(), count.data_ptr(), p0,
-                                              min(win, P - p0), sub, dst, mode,
-                                              scratch.data_ptr(), sp), "tpe_joint_score_rows")
+            head = (dj.host.ctypes.data, dj.dev.data_ptr(), D)
+            tail = (tab, dj.n_tables, dset.data_ptr(), n, d_vals.data_ptr(), ld, n_cols,
+                    rows.data_ptr(), count.data_ptr(), p0, min(win, P - p0), sub, dst, mode,
+                    scratch.data_ptr(), sp)
+            if n_ctx:
+                _L.check(lib.tpe_joint_chain_rows(*(head + (n_ctx,) + tail)),
+                         "tpe_joint_chain_rows")
+            else:
+                _L.check(lib.tpe_joint_score_rows(*(head + tail)), "tpe_joint_score_rows")
 
         for p0 in range(0, P, win):
             score(1, p0, None, above.data_ptr(), 0)

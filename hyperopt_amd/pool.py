@@ -56,7 +56,10 @@ mixture (csrc/tpe_joint_sample.hip); ``joint="tree"``, accepted wherever
 ``joint=True`` is, gives the labels under a ``switch`` joint mixtures as well,
 one per group of labels that share an activation condition (joint.py
 "Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
-interaction between labels.
+interaction between labels.  ``joint="chain"`` (not on a ``GridPool``, not with
+``batch="liar"``) conditions each of those groups on the labels live around it
+(joint.py "Chains"; csrc/tpe_joint_chain.hip), so a root label interacts with a
+branch label; its sampled pools draw the rows of ``"tree"``.
 
 ``batch="liar"`` (``suggest_from_pool``, ``suggest_sampled``, ``pick_batch``;
 with ``joint=True`` on a ``Pool`` / ``SampledPool``) makes the k rows of one
@@ -350,7 +353,12 @@ class Pool(object):
         keys and bits of ``joint=True``, every other group under its own
         component key); the activity follows from the drawn selectors, and
         the pool is born with ``score_configs(joint="tree")`` of its rows.
-        ``keep_terms`` leaves NaN everywhere: every label is joint."""
+        ``keep_terms`` leaves NaN everywhere: every label is joint.
+
+        ``joint="chain"``: the rows are those of ``joint="tree"``, column for
+        column, for the seed -- the draw is a proposal from the groups' own
+        mixtures -- and the pool is born with ``score_configs(joint="chain")``
+        of them (joint.py, "Chains")."""
         st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
         return _sample(domain, trials, seed, n_rows, st, keep_terms)
 
@@ -592,7 +600,10 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
         # the joint labels' columns (with the groups: every group's), for all the
         # rows: one draw per row from the below set's mixture
         fits = _fit(eng, domain, hist, L, st)
-        _J.sample_tree_device(fits, seed, d.vals, P, L, 0, P)
+        # (joint="chain" draws as "tree" does, from the tree fits: a proposal
+        # that its own fits then rank)
+        _J.sample_tree_device(_fit(eng, domain, hist, L, st, tree=True)
+                              if joint["tree"] == "chain" else fits, seed, d.vals, P, L, 0, P)
     if len(chunks) > 1:
         # the fold runs in label order and needs every row's activity: the
         # selectors' columns first (their draws do not depend on the chunking)
@@ -959,6 +970,7 @@ def _score_grid(domain, trials, pool, st, want_terms, hist=None, want_parts=Fals
     (with ``st.joint``: ``_score_grid_joint``).  Returns (engine, device grid,
     {label: T_l} or None)."""
     _same_space(domain, pool)
+    _grid_settings(st, pool)
     if st.joint is not None:
         return _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts)
     eng, obs = _history_inputs(domain, trials, st.gamma, hist)
@@ -991,6 +1003,21 @@ def _history_inputs(domain, trials, gamma, hist=None):
 GRID_JOINT = ("the joint criterion is not separable over the axes of a GridPool; build the grid "
               "with GridPool(..., joint=True), which scores it from per-axis factor tables, or "
               "score its rows as a Pool (GridPool.to_pool())")
+GRID_CHAIN = ("joint='chain' is not built for a GridPool: a group's factor tables hold its own "
+              "axes, and a chain term needs its context's too (joint.py, \"Not built\"); score "
+              "its rows as a Pool (GridPool.to_pool())")
+
+
+def _grid_settings(st, pool):
+    """ValueError where the settings ``st`` ask of the grid pool ``pool`` what
+    it was not built with (GRID_JOINT) or what no grid is built for
+    (GRID_CHAIN); no-op for any other pool."""
+    if st.joint is None or not isinstance(pool, GridPool):
+        return
+    if not pool.joint:
+        raise ValueError(GRID_JOINT)
+    if st.joint["tree"] == "chain":
+        raise ValueError(GRID_CHAIN)
 
 
 class GridJointPlan(object):
@@ -1100,10 +1127,12 @@ def _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts):
     return eng, d, terms
 
 
-def _fit(eng, domain, hist, n_cols, st):
-    """``joint.fit`` of the history under the settings ``st``."""
+def _fit(eng, domain, hist, n_cols, st, tree=None):
+    """``joint.fit`` of the history under the settings ``st`` (``tree``: in
+    place of the settings' own)."""
     return _J.fit(eng, domain, hist, _seen_rows(eng, hist), st.gamma, n_cols, st.prior_weight,
-                  st.lf, st.joint["bandwidth"], st.joint["cat_smoothing"], st.joint["tree"])
+                  st.lf, st.joint["bandwidth"], st.joint["cat_smoothing"],
+                  st.joint["tree"] if tree is None else tree)
 
 
 def _parts(eng, domain, st, P):
@@ -1316,10 +1345,14 @@ def _topk_device(eng, d, P, k, taken=None):
 
 def _joint_kw(joint, bandwidth, cat_smoothing):
     """``_Settings.joint``: None, or the criterion's keywords
-    (``tree``: the string ``"tree"`` was given -- one mixture per group of
-    labels, joint.py "Groups"; any other truthy value is ``joint=True``)."""
+    (``tree``: True where the string ``"tree"`` was given -- one mixture per
+    group of labels, joint.py "Groups" -- and ``"chain"`` where that string
+    was: the groups conditioned on their contexts, joint.py "Chains"; any other
+    truthy value is ``joint=True``, ``tree`` False)."""
     if isinstance(joint, str) and joint == "tree":
         tree = True
+    elif isinstance(joint, str) and joint == "chain":
+        tree = "chain"
     elif not joint:
         return None
     else:
@@ -1372,6 +1405,8 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
     if st.joint is None:
         raise ValueError(BATCH_LIAR + "; the factorised criterion (joint=False) has no such "
                          "update: its bandwidths depend on the sorted neighbours")
+    if st.joint["tree"] == "chain":
+        raise ValueError(BATCH_LIAR + "; joint='chain' keeps no log L_above per group")
     if st.joint["tree"]:
         raise ValueError(BATCH_LIAR + "; joint='tree' keeps no log L_above per group")
     if isinstance(pool, GridPool):
@@ -1468,12 +1503,23 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     ``return_terms`` gives (S, terms, J): ``terms`` all NaN, J the (P, G)
     matrix of J_g, NaN where group g is not live in the row.  A space whose
     switches are not selected by bare choice / randint(n) labels raises
-    ValueError.  Any other truthy ``joint`` is ``joint=True``."""
+    ValueError.
+
+    ``joint="chain"``: the groups of ``"tree"``, each conditioned on its
+    context -- the labels outside it that are live whenever it is
+    (``tpe.joint_contexts``; joint.py, "Chains"): group g adds C_g = (log
+    L_below - log L_ctx,below) - (log L_above - log L_ctx,above) over one
+    mixture of the labels ctx + g, so a root label interacts with a branch
+    label.  A group with an empty context adds J_g as under ``"tree"``; on a
+    flat space S has the bits of ``joint=True``.  ``return_terms`` gives (S,
+    terms, C): ``terms`` all NaN, C the (P, G) matrix of J_root and the C_g,
+    NaN where group g is not live.  A ``GridPool`` raises ValueError.
+
+    Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
     grid, tree = isinstance(pool, GridPool), st.joint is not None and st.joint["tree"]
-    if grid and st.joint is not None and not pool.joint:
-        raise ValueError(GRID_JOINT)
+    _grid_settings(st, pool)
     P = len(pool)
     if tree and return_terms:  # (ValueError on a space without the groups, before any other)
         _J.joint_groups(domain)
@@ -1541,7 +1587,9 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     bandwidth=..., cat_smoothing=...)`` (``joint="tree"``): the same selection,
     ``distinct`` and startup rules, other scores.  A ``GridPool`` needs to
     have been built with ``joint=True`` (else ValueError); its ``keep``,
-    ``exclude`` and taken rules are unchanged.
+    ``exclude`` and taken rules are unchanged.  ``joint="chain"`` ranks by
+    ``score_configs(joint="chain")`` in the same way; a ``GridPool`` raises
+    ValueError.
 
     ``batch="liar"`` (with ``joint=True`` on a ``Pool`` / ``SampledPool``;
     anything else raises ValueError): the ids' rows are picked one at a time on
@@ -1558,8 +1606,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
         raise ValueError(GRID_DISTINCT)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
                    lie_weight, pool)
-    if st.joint is not None and isinstance(pool, GridPool) and not pool.joint:
-        raise ValueError(GRID_JOINT)
+    _grid_settings(st, pool)
     t0 = time.time()
     domain = as_domain(domain)
     _same_space(domain, pool)
@@ -1686,7 +1733,9 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     are the same for both.  ``joint="tree"`` is the same with the groups'
     criterion (``score_configs(joint="tree")``) and, under ``draw="joint"``,
     ``Pool.sample(joint="tree")``: the labels under a ``switch`` are drawn
-    jointly too.
+    jointly too.  ``joint="chain"`` ranks by ``score_configs(joint="chain")``
+    under either ``draw``; ``draw="joint"`` draws the rows of ``joint="tree"``
+    (a draw conditioned on the row's context is not built).
 
     ``batch="liar"`` (needs ``joint=True``; ValueError otherwise, and for any
     other string): the documents' rows are picked one at a time, each pick

@@ -38,7 +38,9 @@ mixture over whole configurations instead of a sum over labels
 also draw the rows from that mixture (``joint_component_key``: the key of the
 draws' component pick).  ``joint="tree"`` gives the labels under a ``switch``
 joint mixtures too, one per group of labels that share an activation
-condition (``joint_groups``, ``joint_group_component_key``).
+condition (``joint_groups``, ``joint_group_component_key``);
+``joint="chain"`` conditions every such group on the labels that are live
+around it (``joint_contexts``), so a root label interacts with a branch label.
 ``GridPool(..., joint=True)`` is ranked by either criterion from per-axis
 factor tables, again without its rows (``grid_joint_plan``).
 ``batch="liar"`` (with ``joint=True``) picks the k rows of a call one at a
@@ -800,5 +802,5 @@ def _suggest_many(requests, shard_studies=False):
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan,  # noqa: E402,F401
                    pick_batch, score_configs, suggest_from_pool, suggest_sampled)
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
-                    group_component_key as joint_group_component_key, joint_groups, joint_labels,
-                    liar_numpy as joint_liar_numpy, score_numpy as joint_score_numpy)
+                    group_component_key as joint_group_component_key, joint_contexts,
+                    joint_groups, joint_labels, liar_numpy as joint_liar_numpy, score_numpy as joint_score_numpy)

@@ -1059,6 +1059,29 @@ int tpe_joint_score_rows(const tpe_joint_label* host_labels, const tpe_joint_lab
                          int64_t max_rows, const double* sub, double* out, int out_mode,
                          void* scratch, void* stream);
 
+/* ---- a group's mixture conditioned on its context -----------------------------
+ * (tpe.score_configs(joint="chain"); hyperopt_amd/joint.py, "Chains".)
+ * tpe_joint_chain_rows: tpe_joint_score_rows on a set prepared over the labels
+ * ctx + g, the n_ctx context labels first, with
+ *   v = (log L(row) - log L_ctx(row)) - (sub ? sub[p - list_begin] : 0)
+ * log L_ctx: the same mixture with the factors of labels [n_ctx, n_labels)
+ * dropped -- a_i cut off after the first n_ctx labels, the same components,
+ * weights and sigmas.  Both come from one walk over the labels; log L has the
+ * bits tpe_joint_score_rows gives the row under this set, log L_ctx the bits it
+ * gives with n_labels = n_ctx under a set prepared from the first n_ctx labels
+ * with this set's sigmas.  -inf - -inf is NaN and is written.  n_ctx <= 0 or
+ * n_ctx >= n_labels: TPE_E_ARG.  scratch: tpe_joint_chain_scratch_bytes(
+ * max_rows, n) bytes (-1: bad arguments), 16-byte aligned.  Everything else --
+ * the list, the three out_modes, skipped entries, limits, errors, no-ops -- as
+ * tpe_joint_score_rows. */
+int64_t tpe_joint_chain_scratch_bytes(int64_t n_rows, int64_t n);
+int tpe_joint_chain_rows(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                         int n_labels, int n_ctx, const double* tables, int64_t n_tables,
+                         const double* set, int64_t n, const double* vals, int64_t ld, int n_cols,
+                         const int64_t* rows, const int64_t* d_count, int64_t list_begin,
+                         int64_t max_rows, const double* sub, double* out, int out_mode,
+                         void* scratch, void* stream);
+
 /* ---- a batch picked one at a time under the joint criterion -------------------
  * (tpe.suggest_from_pool(joint=True, batch="liar"); hyperopt_amd/joint.py,
  * "Batches".)  Pick j enters the above mixture as one more trial component
