@@ -74,6 +74,7 @@ JOINT_CONT, JOINT_QUANT, JOINT_CAT = 0, 1, 2
 JOINT_LOG, JOINT_BOUNDED = 1, 2
 JOINT_MAX_CAT = 65536
 JOINT_OUT_SCATTER, JOINT_OUT_ADD = 1, 2  # tpe_joint_score_rows' out_mode
+REFINE_MAX_CONT = 16  # tpe_joint_refine's continuous labels (TPE_REFINE_MAX_CONT)
 GRID_JOINT_STORE, GRID_JOINT_ADD = 0, 1  # tpe_grid_joint_score's out_mode
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
@@ -202,6 +203,9 @@ _SIGNATURES = {
     "tpe_joint_lie_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _I64, _P, _P,
                                  ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P, _P, _P, _P,
                                  _P, _P]),
+    "tpe_joint_refine": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I,
+                              _P, _P, _P, _P, _P]),
+    "tpe_joint_refine_max_cont": (_I, []),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),
@@ -295,6 +299,9 @@ def load():
     lib.tpe_joint_struct_sizes(ctypes.cast(ssz, _P), 1)
     if tuple(ssz) != (JOINT_LABEL_DTYPE.itemsize,):
         raise ImportError("hyperopt_amd: tpe_joint_label size mismatch %s" % (tuple(ssz),))
+    if lib.tpe_joint_refine_max_cont() != REFINE_MAX_CONT:
+        raise ImportError("hyperopt_amd: TPE_REFINE_MAX_CONT is %d in the library, %d here"
+                          % (lib.tpe_joint_refine_max_cont(), REFINE_MAX_CONT))
     _lib = lib
     return lib
 

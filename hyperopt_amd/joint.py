@@ -237,6 +237,42 @@ L(ctx + g) / L(ctx).
                ranking is this criterion, and the pool is born with the chain S
                of its rows.
 
+Refining (``refine=N``, csrc/tpe_joint_refine.hip).  Every path
+above ends in an argmax over a finite set of rows, and the maximum of J lies
+between them.  On the continuous labels J is smooth with a closed-form
+gradient, so the picked rows are moved.  ``joint=True`` only.
+
+  moving labels   a row's ``JOINT_CONT`` labels, D_c of them in list order, each
+               in its fit coordinate t (log x for the log kinds).  Quantized and
+               discrete labels, and every label under a ``switch``, stay.
+               D_c == 0: the row is returned unchanged; D_c >
+               ``TPE_REFINE_MAX_CONT`` (16): ValueError.
+  evaluation   at a point t, per set: ``a_i`` of "Factors" / "Mixture", log L
+               their log-sum-exp, ``r_i = exp(a_i - log L)``, ``dlogL_d = sum_i
+               r_i (mu_{i,d} - t_d) / sigma_{i,d}^2`` (the set's bandwidth for a
+               trial component, sigma_p for the prior; -log Z does not depend on
+               t).  ``J(t) = log L_below - log L_above``, ``g_d = dlogL_below,d -
+               dlogL_above,d``; a set with log L = -inf contributes no gradient.
+  climb        evaluate at the start, h = 1; then ``refine`` times at the most,
+               and only while h >= 2^-20: ``t'_d = clamp(t_d + (h s_d^2) g_d)``,
+               s_d the below set's bandwidth of label d (sigma_p where that set
+               is empty) -- with h = 1 and no above term the mean-shift (EM)
+               step of the below mixture; ``clamp``, for a bounded kind, lifts
+               to lo and cuts to nextafter(hi, -inf) (``draw64``'s rule).
+               ``J(t') > J(t)``: t, J, g become those of t' and h = min(1, 2 h);
+               otherwise, NaN on either side included, h = h / 2.
+  result       a label whose t ends where it started keeps its stored bits;
+               any other stores exp(t) for a log kind, else t.  J never
+               decreases along the accepted points, ``refine=0`` is the identity
+               bit for bit, and a row whose first J is NaN or +-inf is returned
+               unchanged.  A row's result is a function of the row, the two
+               sets and ``refine`` alone.
+
+``refine_numpy`` is this definition in numpy; ``refine_device`` runs every
+row's whole climb in one launch (inside a_i the device adds the fixed labels'
+factors first, then the moving ones': its J equals the scorer's to rounding,
+and ``tpe.refine_configs`` reports J before and after from ``score_device``).
+
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
 on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
@@ -244,7 +280,8 @@ the context's as well).  ``batch="liar"`` under ``joint="tree"`` and
 ``joint="chain"`` (it needs log L_above per group, which ``score_tree_device``
 does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
 under the factorised criterion (its adaptive bandwidths depend on the sorted
-neighbours: no component can be added without a refit).
+neighbours: no component can be added without a refit).  ``refine`` under
+``joint="tree"`` / ``"chain"`` (a group's labels move only where it is live).
 """
 from __future__ import annotations
 
@@ -509,21 +546,25 @@ def _set_log_l(models, hist, rows, x, lf, prior_weight, bandwidth, smoothing, n_
     for d, m in enumerate(models):
         if n_ctx and d == n_ctx:
             ctx = _log_sum_exp(a)
-        obs = np.asarray(hist.vals)[rows, m.col] if n else np.zeros(0)
-        xd = x[:, d]
-        if m.kind == _L.JOINT_CAT:
-            hit, miss, prior = cat_tables(m, smoothing)
-            c = np.rint(xd).astype(np.int64) - m.offset
-            ci = np.rint(obs).astype(np.int64) - m.offset
-            term = np.where(c[:, None] == ci[None, :], hit[c][:, None], miss[c][:, None])
-            term = np.concatenate([term, prior[c][:, None]], 1)
-        else:
-            mu = np.concatenate([_fit(m, obs), [m.mu]])
-            sigma = np.concatenate([np.full(n, sig[d]), [m.sigma]])
-            term = _density_terms(m, xd, mu, sigma)
         with np.errstate(invalid="ignore"):
-            a = a + term
+            a = a + _label_term(m, hist, rows, sig[d], x[:, d], smoothing)
     return (_log_sum_exp(a), ctx) if n_ctx else _log_sum_exp(a)
+
+
+def _label_term(m, hist, rows, sig_d, xd, smoothing):
+    """log k of one label: the stored values ``xd`` (P,) under the n + 1
+    components of the set of history rows ``rows``: (P, n + 1)."""
+    n = rows.size
+    obs = np.asarray(hist.vals)[rows, m.col] if n else np.zeros(0)
+    if m.kind == _L.JOINT_CAT:
+        hit, miss, prior = cat_tables(m, smoothing)
+        c = np.rint(xd).astype(np.int64) - m.offset
+        ci = np.rint(obs).astype(np.int64) - m.offset
+        term = np.where(c[:, None] == ci[None, :], hit[c][:, None], miss[c][:, None])
+        return np.concatenate([term, prior[c][:, None]], 1)
+    mu = np.concatenate([_fit(m, obs), [m.mu]])
+    sigma = np.concatenate([np.full(n, sig_d), [m.sigma]])
+    return _density_terms(m, xd, mu, sigma)
 
 
 def score_numpy(domain, hist, vals, active=None, prior_weight=1.0, gamma=0.25,
@@ -692,6 +733,152 @@ def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0,
             U = np.where(c == -np.inf, U, np.where(m == -np.inf, -np.inf, both))
             S = np.where(np.isfinite(U0), S0 - (U - U0), S0)
     return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
+
+
+# -- refining (module doc, "Refining") -------------------------------------------
+REFINE_MIN_STEP = 2.0 ** -20
+REFINE_TOL = 1e-6  # the project's relative tolerance per log-density (``info``'s bounds)
+
+
+def check_refine(refine):
+    """``refine`` as a step count: None is 0; ValueError for anything but a
+    non-negative integer."""
+    if refine is None:
+        return 0
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError("refine=%r: None or an integer >= 0" % (refine,))
+    return int(refine)
+
+
+def moving_labels(models):
+    """The positions in ``models`` of the labels a climb moves: the continuous
+    ones, in list order (ValueError for more than ``REFINE_MAX_CONT``)."""
+    cont = [d for d, m in enumerate(models) if m.kind == _L.JOINT_CONT]
+    if len(cont) > _L.REFINE_MAX_CONT:
+        raise ValueError("refine: %d continuous always-live labels, at most %d"
+                         % (len(cont), _L.REFINE_MAX_CONT))
+    return cont
+
+
+def _refine_set(models, cont, hist, rows, x, t, lf, prior_weight, bandwidth, smoothing,
+                bounds=False):
+    """One set at the points ``t`` (P, D_c; fit coordinates of the labels
+    ``cont``) of the rows ``x`` (P, D; stored values): log L (P,) and dlogL
+    (P, D_c); then, zeros unless ``bounds`` (a check's, not the climb's): sum_i
+    r_i |mu_i - t| / sigma_i^2 (P, D_c) and a bound K (P, D_c, D_c) on
+    |d dlogL_d / d t_e|."""
+    n, P, Dc = rows.size, x.shape[0], len(cont)
+    a = np.broadcast_to(log_weights(n, lf, prior_weight), (P, n + 1)).copy()
+    sig = bandwidths(models, n, bandwidth)
+    pull = np.zeros((P, Dc, n + 1))  # (mu - t) / sigma^2
+    curv = np.zeros((Dc, n + 1))  # 1 / sigma^2
+    for d, m in enumerate(models):
+        if m.kind == _L.JOINT_CONT:
+            j = cont.index(d)
+            obs = np.asarray(hist.vals)[rows, m.col] if n else np.zeros(0)
+            mu = np.concatenate([_fit(m, obs), [m.mu]])
+            sigma = np.concatenate([np.full(n, sig[d]), [m.sigma]])
+            with np.errstate(all="ignore"):
+                diff = t[:, j, None] - mu[None, :]
+                z = diff / sigma[None, :]
+                term = (-0.5 * z * z - np.log(sigma * math.sqrt(2.0 * math.pi)) +
+                        _log_norm(m, mu, sigma))
+                pull[:, j], curv[j] = -diff / sigma ** 2, 1.0 / sigma ** 2
+        else:
+            term = _label_term(m, hist, rows, sig[d], x[:, d], smoothing)
+        with np.errstate(invalid="ignore"):
+            a = a + term
+    L = _log_sum_exp(a)
+    with np.errstate(all="ignore"):
+        r = np.where((L == -np.inf)[:, None], 0.0, np.exp(a - L[:, None]))  # (no pull)
+        dlog = np.einsum("pc,pdc->pd", r, pull)
+        if not bounds:
+            return L, dlog, np.zeros((P, Dc)), np.zeros((P, Dc, Dc))
+        m1 = np.einsum("pc,pdc->pd", r, np.abs(pull))
+        # d/dt_e sum_i r_i pull_id = sum_i r_i pull_id (pull_ie - E pull_e) - [d == e] E 1/sigma^2
+        K = (np.einsum("pc,pdc,pec->pde", r, np.abs(pull), np.abs(pull)) +
+             m1[:, :, None] * m1[:, None, :])
+        K[:, np.arange(Dc), np.arange(Dc)] += r @ curv.T
+    return L, dlog, m1, K
+
+
+def refine_numpy(domain, hist, vals, refine, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
+                 bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING, return_info=False):
+    """The climb of module doc "Refining" in vectorised numpy, every row of
+    ``vals`` ((P, L) stored values as ``Pool.vals`` holds them) by itself:
+    (refined copy of ``vals``, J_start, J_end, g_end (P, D_c), accepted).
+
+    ``return_info``: one more entry, what a comparison at ``REFINE_TOL`` per
+    log-density needs, all from this reference alone: ``J_bound`` (P,) =
+    tol (|log L_below| + |log L_above|) and ``g_bound`` (P, D_c) = tol sum_i
+    r_i |mu_i - t| / sigma_i^2 over both sets, both at the last accepted point;
+    ``t_bound`` (P, D_c), the bound on t there propagated per accepted step --
+    a deviation dt of the point and dg <= g_bound of its gradient give
+    dt'_d <= dt_d + h s_d^2 (sum_e K_de dt_e + dg_d), K bounding the gradient's
+    derivative (``K`` (P, D_c, D_c), at the last accepted point; the clamp does
+    not stretch a deviation); and ``margin`` (steps, P), per decision |J(t') -
+    J(t)| over the sum of the two points' J bounds -- NaN where the row took no
+    decision, inf where t' is t itself."""
+    domain = as_domain(domain)
+    refine = check_refine(refine)
+    models = label_models(domain)
+    cont = moving_labels(models)
+    vals = np.array(vals, np.float64, ndmin=2)
+    cols = [m.col for m in models]
+    x = vals[:, cols]
+    P, Dc = x.shape[0], len(cont)
+    sets = [set_rows(hist, mask, cols) for mask in split_sets(hist, gamma)]
+    sb = bandwidths(models, sets[0].size, bandwidth)
+    s2 = np.asarray([(sb[d] if sets[0].size else models[d].sigma) ** 2 for d in cont])
+    t0 = np.stack([_fit(models[d], x[:, d]) for d in cont], 1) if Dc else np.zeros((P, 0))
+
+    def evaluate(t):
+        (Lb, db, ab, Kb), (La, da, aa, Ka) = [
+            _refine_set(models, cont, hist, rows, x, t, linear_forgetting, prior_weight,
+                        bandwidth, cat_smoothing, return_info) for rows in sets]
+        with np.errstate(invalid="ignore"):
+            return (Lb - La, db - da, REFINE_TOL * (np.abs(Lb) + np.abs(La)),
+                    REFINE_TOL * (ab + aa), Kb + Ka)
+
+    t = t0.copy()
+    J, g, Jb, gb, K = evaluate(t)
+    J_start = J.copy()
+    # (the start itself: two implementations of log may differ in the last place)
+    h, acc, tb = np.ones(P), np.zeros(P, np.int32), 4.0 * np.finfo(np.float64).eps * np.abs(t0)
+    live = np.isfinite(J)
+    margin = np.full((refine, P), np.nan)
+    for it in range(refine):
+        go = live & (h >= REFINE_MIN_STEP)
+        if not go.any():
+            break
+        with np.errstate(all="ignore"):
+            tt = t + (h[:, None] * s2[None, :]) * g
+            for j, d in enumerate(cont):
+                m = models[d]
+                if m.bounded:  # (draw64's clamp)
+                    tt[:, j] = np.where(tt[:, j] < m.lo, m.lo, tt[:, j])
+                    tt[:, j] = np.where(tt[:, j] < m.hi, tt[:, j], np.nextafter(m.hi, -np.inf))
+            Jn, gn, Jbn, gbn, Kn = evaluate(tt)
+            better = go & (Jn > J)
+        up = better[:, None]
+        if return_info:  # (the bounds follow the climb; they never steer it)
+            with np.errstate(all="ignore"):
+                margin[it] = np.where(go, np.abs(Jn - J) / (Jbn + Jb), np.nan)
+                # (a trial point that is the current point is a tie in any implementation)
+                margin[it] = np.where(go & (tt == t).all(1), np.inf, margin[it])
+                tbn = tb + (h[:, None] * s2[None, :]) * (np.einsum("pde,pe->pd", K, tb) + gb)
+            gb, tb, Jb = np.where(up, gbn, gb), np.where(up, tbn, tb), np.where(better, Jbn, Jb)
+            K = np.where(better[:, None, None], Kn, K)
+        t, g, J = np.where(up, tt, t), np.where(up, gn, g), np.where(better, Jn, J)
+        acc = acc + better.astype(np.int32)
+        h = np.where(better, np.minimum(1.0, 2.0 * h), np.where(go, 0.5 * h, h))
+    for j, d in enumerate(cont):  # (a label that did not move keeps its stored bits)
+        moved = t[:, j] != t0[:, j]
+        vals[moved, cols[d]] = (np.exp(t[:, j]) if models[d].is_log else t[:, j])[moved]
+    out = (vals, J_start, J, g, acc)
+    if return_info:
+        out += (dict(J_bound=Jb, g_bound=gb, t_bound=tb, K=K, margin=margin),)
+    return out
 
 
 # -- device path -----------------------------------------------------------------
@@ -918,6 +1105,34 @@ def liar_device(fit, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weig
     if not trace:
         return rows
     return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
+
+
+def refine_device(fit, d_block, ld, n_cols, k, refine, trace=None):
+    """The climb of module doc "Refining" for rows [0, k) of the label-major
+    device block ``d_block`` (leading dimension ``ld``, ``n_cols`` columns;
+    offset-free values, as a pool's mirror holds them) under ``fit`` (the
+    joint labels' fit), in place: one tpe_joint_refine, nothing read back.
+    ``trace``: a dict that receives the device tensors ``J_start``, ``J_end``
+    (k), ``g_end`` (k, D_c) and ``accepted`` (k, int32)."""
+    eng, dj, sp = fit.eng, fit.dj, fit.sp
+    t, lib = eng.torch, eng.lib
+    refine = check_refine(refine)
+    Dc = len(moving_labels(dj.models))
+    k = int(k)
+    ptrs = [None] * 4
+    if trace is not None:
+        trace["J_start"] = t.empty(max(k, 1), dtype=t.float64, device=eng.device)[:k]
+        trace["J_end"] = t.empty(max(k, 1), dtype=t.float64, device=eng.device)[:k]
+        trace["g_end"] = t.empty((max(k, 1), max(Dc, 1)), dtype=t.float64,
+                                 device=eng.device)[:k, :Dc]
+        trace["accepted"] = t.empty(max(k, 1), dtype=t.int32, device=eng.device)[:k]
+        ptrs = [trace[name].data_ptr() for name in ("J_start", "J_end", "g_end", "accepted")]
+    (below, nb, _), (above, na, _) = fit.sets
+    _L.check(lib.tpe_joint_refine(dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
+                                  None if dj.tables is None else dj.tables.data_ptr(),
+                                  dj.n_tables, below.data_ptr(), nb, above.data_ptr(), na,
+                                  d_block.data_ptr(), ld, n_cols, k, refine, *ptrs, sp),
+             "tpe_joint_refine")
 
 
 # -- groups on the device (module doc, "Groups") ---------------------------------

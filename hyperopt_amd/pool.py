@@ -623,6 +623,8 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
         else:
             if st.lie is not None:  # (log L_above of the born rows stays, for the batch)
                 d.fits, d.parts = fits, _parts(eng, domain, st, P)
+            elif st.refine:  # (the fit stays, for the climb)
+                d.fits = fits
             _J.score_device(fits[0], d.vals, P, L, P, d.S, d.parts)
         init = 0
         if keep_terms:  # the joint labels have no term of their own
@@ -1377,25 +1379,37 @@ BATCH_LIAR = ("batch='liar' is supported with joint=True on a Pool or a SampledP
               "(suggest_from_pool, suggest_sampled, pick_batch)")
 
 
+REFINE = ("refine= moves the picked rows' continuous always-live labels up the joint "
+          "criterion: it needs joint=True (suggest_sampled, refine_configs)")
+
+
 class _Settings(object):
     """What a scoring and the picks after it run under: ``prior_weight``,
     ``gamma``, ``lf`` (linear forgetting), ``joint`` (``_joint_kw``) and
-    ``lie`` (None, or the lie's weight of ``batch="liar"``)."""
-    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie")
+    ``lie`` (None, or the lie's weight of ``batch="liar"``) and ``refine`` (the
+    steps the picked rows climb, joint.py "Refining"; 0: none)."""
+    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine")
 
-    def __init__(self, prior_weight, gamma, lf, joint=None, lie=None):
-        self.prior_weight, self.gamma, self.lf, self.joint, self.lie = \
-            prior_weight, gamma, lf, joint, lie
+    def __init__(self, prior_weight, gamma, lf, joint=None, lie=None, refine=0):
+        self.prior_weight, self.gamma, self.lf, self.joint, self.lie, self.refine = \
+            prior_weight, gamma, lf, joint, lie, refine
 
 
 def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
-              cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, pool=None):
+              cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, pool=None,
+              refine=None):
     """The ``_Settings`` of a public call's keywords, after the checks:
     ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
     ``"liar"``, on a ``lie_weight`` that is not a finite number > 0, and on
     what the batch is not built for (joint.py, "Not built"; ``pool``: the
-    call's pool, where it has one)."""
+    call's pool, where it has one).  A ``refine`` that is not None: ValueError
+    unless it is an integer >= 0 and ``joint`` is ``True``."""
     st = _Settings(prior_weight, gamma, lf, _joint_kw(joint, bandwidth, cat_smoothing))
+    if refine is not None:
+        st.refine = _J.check_refine(refine)
+        if st.joint is None or st.joint["tree"]:
+            raise ValueError(REFINE + "; the groups of joint='tree' / 'chain' and the "
+                             "factorised criterion (joint=False) are not refined")
     if batch is None:
         return st
     if batch != "liar":
@@ -1563,7 +1577,7 @@ def startup_rows(pool, seed, k, stale=None):
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0,
                       n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True,
                       distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
-                      cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0):
+                      cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, refine=None):
     """An ``algo`` for fmin (``partial(tpe.suggest_from_pool, pool=pool)``): one
     document per id, the first id the best untaken row of ``pool`` by
     ``score_configs``, the second the next best, and so on -- larger S first,
@@ -1598,10 +1612,18 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     pick keeps away from it (joint.py, "Batches") -- a batch for parallel
     evaluation that does not crowd one mode.  The first document is the one
     ``batch=None`` gives; the startup phase, ``distinct`` and the taken rules
-    are unchanged.  ``batch=None``: the k best rows of one score."""
+    are unchanged.  ``batch=None``: the k best rows of one score.
+
+    ``refine``: anything but None raises ValueError -- a fixed pool's rows are
+    a closed set, and a ``GridPool`` has no row to move
+    (``suggest_sampled(refine=N)``, ``refine_configs``)."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
+    if refine is not None:
+        raise ValueError(REFINE + ("; a GridPool has no row values to move"
+                                   if isinstance(pool, GridPool) else
+                                   "; a fixed pool's rows are a closed set"))
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
@@ -1681,11 +1703,75 @@ def take_rows(pool, rows_dev, k):
     return vals, active
 
 
+def _refine_rows(eng, d, k, refine):
+    """Rows ``d.rows_out[:k]`` of the mirror ``d`` climb J under the fit the
+    scoring left in ``d.fits`` (``joint.refine_device``): gathered into a
+    label-major block of k rows, refined there, and put back into the mirror's
+    values, where ``take_rows`` finds them.  Nothing is read back."""
+    idx = d.rows_out[:k]
+    block = d.vals.index_select(1, idx)
+    _J.refine_device(d.fits[0], block, k, d.vals.shape[0], k, refine)
+    d.vals.index_copy_(1, idx, block)
+
+
+def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weight=1.0, gamma=0.25,
+                   linear_forgetting=25, bandwidth=_J.BANDWIDTH, cat_smoothing=_J.CAT_SMOOTHING):
+    """The configurations ``vals`` -- (P, L) stored values in ``domain.params``
+    column order, NaN where a label is not live, as ``Pool.vals`` holds them --
+    after at most ``refine`` steps up the joint criterion of ``trials``
+    (joint.py, "Refining"; ``joint=True``'s fit): every row by itself, on the
+    device, its continuous always-live labels alone.  Returns the refined
+    (P, L) array; every entry that did not move keeps its bits, and
+    ``refine=0`` returns ``vals``.
+
+    ``return_trace``: (vals, J_before, J_after, accepted, g_end) -- J of the
+    rows before and after by ``score_configs(joint=True)``'s scorer (its bits;
+    the climb's own J is internal), the steps each row kept, and the gradient
+    (P, D_c) in the fit coordinates at the point it ended on.
+
+    ValueError: a space without an always-live label, more than
+    ``TPE_REFINE_MAX_CONT`` continuous ones, a ``refine`` that is not an
+    integer >= 0."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing,
+                   refine=0 if refine is None else refine)
+    labels = list(domain.params)
+    models = _J.label_models(domain)
+    cont = _J.moving_labels(models)
+    vals = np.array(vals, dtype=np.float64, ndmin=2)
+    pool = Pool.from_arrays(domain, vals, ~np.isnan(vals))
+    P, L = vals.shape
+    if P == 0:
+        none = np.zeros(0)
+        return (vals, none, none, np.zeros(0, np.int32), np.zeros((0, len(cont)))) \
+            if return_trace else vals
+    hist = T.collect_history(trials, labels)
+    eng = T.engine()
+    t = eng.torch
+    d = pool.device(eng)
+    ld = d.vals.shape[1]
+    fit = _fit(eng, domain, hist, L, st)[0]
+    trace = {} if return_trace else None
+    if return_trace:
+        J = t.empty((2, P), dtype=t.float64, device=eng.device)
+        _J.score_device(fit, d.vals, ld, L, P, J[0])
+    _J.refine_device(fit, d.vals, ld, L, P, st.refine, trace)
+    if return_trace:
+        _J.score_device(fit, d.vals, ld, L, P, J[1])
+    for j in [models[i].col for i in cont]:  # (continuous labels carry no offset)
+        vals[:, j] = d.vals[j, :P].cpu().numpy()
+    if not return_trace:
+        return vals
+    J = J.cpu().numpy()
+    return (vals, J[0], J[1], trace["accepted"].cpu().numpy(), trace["g_end"].cpu().numpy())
+
+
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
                     verbose=True, distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
                     cat_smoothing=_J.CAT_SMOOTHING, draw="factorised", batch=None,
-                    lie_weight=1.0):
+                    lie_weight=1.0, refine=None):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -1742,7 +1828,17 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     joining the above mixture with weight ``lie_weight`` (joint.py,
     "Batches"; ``suggest_from_pool``).  log L_above is the one the scoring
     leaves: the pool's born parts under ``draw="joint"``.  ``keep``,
-    ``distinct`` and the startup phase are unchanged."""
+    ``distinct`` and the startup phase are unchanged.
+
+    ``refine=N`` (needs ``joint=True``; ValueError otherwise, and for anything
+    but an integer >= 0): the best draw lies between the mixture's peaks and
+    the rows that happen to fall near them, so after the k rows are picked
+    (plain or ``batch="liar"``) their continuous always-live labels climb J
+    on the device for at most N steps (joint.py, "Refining";
+    ``refine_configs``): the documents carry the refined values, their
+    quantized and discrete labels and every label under a ``switch`` those of
+    the picked rows.  ``keep`` and ``distinct`` judge the rows as drawn.
+    ``refine=None`` or 0: the rows as they fell."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
@@ -1753,9 +1849,11 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
                          "joint=True")
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
-                   lie_weight)
+                   lie_weight, refine=refine)
     if st.joint is not None:
         _joint_cols(domain, st.joint)  # (ValueError on a space without a joint label)
+    if st.refine:  # (ValueError over the kernel's limit of continuous labels)
+        _J.moving_labels(_J.label_models(domain))
     labels = list(domain.params)
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)
@@ -1791,6 +1889,8 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     rows = _pick(eng, pool, d, k, hist, distinct, st)
     if not len(rows):
         return []
+    if st.refine:
+        _refine_rows(eng, d, len(rows), st.refine)
     vals, active = take_rows(pool, d.rows_out, len(rows))
     pool.mark_taken(rows)
     configs = [_stored_config(domain, labels, vals[i], active[i]) for i in range(len(rows))]

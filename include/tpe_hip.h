@@ -1126,6 +1126,43 @@ int tpe_joint_lie_picks(const tpe_joint_label* host_labels, const tpe_joint_labe
                         int64_t k, int64_t* out_rows, int64_t* out_count, double* S_at_pick,
                         double* S_k, void* scratch, void* stream);
 
+/* ---- rows that climb the joint criterion ---------------------------------------
+ * (tpe.suggest_sampled(joint=True, refine=N), tpe.refine_configs;
+ * hyperopt_amd/joint.py, "Refining".)  Rows [0, n_rows) of the label-major block
+ * `vals` (ld, n_cols; label d's column is labels[d].col) move, each by itself,
+ * in the fit coordinates t of their TPE_JOINT_CONT labels -- D_c of them, in
+ * list order -- towards a maximum of J(t) = log L_below(t) - log L_above(t), the
+ * two prepared sets' mixtures as tpe_joint_score states them.  Per set, with
+ * r_i = exp(a_i - log L): dlogL_d = sum_i r_i (mu_{i,d} - t_d) / sigma_{i,d}^2
+ * (0 where log L = -inf), g = dlogL_below - dlogL_above.  From h = 1, `refine`
+ * times at the most and while h >= 2^-20:
+ *   t'_d = t_d + (h s_d^2) g_d, for TPE_JOINT_BOUNDED lifted to lo and cut to
+ *   nextafter(hi, -inf); s_d the below set's bandwidth (prior_sigma when n_below
+ *   is 0); J(t') > J(t): t, J, g <- those of t', h = min(1, 2 h); else h = h / 2.
+ * A row whose first J is NaN or infinite does not move.  The block is updated in
+ * place: a label whose t changed stores exp(t) (TPE_JOINT_LOG) or t; every
+ * other entry keeps its bits.  Optional outputs (device, may be NULL): J_start,
+ * J_end (n_rows doubles: the climb's own first and last J), g_end (n_rows x D_c,
+ * row-major: g at the last accepted point) and accepted (n_rows int32: steps
+ * kept).  Inside a_i the quantized and discrete labels' factors are added
+ * first, then the continuous ones, each in list order: J_start equals
+ * tpe_joint_score's difference to rounding, not bit for bit.  D_c == 0: no
+ * row moves; J is evaluated once where an output wants it, else nothing runs.
+ *
+ * One block per row and the whole climb in one launch; a row's bits depend on
+ * the row, the sets and `refine` alone; no atomics.  Limits as tpe_joint_score,
+ * and D_c <= TPE_REFINE_MAX_CONT, else TPE_E_UNSUPPORTED; bad arguments return
+ * TPE_E_ARG before any launch.  Asynchronous on `stream`, no allocation. */
+#define TPE_REFINE_MAX_CONT 16
+int tpe_joint_refine(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                     int n_labels, const double* tables, int64_t n_tables,
+                     const double* set_below, int64_t n_below, const double* set_above,
+                     int64_t n_above, double* vals, int64_t ld, int n_cols, int64_t n_rows,
+                     int refine, double* J_start, double* J_end, double* g_end,
+                     int32_t* accepted, void* stream);
+/* host: TPE_REFINE_MAX_CONT as the library was built */
+int tpe_joint_refine_max_cont(void);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
