@@ -75,6 +75,7 @@ JOINT_LOG, JOINT_BOUNDED = 1, 2
 JOINT_MAX_CAT = 65536
 JOINT_OUT_SCATTER, JOINT_OUT_ADD = 1, 2  # tpe_joint_score_rows' out_mode
 REFINE_MAX_CONT = 16  # tpe_joint_refine's continuous labels (TPE_REFINE_MAX_CONT)
+LOO_MAX_GRID = 16  # tpe_joint_loo's multipliers per call (TPE_LOO_MAX_GRID)
 GRID_JOINT_STORE, GRID_JOINT_ADD = 0, 1  # tpe_grid_joint_score's out_mode
 OP_ARGS = 23
 OP_DTYPE = np.dtype([("code", "<i4"), ("n_args", "<i4"), ("a", "<i8", (OP_ARGS,))], align=True)
@@ -206,6 +207,10 @@ _SIGNATURES = {
     "tpe_joint_refine": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I,
                               _P, _P, _P, _P, _P]),
     "tpe_joint_refine_max_cont": (_I, []),
+    "tpe_joint_loo_scratch_bytes": (_I64, [_I, _I, _I64, _I]),
+    "tpe_joint_loo": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, ctypes.c_double,
+                           ctypes.c_double, _P, _I, _P, _P, _P]),
+    "tpe_joint_loo_max_grid": (_I, []),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),
@@ -302,6 +307,9 @@ def load():
     if lib.tpe_joint_refine_max_cont() != REFINE_MAX_CONT:
         raise ImportError("hyperopt_amd: TPE_REFINE_MAX_CONT is %d in the library, %d here"
                           % (lib.tpe_joint_refine_max_cont(), REFINE_MAX_CONT))
+    if lib.tpe_joint_loo_max_grid() != LOO_MAX_GRID:
+        raise ImportError("hyperopt_amd: TPE_LOO_MAX_GRID is %d in the library, %d here"
+                          % (lib.tpe_joint_loo_max_grid(), LOO_MAX_GRID))
     _lib = lib
     return lib
 

@@ -273,6 +273,38 @@ row's whole climb in one launch (inside a_i the device adds the fixed labels'
 factors first, then the moving ones': its J equals the scorer's to rounding,
 and ``tpe.refine_configs`` reports J before and after from ``score_device``).
 
+Bandwidth (``bandwidth="loo"``, ``tpe.joint_bandwidth``, csrc/tpe_joint_loo.hip,
+DESIGN 3.5.11).  Every path above takes one multiplier h in ``sigma = h sigma_p
+n ** (-1 / (D + 4))``; ``BANDWIDTH`` is a guess.  ``"loo"`` takes the grid value
+that maximises the mixtures' leave-one-out log-likelihood on their own sets.
+
+  set          a group's set of n rows in ascending row order, its label list
+               ``models`` (D labels), ``sigma(h) = bandwidths(models, n, h)``, ``v =
+               forgetting_weights(n, lf)``, ``W = sum(v) + prior_weight``.  Row i's
+               x_i are its own stored history values, converted as a component's
+               are (``randint``'s ``low`` comes off once, for rows and components
+               alike).
+  row          ``a_ij = log v_j + sum_d log k_{d,j}(x_{i,d})`` for every trial
+               component j != i -- excluded by index: another trial with the same
+               values stays in -- and ``a_i,prior = log prior_weight + sum_d log
+               k_{d,prior}(x_{i,d})``; the factors are those of "Factors" with
+               ``sigma(h)``.  ``LOO_i(h) = logsumexp(a_i.) - log(W - v_i)``.
+  set score    ``Q_set(h) = sum_i v_i LOO_i(h) / sum_i v_i``; a set with n < 2 has
+               Q_set = 0 for every h (nothing in it depends on h).
+  choice       ``Q(h)`` = the sum of Q_set over the groups (``joint=True``: the
+               joint labels' one group; ``"tree"``: those of ``joint_groups``),
+               below set then above set.  The multiplier is the first grid value
+               with the largest finite Q; ``BANDWIDTH`` where no set has n >= 2 or
+               no Q is finite.
+  grid         ascending, finite, > 0, 1 <= B <= ``TPE_LOO_MAX_GRID`` (16) values;
+               the default ``LOO_GRID`` = BANDWIDTH 2^(k / 2), k = -6 .. 9.
+
+``loo_numpy`` is this definition in numpy; ``loo_device`` runs one
+tpe_joint_loo per set -- all B multipliers and all n^2 pairs in one call -- and
+reads the (G, 2, B) curves back once.  ``bandwidth="loo"`` resolves the
+multiplier once per public call, where the fit is made, over ``LOO_GRID``; the
+float is what the fit, the lie, the climb and the settings hold from there on.
+
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
 on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
@@ -282,6 +314,10 @@ does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
 under the factorised criterion (its adaptive bandwidths depend on the sorted
 neighbours: no component can be added without a refit).  ``refine`` under
 ``joint="tree"`` / ``"chain"`` (a group's labels move only where it is live).
+``bandwidth="loo"`` under ``joint="chain"`` (its fits are over ctx + g and enter
+as a ratio: the likelihood of a set under its own fit is not what they are
+ranked by) and on a ``GridPool``.  Per-set or per-label multipliers (``fit``
+takes one float).
 """
 from __future__ import annotations
 
@@ -881,6 +917,93 @@ def refine_numpy(domain, hist, vals, refine, prior_weight=1.0, gamma=0.25, linea
     return out
 
 
+# -- bandwidth (module doc, "Bandwidth") -----------------------------------------
+LOO_GRID = BANDWIDTH * 2.0 ** (np.arange(-6, 10) / 2.0)
+LOO_BAD_GRID = ("a bandwidth grid is 1 to %d multipliers: ascending, finite, > 0"
+                % _L.LOO_MAX_GRID)
+LOO_CHAIN = ("bandwidth='loo' is not built for joint='chain': its fits are over ctx + g and "
+             "enter as a ratio (joint.py, \"Not built\"); joint=True or joint='tree'")
+LOO_GRID_POOL = ("bandwidth='loo' is not built for a GridPool (joint.py, \"Not built\"): pass the "
+                 "float of tpe.joint_bandwidth(domain, trials)")
+
+
+def check_grid(grid):
+    """``grid`` as a float64 vector (None: ``LOO_GRID``); ValueError(LOO_BAD_GRID)."""
+    if grid is None:
+        return LOO_GRID.copy()
+    try:
+        grid = np.array(grid, np.float64, ndmin=1)
+    except (TypeError, ValueError):
+        raise ValueError(LOO_BAD_GRID)
+    if (grid.ndim != 1 or not 1 <= grid.size <= _L.LOO_MAX_GRID or
+            not (np.isfinite(grid) & (grid > 0.0)).all() or not (np.diff(grid) > 0.0).all()):
+        raise ValueError(LOO_BAD_GRID)
+    return grid
+
+
+def loo_sets(domain, hist, gamma, tree=False):
+    """[(models, [below rows, above rows])] per group the likelihood covers:
+    the joint labels' one group, or with ``tree`` those of ``joint_groups``."""
+    domain = as_domain(domain)
+    if tree == "chain":
+        raise ValueError(LOO_CHAIN)
+    groups = [grp.labels for grp in joint_groups(domain)] if tree else [None]
+    masks = split_sets(hist, gamma)
+    out = []
+    for group in groups:
+        models = label_models(domain, group)
+        cols = [m.col for m in models]
+        out.append((models, [set_rows(hist, mask, cols) for mask in masks]))
+    return out
+
+
+def _loo_set(models, hist, rows, grid, lf, prior_weight, smoothing):
+    """Q_set over ``grid`` of the set of history rows ``rows``: (B,)."""
+    n = rows.size
+    if n < 2:
+        return np.zeros(grid.size)
+    v = forgetting_weights(n, lf)
+    W = v.sum() + float(prior_weight)
+    x = np.asarray(hist.vals)[rows]
+    own = np.arange(n)
+    Q = np.zeros(grid.size)
+    for b, h in enumerate(grid):
+        sig = bandwidths(models, n, h)
+        with np.errstate(divide="ignore"):
+            a = np.broadcast_to(np.log(np.concatenate([v, [float(prior_weight)]])),
+                                (n, n + 1)).copy()
+        for d, m in enumerate(models):
+            with np.errstate(invalid="ignore"):
+                a = a + _label_term(m, hist, rows, sig[d], x[:, m.col], smoothing)
+        a[own, own] = -np.inf  # (itself, by index)
+        with np.errstate(all="ignore"):
+            Q[b] = (v * (_log_sum_exp(a) - np.log(W - v))).sum() / v.sum()
+    return Q
+
+
+def loo_numpy(domain, hist, grid=None, tree=False, prior_weight=1.0, gamma=0.25,
+              linear_forgetting=25, cat_smoothing=CAT_SMOOTHING):
+    """Q_set (module doc, "Bandwidth") of every group's below and above set over
+    the multipliers ``grid``, in vectorised numpy: fp64 (G, 2, B)."""
+    grid = check_grid(grid)
+    return np.asarray([[_loo_set(models, hist, rows, grid, linear_forgetting, prior_weight,
+                                 cat_smoothing) for rows in sets]
+                       for models, sets in loo_sets(domain, hist, gamma, tree)])
+
+
+def loo_choice(grid, Q_sets, sizes):
+    """The multiplier of module doc "Bandwidth": ``Q_sets`` (G, 2, B) summed
+    over the sets, the first grid value with the largest finite sum;
+    ``BANDWIDTH`` where no set of ``sizes`` (the sets' n) reaches 2 or no sum
+    is finite."""
+    with np.errstate(invalid="ignore"):
+        Q = np.asarray(Q_sets, np.float64).sum((0, 1))
+    fin = np.isfinite(Q)
+    if not (np.asarray(sizes) >= 2).any() or not fin.any():
+        return BANDWIDTH
+    return float(np.asarray(grid)[int(np.argmax(np.where(fin, Q, -np.inf)))])
+
+
 # -- device path -----------------------------------------------------------------
 class _DeviceJoint(object):
     """A space's joint labels as the kernels take them: the label records on
@@ -1133,6 +1256,47 @@ def refine_device(fit, d_block, ld, n_cols, k, refine, trace=None):
                                   dj.n_tables, below.data_ptr(), nb, above.data_ptr(), na,
                                   d_block.data_ptr(), ld, n_cols, k, refine, *ptrs, sp),
              "tpe_joint_refine")
+
+
+def loo_device(eng, domain, hist, seen, gamma, n_cols, grid=None, prior_weight=1.0,
+               linear_forgetting=25, cat_smoothing=CAT_SMOOTHING, tree=False):
+    """``loo_numpy`` on the device: Q_set of every group's below and above set
+    over ``grid`` as a numpy (G, 2, B) array.  One tpe_joint_loo per set with n
+    >= 2 -- every pair of its rows once, for all B multipliers -- reading the
+    history ``seen`` (``fit``'s tuple) through the set's row list; one readback
+    after the last."""
+    t, lib = eng.torch, eng.lib
+    grid = np.ascontiguousarray(check_grid(grid))
+    sets = loo_sets(domain, hist, gamma, tree)
+    _alive, sv, sa, sld, srows, _n = seen
+    view = hist.rows if srows is not None else None  # (positions -> rows of the mirror)
+    out = t.zeros((len(sets), 2, grid.size), dtype=t.float64, device=eng.device)
+    sp = stream_ptr(eng)
+    keep = []  # (what a launch reads stays allocated until the readback)
+    for g, (models, pair) in enumerate(sets):
+        if max(rows.size for rows in pair) < 2:
+            continue
+        dj = _device_labels(eng, models, cat_smoothing)
+        n_quant = sum(m.kind == _L.JOINT_QUANT for m in models)
+        for which, rows in enumerate(pair):
+            n = int(rows.size)
+            if n < 2:  # (Q_set = 0: ``out`` holds it)
+                continue
+            if view is not None:
+                rows = np.asarray(view)[rows]
+            v = forgetting_weights(n, linear_forgetting)
+            drows = t.from_numpy(np.ascontiguousarray(rows, np.int32)).to(eng.device)
+            dv = t.from_numpy(np.ascontiguousarray(v)).to(eng.device)
+            scratch = t.empty(lib.tpe_joint_loo_scratch_bytes(len(models), n_quant, n, grid.size),
+                              dtype=t.uint8, device=eng.device)
+            keep.append((dj, drows, dv, scratch))
+            _L.check(lib.tpe_joint_loo(
+                dj.host.ctypes.data, dj.dev.data_ptr(), len(models),
+                None if dj.tables is None else dj.tables.data_ptr(), dj.n_tables, sv, sa, sld,
+                n_cols, drows.data_ptr(), n, dv.data_ptr(), float(v.sum()), float(prior_weight),
+                grid.ctypes.data, grid.size, out[g, which].data_ptr(), scratch.data_ptr(), sp),
+                "tpe_joint_loo")
+    return out.cpu().numpy()
 
 
 # -- groups on the device (module doc, "Groups") ---------------------------------

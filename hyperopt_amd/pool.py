@@ -1016,6 +1016,8 @@ def _grid_settings(st, pool):
     (GRID_CHAIN); no-op for any other pool."""
     if st.joint is None or not isinstance(pool, GridPool):
         return
+    if st.joint["bandwidth"] == "loo":
+        raise ValueError(_J.LOO_GRID_POOL)
     if not pool.joint:
         raise ValueError(GRID_JOINT)
     if st.joint["tree"] == "chain":
@@ -1131,10 +1133,26 @@ def _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts):
 
 def _fit(eng, domain, hist, n_cols, st, tree=None):
     """``joint.fit`` of the history under the settings ``st`` (``tree``: in
-    place of the settings' own)."""
+    place of the settings' own).  ``bandwidth="loo"`` is resolved here, once:
+    the settings hold the float afterwards."""
+    if st.joint["bandwidth"] == "loo":
+        st.joint["bandwidth"] = _loo_bandwidth(eng, domain, hist, n_cols, None, st.prior_weight,
+                                               st.gamma, st.lf, st.joint["cat_smoothing"],
+                                               st.joint["tree"])[0]
     return _J.fit(eng, domain, hist, _seen_rows(eng, hist), st.gamma, n_cols, st.prior_weight,
                   st.lf, st.joint["bandwidth"], st.joint["cat_smoothing"],
                   st.joint["tree"] if tree is None else tree)
+
+
+def _loo_bandwidth(eng, domain, hist, n_cols, grid, prior_weight, gamma, lf, cat_smoothing, tree):
+    """(h, grid, Q_sets): the multiplier of joint.py "Bandwidth" for the history
+    ``hist`` over ``grid`` (None: ``joint.LOO_GRID``), from the device's curves
+    (``joint.loo_device``: one readback)."""
+    grid = _J.check_grid(grid)
+    Q = _J.loo_device(eng, domain, hist, _seen_rows(eng, hist), gamma, n_cols, grid, prior_weight,
+                      lf, cat_smoothing, tree)
+    sizes = [[rows.size for rows in pair] for _m, pair in _J.loo_sets(domain, hist, gamma, tree)]
+    return _J.loo_choice(grid, Q, sizes), grid, Q
 
 
 def _parts(eng, domain, st, P):
@@ -1359,6 +1377,16 @@ def _joint_kw(joint, bandwidth, cat_smoothing):
         return None
     else:
         tree = False
+    if isinstance(bandwidth, str):
+        # "loo": the multiplier is fitted where the fit is made (``_fit``), and
+        # the float takes this entry's place from there on
+        if bandwidth != "loo":
+            raise ValueError("bandwidth=%r: a number > 0, or 'loo'" % (bandwidth,))
+        if tree == "chain":
+            raise ValueError(_J.LOO_CHAIN)
+        if not cat_smoothing >= 0.0:
+            raise ValueError("cat_smoothing=%r must be >= 0" % (cat_smoothing,))
+        return dict(bandwidth="loo", cat_smoothing=float(cat_smoothing), tree=tree)
     if not bandwidth > 0.0 or not cat_smoothing >= 0.0:
         raise ValueError("bandwidth=%r must be > 0, cat_smoothing=%r >= 0"
                          % (bandwidth, cat_smoothing))
@@ -1528,6 +1556,11 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     flat space S has the bits of ``joint=True``.  ``return_terms`` gives (S,
     terms, C): ``terms`` all NaN, C the (P, G) matrix of J_root and the C_g,
     NaN where group g is not live.  A ``GridPool`` raises ValueError.
+
+    ``bandwidth="loo"`` (here and wherever ``bandwidth=`` is taken, with
+    ``joint=True`` or ``"tree"``): the multiplier ``joint_bandwidth`` returns
+    for these trials, fitted once per call (joint.py, "Bandwidth").
+    ``joint="chain"`` and a ``GridPool`` raise ValueError.
 
     Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
@@ -1765,6 +1798,32 @@ def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weigh
         return vals
     J = J.cpu().numpy()
     return (vals, J[0], J[1], trace["accepted"].cpu().numpy(), trace["g_end"].cpu().numpy())
+
+
+def joint_bandwidth(domain, trials, grid=None, joint=True, prior_weight=1.0, gamma=0.25,
+                    linear_forgetting=25, cat_smoothing=_J.CAT_SMOOTHING, return_curves=False):
+    """The bandwidth multiplier that maximises the leave-one-out log-likelihood
+    of the joint mixtures of ``trials`` on their own sets (joint.py,
+    "Bandwidth"): a float of ``grid`` (None: ``joint.LOO_GRID``, 16 values
+    around ``joint.BANDWIDTH``), what ``bandwidth="loo"`` passes on.  ``joint``:
+    True for the always-live labels' mixture, ``"tree"`` for every group's.
+    ``return_curves``: (h, grid, Q_sets) -- Q_sets the (G, 2, B) curves per
+    group and set (below, above), which the choice sums.
+
+    ValueError: a bad grid, ``joint="chain"`` or a false ``joint``, a space
+    without the labels or groups ``joint`` needs."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    grid = _J.check_grid(grid)
+    jkw = _joint_kw(joint, "loo", cat_smoothing)
+    if jkw is None:
+        raise ValueError("joint_bandwidth: joint=True or joint='tree'")
+    _joint_cols(domain, jkw)
+    labels = list(domain.params)
+    hist = T.collect_history(trials, labels)
+    out = _loo_bandwidth(T.engine(), domain, hist, len(labels), grid, prior_weight, gamma,
+                         linear_forgetting, jkw["cat_smoothing"], jkw["tree"])
+    return out if return_curves else out[0]
 
 
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,

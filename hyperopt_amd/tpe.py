@@ -49,7 +49,10 @@ it is about to become, so a batch for parallel evaluation spreads out
 (``pick_batch``: the rows alone; ``joint_liar_numpy``).
 ``suggest_sampled(joint=True, refine=N)`` lets the picked rows climb the joint
 criterion on their continuous labels, on the device (``refine_configs``: any
-rows; ``joint_refine_numpy``).
+rows; ``joint_refine_numpy``).  ``bandwidth="loo"`` (with ``joint=True`` /
+``"tree"``) fits the joint mixtures' bandwidth multiplier by leave-one-out
+likelihood on the device, once per call (``joint_bandwidth``: the float and its
+curves; ``joint_loo_numpy``).
 """
 from __future__ import annotations
 
@@ -803,8 +806,9 @@ def _suggest_many(requests, shard_studies=False):
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan,  # noqa: E402,F401
-                   pick_batch, refine_configs, score_configs, suggest_from_pool, suggest_sampled)
+                   joint_bandwidth, pick_batch, refine_configs, score_configs, suggest_from_pool, suggest_sampled)
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_contexts,
                     joint_groups, joint_labels, liar_numpy as joint_liar_numpy,
+                    loo_numpy as joint_loo_numpy,
                     refine_numpy as joint_refine_numpy, score_numpy as joint_score_numpy)

@@ -1163,6 +1163,41 @@ int tpe_joint_refine(const tpe_joint_label* host_labels, const tpe_joint_label* 
 /* host: TPE_REFINE_MAX_CONT as the library was built */
 int tpe_joint_refine_max_cont(void);
 
+/* ---- a set's leave-one-out log-likelihood over a grid of bandwidths -------------
+ * (tpe.joint_bandwidth, bandwidth="loo"; hyperopt_amd/joint.py, "Bandwidth".)
+ * The set is rows[0 .. n) of a label-major history, read as tpe_joint_prep reads
+ * it (rows NULL: rows 0 .. n - 1).  With v (device, n doubles) the rows' weights,
+ * sum_v their sum, W = sum_v + prior_weight, and for multiplier h = grid[b]
+ * (host, n_grid doubles: ascending, finite, > 0) the trial components' bandwidths
+ * sigma_d = h prior_sigma_d n^(-1 / (n_labels + 4)):
+ *   a_ij   = log v_j + sum_d log k_{d,j}(x_i,d)     j != i (by index), x_i row
+ *            i's own values, the factors tpe_joint_score's
+ *   a_i,p  = log prior_weight + sum_d log k_{d,prior}(x_i,d)
+ *   LOO_i  = logsumexp(a_i., a_i,p) - log(W - v_i)
+ *   out[b] = sum_i v_i LOO_i / sum_v                 (device, n_grid doubles)
+ * n < 2: out[b] = 0 (nothing depends on h).  One call walks every pair (i, j)
+ * once for all n_grid multipliers: the continuous labels' squared distance and
+ * the discrete labels' hit / miss sum do not depend on h, a B x n table holds
+ * what depends on (j, h) alone, and only a quantized label's mass is formed per
+ * (pair, label, multiplier).  Partials per (component chunk of TPE_JOINT_CHUNK,
+ * multiplier, row) in `scratch` (tpe_joint_loo_scratch_bytes(n_labels, n_quant,
+ * n, n_grid) bytes, n_quant the number of TPE_JOINT_QUANT labels; -1: bad
+ * arguments; 16-byte aligned), merged in chunk order, the rows by a block tree
+ * and the blocks in block order: no atomics, the result is a function of the
+ * inputs alone.  Limits as tpe_joint_score and n_grid <= TPE_LOO_MAX_GRID; bad
+ * arguments return TPE_E_ARG before any launch.  Asynchronous on `stream`, no
+ * allocation. */
+#define TPE_LOO_MAX_GRID 16
+int64_t tpe_joint_loo_scratch_bytes(int n_labels, int n_quant, int64_t n, int n_grid);
+int tpe_joint_loo(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                  int n_labels, const double* tables, int64_t n_tables,
+                  const double* hist_vals, const uint8_t* hist_active, int64_t hist_ld,
+                  int hist_cols, const int32_t* rows, int64_t n, const double* v, double sum_v,
+                  double prior_weight, const double* grid, int n_grid, double* out,
+                  void* scratch, void* stream);
+/* host: TPE_LOO_MAX_GRID as the library was built */
+int tpe_joint_loo_max_grid(void);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
