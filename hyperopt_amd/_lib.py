@@ -211,6 +211,9 @@ _SIGNATURES = {
     "tpe_joint_loo": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, ctypes.c_double,
                            ctypes.c_double, _P, _I, _P, _P, _P]),
     "tpe_joint_loo_max_grid": (_I, []),
+    "tpe_joint_loo_label_scratch_bytes": (_I64, [_I, _I, _I64, _I]),
+    "tpe_joint_loo_label": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P,
+                                 ctypes.c_double, ctypes.c_double, _P, _I, _P, _I, _P, _P, _P]),
     "tpe_run_ops": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "tpe_set_issue_threads": (_I, [_I]),
     "tpe_ops_capture": (_I, [_P, _I, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I)]),

@@ -37,17 +37,10 @@
 // 4, 8 and 16, and once more each for a label list with a quantized label (the
 // calls of log_mass cost registers that a list without one does not pay).  No
 // atomics, every sum has a fixed order: Q's bits depend on the inputs alone.
-#include "tpe_joint.hpp"
+#include "tpe_joint_loo.hpp"
 
 namespace tpe {
 namespace {
-constexpr int kLMaxB = TPE_LOO_MAX_GRID;
-
-struct LooGrid {
-  double scale[kLMaxB];  // s_b = h_b n^(-1/(D+4))
-  double inv[kLMaxB];    // 1 / s_b^2
-};
-
 // the scratch, in doubles: partials (double2) | mu | edges | constants | block sums
 struct LooLayout {
   int64_t chunks, blocks, mu, edges, cst, blk, total;
@@ -62,11 +55,6 @@ inline LooLayout loo_layout(int n_labels, int n_quant, int64_t n, int n_grid) {
   L.blk = L.cst + (int64_t)n_grid * n;
   L.total = L.blk + (int64_t)n_grid * L.blocks;
   return L;
-}
-
-// -log Z of a bounded label's component
-__device__ __forceinline__ double neg_log_z(const tpe_joint_label& lab, double mu, double sigma) {
-  return -log(normal_cdf(lab.hi, mu, sigma) - normal_cdf(lab.lo, mu, sigma));
 }
 
 // thread (j, b): component j's constant under multiplier b; b == 0 also gathers
@@ -117,16 +105,6 @@ __global__ __launch_bounds__(kJBS) void k_loo_prep(const tpe_joint_label* __rest
     }
   }
   cst[(int64_t)b * n + j] = acc;
-}
-
-// (m, s) <- (m, s) joined with the exponent a: one exp whichever is larger
-__device__ __forceinline__ void loo_join(double& m, double& s, double a) {
-  if (a != kNegInf) {
-    const double d = a - m;  // (m = -inf: +inf, e = 0 and s, which is 0, becomes 1)
-    const double e = exp(-fabs(d));
-    s = d > 0.0 ? fma(s, e, 1.0) : s + e;
-    m = d > 0.0 ? a : m;
-  }
 }
 
 template <int NB, bool QUANT>
@@ -307,16 +285,6 @@ __global__ __launch_bounds__(kJBS) void k_loo_merge(const tpe_joint_label* __res
     }
     if (tid == 0) blk[(int64_t)b * gridDim.x + blockIdx.x] = red[0];
   }
-}
-
-// out[b] = the block sums in block order, over sum v (no block: 0, the n < 2 rule)
-__global__ void k_loo_final(const double* __restrict__ blk, int64_t n_blocks, int n_grid,
-                            double sum_v, double* __restrict__ out) {
-  const int b = threadIdx.x;
-  if (b >= n_grid) return;
-  double s = 0.0;
-  for (int64_t k = 0; k < n_blocks; ++k) s = s + blk[(int64_t)b * n_blocks + k];
-  out[b] = n_blocks ? s / sum_v : 0.0;
 }
 
 template <int NB>

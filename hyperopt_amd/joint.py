@@ -305,6 +305,44 @@ reads the (G, 2, B) curves back once.  ``bandwidth="loo"`` resolves the
 multiplier once per public call, where the fit is made, over ``LOO_GRID``; the
 float is what the fit, the lie, the climb and the settings hold from there on.
 
+Bandwidth per label (``bandwidth="loo-label"``, ``tpe.joint_bandwidths``,
+csrc/tpe_joint_loo_label.hip).  One h for every label lets the
+labels the loss does not depend on take their share of the product kernel's
+distance.  Here every label with a bandwidth (continuous or quantized) has its
+own multiplier, chosen by the same likelihood, one coordinate at a time.
+
+  multipliers  ``bandwidths(models, n, bandwidth)`` also takes a mapping label ->
+               multiplier: ``sigma_d = h_d sigma_p,d n ** (-1 / (D + 4))``; a label
+               the mapping does not name takes ``BANDWIDTH``, a discrete label has
+               no bandwidth.  A float is unchanged bit for bit, and a mapping whose
+               values all equal h gives the float's bits on every path: prep,
+               score, tree, chain, draw, lie and refine read sigma through this
+               function alone.
+  curve        for a group's set (the sets, v, W, a_ij, LOO_i, Q_set and the n < 2
+               rule of "Bandwidth"), current multipliers h, a label d with a
+               bandwidth and a grid of B values: ``Q_set,d(b)`` = Q_set under
+               sigma_e of h_e for e != d and sigma_d of ``grid[b]``.  ``Q_d(b)`` is
+               the sum over the below and the above set of d's group; a label sits
+               in exactly one group, so no other group depends on it.
+  choice       start: every label at ``loo_choice`` over the same grid (what
+               ``bandwidth="loo"`` returns); where that falls back -- no set with
+               n >= 2, no finite Q -- every label gets ``BANDWIDTH`` and nothing
+               else is run.  Then at most ``sweeps`` (default 2) passes over the
+               groups in ``joint_groups`` order and their labels with a bandwidth
+               in list order: label d keeps its value unless some grid value's Q_d
+               is finite and strictly larger than Q_d at the current value, and
+               then takes the first grid value with the largest finite Q_d.  An
+               update is visible to the next label (Gauss-Seidel), so Q never
+               falls along the run; a pass that changes nothing ends it.  Every
+               multiplier returned is a grid value (``check_grid``'s rules).
+
+``loo_label_numpy`` is the curve and ``loo_label_fit_numpy`` the run in numpy;
+``loo_label_choice`` is the rule both it and the device path go through.
+``loo_label_device`` runs ``loo_device`` for the start, then per visited label
+two tpe_joint_loo_label calls (below set, above set) and one readback of the B
+values: the choice is made on the host and steers the next call.
+``bandwidth="loo-label"`` is resolved where ``"loo"`` is, into the mapping.
+
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
 on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
@@ -314,15 +352,16 @@ does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
 under the factorised criterion (its adaptive bandwidths depend on the sorted
 neighbours: no component can be added without a refit).  ``refine`` under
 ``joint="tree"`` / ``"chain"`` (a group's labels move only where it is live).
-``bandwidth="loo"`` under ``joint="chain"`` (its fits are over ctx + g and enter
-as a ratio: the likelihood of a set under its own fit is not what they are
-ranked by) and on a ``GridPool``.  Per-set or per-label multipliers (``fit``
-takes one float).
+``bandwidth="loo"`` / ``"loo-label"`` under ``joint="chain"`` (its fits are over
+ctx + g and enter as a ratio: the likelihood of a set under its own fit is not
+what they are ranked by) and on a ``GridPool`` (both take a float or a mapping).
+Per-set multipliers (a label has one multiplier for its below and its above set).
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -516,8 +555,14 @@ def split_sets(hist, gamma):
 
 def bandwidths(models, n, bandwidth):
     """sigma of the trial components of a set of n rows, per joint label (0
-    for a discrete label, and for n == 0: there is no such component)."""
+    for a discrete label, and for n == 0: there is no such component).
+    ``bandwidth``: one multiplier, or a mapping label -> multiplier (a label it
+    does not name takes ``BANDWIDTH``)."""
     D = len(models)
+    if isinstance(bandwidth, Mapping):  # (module doc, "Bandwidth per label")
+        root = float(n) ** (-1.0 / (D + 4)) if n else 0.0
+        return np.asarray([float(bandwidth.get(m.label, BANDWIDTH)) * root * m.sigma
+                           for m in models])
     scale = float(bandwidth) * float(n) ** (-1.0 / (D + 4)) if n else 0.0
     return np.asarray([scale * m.sigma for m in models])
 
@@ -957,18 +1002,18 @@ def loo_sets(domain, hist, gamma, tree=False):
     return out
 
 
-def _loo_set(models, hist, rows, grid, lf, prior_weight, smoothing):
-    """Q_set over ``grid`` of the set of history rows ``rows``: (B,)."""
+def _loo_set(models, hist, rows, sigmas, lf, prior_weight, smoothing):
+    """Q_set of the set of history rows ``rows`` under each row of ``sigmas``
+    ((B, D): the trial components' sigma per label): (B,)."""
     n = rows.size
     if n < 2:
-        return np.zeros(grid.size)
+        return np.zeros(len(sigmas))
     v = forgetting_weights(n, lf)
     W = v.sum() + float(prior_weight)
     x = np.asarray(hist.vals)[rows]
     own = np.arange(n)
-    Q = np.zeros(grid.size)
-    for b, h in enumerate(grid):
-        sig = bandwidths(models, n, h)
+    Q = np.zeros(len(sigmas))
+    for b, sig in enumerate(sigmas):
         with np.errstate(divide="ignore"):
             a = np.broadcast_to(np.log(np.concatenate([v, [float(prior_weight)]])),
                                 (n, n + 1)).copy()
@@ -986,9 +1031,20 @@ def loo_numpy(domain, hist, grid=None, tree=False, prior_weight=1.0, gamma=0.25,
     """Q_set (module doc, "Bandwidth") of every group's below and above set over
     the multipliers ``grid``, in vectorised numpy: fp64 (G, 2, B)."""
     grid = check_grid(grid)
-    return np.asarray([[_loo_set(models, hist, rows, grid, linear_forgetting, prior_weight,
-                                 cat_smoothing) for rows in sets]
+    return np.asarray([[_loo_set(models, hist, rows,
+                                 [bandwidths(models, rows.size, h) for h in grid],
+                                 linear_forgetting, prior_weight, cat_smoothing) for rows in sets]
                        for models, sets in loo_sets(domain, hist, gamma, tree)])
+
+
+def _loo_argmax(grid, Q_sets, sizes):
+    """The index ``loo_choice`` takes, or None where it falls back."""
+    with np.errstate(invalid="ignore"):
+        Q = np.asarray(Q_sets, np.float64).sum((0, 1))
+    fin = np.isfinite(Q)
+    if not (np.asarray(sizes) >= 2).any() or not fin.any():
+        return None
+    return int(np.argmax(np.where(fin, Q, -np.inf)))
 
 
 def loo_choice(grid, Q_sets, sizes):
@@ -996,12 +1052,115 @@ def loo_choice(grid, Q_sets, sizes):
     over the sets, the first grid value with the largest finite sum;
     ``BANDWIDTH`` where no set of ``sizes`` (the sets' n) reaches 2 or no sum
     is finite."""
-    with np.errstate(invalid="ignore"):
-        Q = np.asarray(Q_sets, np.float64).sum((0, 1))
-    fin = np.isfinite(Q)
-    if not (np.asarray(sizes) >= 2).any() or not fin.any():
-        return BANDWIDTH
-    return float(np.asarray(grid)[int(np.argmax(np.where(fin, Q, -np.inf)))])
+    b = _loo_argmax(grid, Q_sets, sizes)
+    return BANDWIDTH if b is None else float(np.asarray(grid)[b])
+
+
+# -- bandwidth per label (module doc, "Bandwidth per label") -----------------------
+def check_sweeps(sweeps):
+    """``sweeps`` as an int >= 0, else ValueError."""
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or sweeps < 0:
+        raise ValueError("sweeps=%r: an integer >= 0" % (sweeps,))
+    return int(sweeps)
+
+
+def check_bandwidth_map(bandwidth, labels=None):
+    """A mapping label -> multiplier as a dict of floats; ValueError on a key
+    that is not one of ``labels`` (None: not checked) and on a value that is
+    not a finite number > 0."""
+    out = {}
+    for lab, h in bandwidth.items():
+        if labels is not None and lab not in labels:
+            raise ValueError("bandwidth: %r is not a label of the space" % (lab,))
+        try:
+            h = float(h)
+        except (TypeError, ValueError):
+            raise ValueError("bandwidth[%r]=%r: a finite number > 0" % (lab, h))
+        if not (h > 0.0 and math.isfinite(h)):
+            raise ValueError("bandwidth[%r]=%r: a finite number > 0" % (lab, h))
+        out[lab] = h
+    return out
+
+
+def bandwidth_key(bandwidth):
+    """``bandwidth`` as it enters a comparison or a key: a mapping as the sorted
+    tuple of its items, anything else as it is."""
+    return tuple(sorted(bandwidth.items())) if isinstance(bandwidth, Mapping) else bandwidth
+
+
+def banded_labels(sets):
+    """The labels with a bandwidth (continuous or quantized) of ``loo_sets``'s
+    groups, in the order the sweeps visit them: [(group index, label index in
+    the group, label)]."""
+    return [(g, d, m.label) for g, (models, _pair) in enumerate(sets)
+            for d, m in enumerate(models) if m.kind != _L.JOINT_CAT]
+
+
+def loo_label_numpy(domain, hist, mult, label, grid=None, tree=False, prior_weight=1.0,
+                    gamma=0.25, linear_forgetting=25, cat_smoothing=CAT_SMOOTHING):
+    """Q_set,d (module doc, "Bandwidth per label") of the below and the above
+    set of ``label``'s group, ``label`` over ``grid`` and every other label at
+    its multiplier of the mapping ``mult``: fp64 (2, B)."""
+    grid = check_grid(grid)
+    sets = loo_sets(domain, hist, gamma, tree)
+    where = [(g, d) for g, d, lab in banded_labels(sets) if lab == label]
+    if not where:
+        raise ValueError("%r is not a label with a bandwidth of the joint criterion" % (label,))
+    (g, d), out = where[0], []
+    models, pair = sets[g]
+    for rows in pair:
+        sig = np.tile(bandwidths(models, rows.size, mult), (grid.size, 1))
+        sig[:, d] = [bandwidths(models, rows.size, h)[d] for h in grid]
+        out.append(_loo_set(models, hist, rows, sig, linear_forgetting, prior_weight,
+                            cat_smoothing))
+    return np.asarray(out)
+
+
+def loo_label_choice(grid, Q_sets, sizes, labels, curve, sweeps=2):
+    """The multipliers of module doc "Bandwidth per label": (mapping, visited).
+    ``Q_sets`` / ``sizes``: the scalar curves and set sizes ``loo_choice``
+    takes, for the start; ``labels``: the labels with a bandwidth in visiting
+    order; ``curve(mult, label)`` -> (2, B), Q_set,d of the label's below and
+    above set under the mapping ``mult``; ``visited``: [(label, curve)] in the
+    order the run asked for them."""
+    grid, sweeps = np.asarray(grid, np.float64), check_sweeps(sweeps)
+    start = _loo_argmax(grid, Q_sets, sizes)
+    if start is None:
+        return {lab: BANDWIDTH for lab in labels}, []
+    at = {lab: start for lab in labels}
+    mult = {lab: float(grid[start]) for lab in labels}
+    visited = []
+    for _sweep in range(sweeps):
+        moved = False
+        for lab in labels:
+            Q2 = np.asarray(curve(dict(mult), lab), np.float64)
+            visited.append((lab, Q2))
+            with np.errstate(invalid="ignore"):
+                Q = Q2.sum(0)
+            fin = np.isfinite(Q)
+            if not fin.any():
+                continue
+            best = int(np.argmax(np.where(fin, Q, -np.inf)))
+            if Q[best] > Q[at[lab]]:  # (strictly: a tie keeps the value)
+                at[lab], mult[lab], moved = best, float(grid[best]), True
+        if not moved:
+            break
+    return mult, visited
+
+
+def loo_label_fit_numpy(domain, hist, grid=None, tree=False, sweeps=2, prior_weight=1.0,
+                        gamma=0.25, linear_forgetting=25, cat_smoothing=CAT_SMOOTHING):
+    """``loo_label_choice`` over ``loo_numpy`` and ``loo_label_numpy``:
+    (mapping, visited)."""
+    grid = check_grid(grid)
+    kw = dict(prior_weight=prior_weight, gamma=gamma, linear_forgetting=linear_forgetting,
+              cat_smoothing=cat_smoothing)
+    sets = loo_sets(domain, hist, gamma, tree)
+    sizes = [[rows.size for rows in pair] for _m, pair in sets]
+    return loo_label_choice(
+        grid, loo_numpy(domain, hist, grid, tree, **kw), sizes,
+        [lab for _g, _d, lab in banded_labels(sets)],
+        lambda mult, lab: loo_label_numpy(domain, hist, mult, lab, grid, tree, **kw), sweeps)
 
 
 # -- device path -----------------------------------------------------------------
@@ -1297,6 +1456,85 @@ def loo_device(eng, domain, hist, seen, gamma, n_cols, grid=None, prior_weight=1
                 grid.ctypes.data, grid.size, out[g, which].data_ptr(), scratch.data_ptr(), sp),
                 "tpe_joint_loo")
     return out.cpu().numpy()
+
+
+def loo_label_curves(eng, domain, hist, seen, gamma, n_cols, grid=None, prior_weight=1.0,
+                     linear_forgetting=25, cat_smoothing=CAT_SMOOTHING, tree=False):
+    """``loo_label_numpy`` on the device, as the function ``curve(mult, label)``
+    -> (2, B) numpy: two tpe_joint_loo_label calls (the label's group's below
+    and above set; a set with n < 2 is 0 without a launch) and one readback.
+    A group's label records, row lists, weights and scratch go up at the first
+    call for one of its labels and serve every later one."""
+    t, lib = eng.torch, eng.lib
+    grid = np.ascontiguousarray(check_grid(grid))
+    sets = loo_sets(domain, hist, gamma, tree)
+    _alive, sv, sa, sld, srows, _n = seen
+    view = hist.rows if srows is not None else None  # (positions -> rows of the mirror)
+    sp = stream_ptr(eng)
+    out = t.zeros((2, grid.size), dtype=t.float64, device=eng.device)
+    where = {lab: (g, d) for g, d, lab in banded_labels(sets)}
+    groups = {}
+
+    def group(g):
+        """Group g on the device: (label records, per set None or (rows, v, sum v,
+        scratch, n))."""
+        if g not in groups:
+            models, pair = sets[g]
+            dj = _device_labels(eng, models, cat_smoothing)
+            n_quant = sum(m.kind == _L.JOINT_QUANT for m in models)
+            up = []
+            for rows in pair:
+                n = int(rows.size)
+                if n < 2:
+                    up.append(None)
+                    continue
+                if view is not None:
+                    rows = np.asarray(view)[rows]
+                v = forgetting_weights(n, linear_forgetting)
+                need = lib.tpe_joint_loo_label_scratch_bytes(len(models), n_quant, n, grid.size)
+                up.append((t.from_numpy(np.ascontiguousarray(rows, np.int32)).to(eng.device),
+                           t.from_numpy(np.ascontiguousarray(v)).to(eng.device), float(v.sum()),
+                           t.empty(need, dtype=t.uint8, device=eng.device), n))
+            groups[g] = (dj, up)
+        return groups[g]
+
+    def curve(mult, label):
+        if label not in where:
+            raise ValueError("%r is not a label with a bandwidth of the joint criterion"
+                             % (label,))
+        g, d = where[label]
+        dj, up = group(g)
+        h = np.asarray([mult.get(m.label, BANDWIDTH) for m in dj.models], np.float64)
+        out.zero_()
+        for which, one in enumerate(up):
+            if one is None:  # (Q_set = 0: ``out`` holds it)
+                continue
+            drows, dv, sum_v, scratch, n = one
+            _L.check(lib.tpe_joint_loo_label(
+                dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
+                None if dj.tables is None else dj.tables.data_ptr(), dj.n_tables, sv, sa, sld,
+                n_cols, drows.data_ptr(), n, dv.data_ptr(), sum_v, float(prior_weight),
+                h.ctypes.data, d, grid.ctypes.data, grid.size, out[which].data_ptr(),
+                scratch.data_ptr(), sp), "tpe_joint_loo_label")
+        return out.cpu().numpy()  # (the scratch is free for the next call after it)
+
+    return curve
+
+
+def loo_label_device(eng, domain, hist, seen, gamma, n_cols, grid=None, prior_weight=1.0,
+                     linear_forgetting=25, cat_smoothing=CAT_SMOOTHING, tree=False, sweeps=2):
+    """``loo_label_fit_numpy`` on the device: (mapping, visited).  The start is
+    ``loo_device``'s scalar choice; then per visited label the (2, B) curves of
+    ``loo_label_curves`` -- the choice is made on the host and steers the next
+    call."""
+    grid, sweeps = check_grid(grid), check_sweeps(sweeps)
+    sets = loo_sets(domain, hist, gamma, tree)
+    args = (eng, domain, hist, seen, gamma, n_cols, grid, prior_weight, linear_forgetting,
+            cat_smoothing, tree)
+    sizes = [[rows.size for rows in pair] for _m, pair in sets]
+    return loo_label_choice(grid, loo_device(*args), sizes,
+                            [lab for _g, _d, lab in banded_labels(sets)],
+                            loo_label_curves(*args), sweeps)
 
 
 # -- groups on the device (module doc, "Groups") ---------------------------------

@@ -73,6 +73,7 @@ from __future__ import annotations
 import logging
 import math
 import time
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -359,7 +360,8 @@ class Pool(object):
         column, for the seed -- the draw is a proposal from the groups' own
         mixtures -- and the pool is born with ``score_configs(joint="chain")``
         of them (joint.py, "Chains")."""
-        st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
+        st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing,
+                       domain=domain)
         return _sample(domain, trials, seed, n_rows, st, keep_terms)
 
     def _setup(self, domain, labels, vals, active):
@@ -1016,7 +1018,7 @@ def _grid_settings(st, pool):
     (GRID_CHAIN); no-op for any other pool."""
     if st.joint is None or not isinstance(pool, GridPool):
         return
-    if st.joint["bandwidth"] == "loo":
+    if st.joint["bandwidth"] in ("loo", "loo-label"):
         raise ValueError(_J.LOO_GRID_POOL)
     if not pool.joint:
         raise ValueError(GRID_JOINT)
@@ -1133,8 +1135,12 @@ def _score_grid_joint(domain, trials, pool, st, want_terms, hist, want_parts):
 
 def _fit(eng, domain, hist, n_cols, st, tree=None):
     """``joint.fit`` of the history under the settings ``st`` (``tree``: in
-    place of the settings' own).  ``bandwidth="loo"`` is resolved here, once:
-    the settings hold the float afterwards."""
+    place of the settings' own).  ``bandwidth="loo"`` / ``"loo-label"`` is
+    resolved here, once: the settings hold the float / the mapping afterwards."""
+    if st.joint["bandwidth"] == "loo-label":
+        st.joint["bandwidth"] = _J.loo_label_device(
+            eng, domain, hist, _seen_rows(eng, hist), st.gamma, n_cols, None, st.prior_weight,
+            st.lf, st.joint["cat_smoothing"], st.joint["tree"])[0]
     if st.joint["bandwidth"] == "loo":
         st.joint["bandwidth"] = _loo_bandwidth(eng, domain, hist, n_cols, None, st.prior_weight,
                                                st.gamma, st.lf, st.joint["cat_smoothing"],
@@ -1363,12 +1369,14 @@ def _topk_device(eng, d, P, k, taken=None):
     return d.rows_out[:n].cpu().numpy()
 
 
-def _joint_kw(joint, bandwidth, cat_smoothing):
+def _joint_kw(joint, bandwidth, cat_smoothing, domain=None):
     """``_Settings.joint``: None, or the criterion's keywords
     (``tree``: True where the string ``"tree"`` was given -- one mixture per
     group of labels, joint.py "Groups" -- and ``"chain"`` where that string
     was: the groups conditioned on their contexts, joint.py "Chains"; any other
-    truthy value is ``joint=True``, ``tree`` False)."""
+    truthy value is ``joint=True``, ``tree`` False).  ``bandwidth``: a number,
+    ``"loo"`` / ``"loo-label"``, or a mapping label -> number whose keys are
+    labels of ``domain`` (joint.py, "Bandwidth per label")."""
     if isinstance(joint, str) and joint == "tree":
         tree = True
     elif isinstance(joint, str) and joint == "chain":
@@ -1378,15 +1386,22 @@ def _joint_kw(joint, bandwidth, cat_smoothing):
     else:
         tree = False
     if isinstance(bandwidth, str):
-        # "loo": the multiplier is fitted where the fit is made (``_fit``), and
-        # the float takes this entry's place from there on
-        if bandwidth != "loo":
-            raise ValueError("bandwidth=%r: a number > 0, or 'loo'" % (bandwidth,))
+        # "loo" / "loo-label": the multiplier (the mapping) is fitted where the fit
+        # is made (``_fit``), and takes this entry's place from there on
+        if bandwidth not in ("loo", "loo-label"):
+            raise ValueError("bandwidth=%r: a number > 0, a mapping label -> number > 0, "
+                             "'loo-label' or 'loo'" % (bandwidth,))
         if tree == "chain":
             raise ValueError(_J.LOO_CHAIN)
         if not cat_smoothing >= 0.0:
             raise ValueError("cat_smoothing=%r must be >= 0" % (cat_smoothing,))
-        return dict(bandwidth="loo", cat_smoothing=float(cat_smoothing), tree=tree)
+        return dict(bandwidth=bandwidth, cat_smoothing=float(cat_smoothing), tree=tree)
+    if isinstance(bandwidth, Mapping):
+        if not cat_smoothing >= 0.0:
+            raise ValueError("cat_smoothing=%r must be >= 0" % (cat_smoothing,))
+        labels = None if domain is None else list(as_domain(domain).params)
+        return dict(bandwidth=_J.check_bandwidth_map(bandwidth, labels),
+                    cat_smoothing=float(cat_smoothing), tree=tree)
     if not bandwidth > 0.0 or not cat_smoothing >= 0.0:
         raise ValueError("bandwidth=%r must be > 0, cat_smoothing=%r >= 0"
                          % (bandwidth, cat_smoothing))
@@ -1425,14 +1440,15 @@ class _Settings(object):
 
 def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
               cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, pool=None,
-              refine=None):
+              refine=None, domain=None):
     """The ``_Settings`` of a public call's keywords, after the checks:
     ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
     ``"liar"``, on a ``lie_weight`` that is not a finite number > 0, and on
     what the batch is not built for (joint.py, "Not built"; ``pool``: the
-    call's pool, where it has one).  A ``refine`` that is not None: ValueError
+    call's pool, where it has one; ``domain``: the call's space, for the keys of
+    a ``bandwidth`` mapping).  A ``refine`` that is not None: ValueError
     unless it is an integer >= 0 and ``joint`` is ``True``."""
-    st = _Settings(prior_weight, gamma, lf, _joint_kw(joint, bandwidth, cat_smoothing))
+    st = _Settings(prior_weight, gamma, lf, _joint_kw(joint, bandwidth, cat_smoothing, domain))
     if refine is not None:
         st.refine = _J.check_refine(refine)
         if st.joint is None or st.joint["tree"]:
@@ -1499,7 +1515,7 @@ def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_
     from . import tpe as T
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing, "liar",
-                   lie_weight, pool)
+                   lie_weight, pool, domain=domain)
     _same_space(domain, pool)
     hist = T.collect_history(trials, pool.labels)
     eng, d = _score_device(domain, trials, pool, st, False, hist=hist)
@@ -1560,11 +1576,16 @@ def score_configs(domain, trials, pool, prior_weight=1.0, gamma=0.25, linear_for
     ``bandwidth="loo"`` (here and wherever ``bandwidth=`` is taken, with
     ``joint=True`` or ``"tree"``): the multiplier ``joint_bandwidth`` returns
     for these trials, fitted once per call (joint.py, "Bandwidth").
-    ``joint="chain"`` and a ``GridPool`` raise ValueError.
+    ``bandwidth="loo-label"``: likewise the mapping ``joint_bandwidths`` returns
+    (joint.py, "Bandwidth per label").  For both, ``joint="chain"`` and a
+    ``GridPool`` raise ValueError.  ``bandwidth=`` a mapping label -> multiplier
+    is taken wherever a float is (a label it does not name: ``joint.BANDWIDTH``;
+    a key that is not a label of the space: ValueError).
 
     Any other truthy ``joint`` is ``joint=True``."""
     domain = as_domain(domain)
-    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing)
+    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing,
+                   domain=domain)
     grid, tree = isinstance(pool, GridPool), st.joint is not None and st.joint["tree"]
     _grid_settings(st, pool)
     P = len(pool)
@@ -1660,7 +1681,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
-                   lie_weight, pool)
+                   lie_weight, pool, domain=domain)
     _grid_settings(st, pool)
     t0 = time.time()
     domain = as_domain(domain)
@@ -1768,7 +1789,7 @@ def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weigh
     from . import tpe as T
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing,
-                   refine=0 if refine is None else refine)
+                   refine=0 if refine is None else refine, domain=domain)
     labels = list(domain.params)
     models = _J.label_models(domain)
     cont = _J.moving_labels(models)
@@ -1824,6 +1845,33 @@ def joint_bandwidth(domain, trials, grid=None, joint=True, prior_weight=1.0, gam
     out = _loo_bandwidth(T.engine(), domain, hist, len(labels), grid, prior_weight, gamma,
                          linear_forgetting, jkw["cat_smoothing"], jkw["tree"])
     return out if return_curves else out[0]
+
+
+def joint_bandwidths(domain, trials, grid=None, joint=True, sweeps=2, prior_weight=1.0, gamma=0.25,
+                     linear_forgetting=25, cat_smoothing=_J.CAT_SMOOTHING, return_curves=False):
+    """One bandwidth multiplier per label with a bandwidth, {label: float of
+    ``grid``}: from ``joint_bandwidth``'s value every label climbs the
+    leave-one-out log-likelihood along its own multiplier, the others held, for
+    at most ``sweeps`` passes (joint.py, "Bandwidth per label"); what
+    ``bandwidth="loo-label"`` passes on, and what ``bandwidth=`` takes wherever
+    it takes a float.  ``return_curves``: (mapping, grid, visited) -- visited
+    the [(label, (2, B) curves of its below and above set)] of the run.
+
+    ValueError: as ``joint_bandwidth``, and ``sweeps`` not an integer >= 0."""
+    from . import tpe as T
+    domain = as_domain(domain)
+    grid, sweeps = _J.check_grid(grid), _J.check_sweeps(sweeps)
+    jkw = _joint_kw(joint, "loo-label", cat_smoothing)
+    if jkw is None:
+        raise ValueError("joint_bandwidths: joint=True or joint='tree'")
+    _joint_cols(domain, jkw)
+    labels = list(domain.params)
+    hist = T.collect_history(trials, labels)
+    eng = T.engine()
+    mult, visited = _J.loo_label_device(eng, domain, hist, _seen_rows(eng, hist), gamma,
+                                        len(labels), grid, prior_weight, linear_forgetting,
+                                        jkw["cat_smoothing"], jkw["tree"], sweeps)
+    return (mult, grid, visited) if return_curves else mult
 
 
 def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=None,
@@ -1908,7 +1956,7 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
                          "joint=True")
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
-                   lie_weight, refine=refine)
+                   lie_weight, refine=refine, domain=domain)
     if st.joint is not None:
         _joint_cols(domain, st.joint)  # (ValueError on a space without a joint label)
     if st.refine:  # (ValueError over the kernel's limit of continuous labels)

@@ -52,7 +52,10 @@ criterion on their continuous labels, on the device (``refine_configs``: any
 rows; ``joint_refine_numpy``).  ``bandwidth="loo"`` (with ``joint=True`` /
 ``"tree"``) fits the joint mixtures' bandwidth multiplier by leave-one-out
 likelihood on the device, once per call (``joint_bandwidth``: the float and its
-curves; ``joint_loo_numpy``).
+curves; ``joint_loo_numpy``); ``bandwidth="loo-label"`` one multiplier per
+label, each climbing the same likelihood along its own coordinate
+(``joint_bandwidths``: the mapping, which ``bandwidth=`` also takes;
+``joint_loo_label_numpy``).
 """
 from __future__ import annotations
 
@@ -806,9 +809,10 @@ def _suggest_many(requests, shard_studies=False):
 
 # a fixed pool of configurations ranked by the same posteriors (hyperopt_amd/pool.py)
 from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan,  # noqa: E402,F401
-                   joint_bandwidth, pick_batch, refine_configs, score_configs, suggest_from_pool, suggest_sampled)
+                   joint_bandwidth, joint_bandwidths, pick_batch, refine_configs, score_configs, suggest_from_pool, suggest_sampled)
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_contexts,
                     joint_groups, joint_labels, liar_numpy as joint_liar_numpy,
-                    loo_numpy as joint_loo_numpy,
+                    loo_label_fit_numpy as joint_loo_label_fit_numpy,
+                    loo_label_numpy as joint_loo_label_numpy, loo_numpy as joint_loo_numpy,
                     refine_numpy as joint_refine_numpy, score_numpy as joint_score_numpy)

@@ -1198,6 +1198,35 @@ int tpe_joint_loo(const tpe_joint_label* host_labels, const tpe_joint_label* lab
 /* host: TPE_LOO_MAX_GRID as the library was built */
 int tpe_joint_loo_max_grid(void);
 
+/* ---- the same likelihood along one label's multiplier -----------------------------
+ * (tpe.joint_bandwidths, bandwidth="loo-label"; hyperopt_amd/joint.py, "Bandwidth
+ * per label".)  The set, v, sum_v, prior_weight, a_ij, LOO_i and out as
+ * tpe_joint_loo; the trial components' bandwidths are
+ *   sigma_e    = mult[e] prior_sigma_e n^(-1 / (n_labels + 4))     e != which
+ *   sigma_d(b) = grid[b] prior_sigma_d n^(-1 / (n_labels + 4))     d  = which
+ * with mult (host, n_labels doubles: finite, > 0; the entries of discrete labels
+ * and of `which` are not read) and which the index of a TPE_JOINT_CONT or
+ * TPE_JOINT_QUANT label (a discrete one: TPE_E_ARG).  out[b] (device, n_grid
+ * doubles) is Q_set with label `which` at grid[b]; n < 2: 0.  One call walks every
+ * pair (i, j) once for all n_grid values: what the other labels contribute is
+ * formed once per pair from coordinates pre-scaled by their own sigma, label
+ * `which` adds one fma per grid value (continuous) or one mass (quantized).
+ * Partials per (grid value, component chunk of TPE_JOINT_CHUNK, row), the prior
+ * component's after the last chunk, in `scratch`
+ * (tpe_joint_loo_label_scratch_bytes(n_labels, n_quant, n, n_grid) bytes; -1: bad
+ * arguments; 16-byte aligned); merged in chunk order with the prior last, the
+ * rows by a block tree and the blocks in block order: no atomics, the result is a
+ * function of the inputs alone.  Limits, errors and asynchrony as tpe_joint_loo;
+ * no allocation. */
+int64_t tpe_joint_loo_label_scratch_bytes(int n_labels, int n_quant, int64_t n, int n_grid);
+int tpe_joint_loo_label(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                        int n_labels, const double* tables, int64_t n_tables,
+                        const double* hist_vals, const uint8_t* hist_active, int64_t hist_ld,
+                        int hist_cols, const int32_t* rows, int64_t n, const double* v,
+                        double sum_v, double prior_weight, const double* mult, int which,
+                        const double* grid, int n_grid, double* out, void* scratch,
+                        void* stream);
+
 /* ---- argmax combine: n_sets tpe_best arrays of n_labels each (e.g. one per
  * rank after an all-gather) -> n_labels winners, same tie rules. ------------ */
 int tpe_best_combine(const tpe_best* sets, int n_sets, int n_labels, tpe_best* out,
