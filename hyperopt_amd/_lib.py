@@ -204,6 +204,11 @@ _SIGNATURES = {
     "tpe_joint_lie_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _I64, _P, _P,
                                  ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P, _P, _P, _P,
                                  _P, _P]),
+    "tpe_joint_lie_tree_scratch_bytes": (_I64, [_I64, _I]),
+    "tpe_joint_lie_tree_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _P, _I, _P, _P, _P, _I64, _I,
+                                      _I64, _P, _P, _I64, ctypes.c_double, _P, _P, _I64, _P, _P,
+                                      _P, _P, _P, _P]),
+    "tpe_rows_scatter": (_I, [_P, _P, _P, _I64, _I64, _P, _I64, _P]),
     "tpe_joint_refine": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I,
                               _P, _P, _P, _P, _P]),
     "tpe_joint_refine_max_cont": (_I, []),

@@ -18,7 +18,8 @@
 //                 block's best untaken row of S_0
 //   k_lie_final   one block: the best of the blocks' bests is pick j -- its row
 //                 to out_rows[j] and to the control word the next update reads,
-//                 its byte of the working mask set
+//                 its byte of the working mask set (tpe_joint_lie.hpp, shared
+//                 with tpe_joint_lie_tree.hip)
 //   k_lie_update  the first D threads of each block build the pick's {mu,
 //                 constant} pairs in LDS; a thread per row adds the factors,
 //                 updates U, writes S_j and the block's best untaken row
@@ -28,39 +29,10 @@
 // NaN before everything, equal scores to the smaller row.  The minimum of such
 // pairs is exact in any order, a thread owns its row alone, there are no
 // atomics: a row's bits depend on the row, the set and the pick sequence only.
-#include "tpe_joint.hpp"
+#include "tpe_joint_lie.hpp"
 
 namespace tpe {
 namespace {
-struct LieCtl {
-  int64_t cur;  // the row of the last pick; -1: none was left
-  int64_t pad_;
-};
-
-struct LieBest {
-  uint64_t key;
-  int64_t row;  // -1: no row
-};
-
-__device__ __forceinline__ uint64_t lie_key(double v) { return ~order_key(v); }
-
-// a precedes b in (key, row) order; a missing row precedes nothing
-__device__ __forceinline__ bool lie_before(const LieBest& a, const LieBest& b) {
-  return a.row >= 0 && (b.row < 0 || a.key < b.key || (a.key == b.key && a.row < b.row));
-}
-
-// the block's first entry in (key, row) order, in thread 0
-__device__ __forceinline__ LieBest lie_block_best(LieBest mine, LieBest* sb) {
-  sb[threadIdx.x] = mine;
-  __syncthreads();
-  for (int off = kJBS / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off && lie_before(sb[threadIdx.x + off], sb[threadIdx.x]))
-      sb[threadIdx.x] = sb[threadIdx.x + off];
-    __syncthreads();
-  }
-  return sb[0];
-}
-
 __global__ __launch_bounds__(kJBS) void k_lie_init(const double* __restrict__ S0,
                                                    const double* __restrict__ A0, double log_w,
                                                    const uint8_t* __restrict__ taken,
@@ -89,34 +61,6 @@ __global__ __launch_bounds__(kJBS) void k_lie_init(const double* __restrict__ S0
     if (blockIdx.x == 0) {
       ctl->cur = -1;
       *out_count = 0;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kJBS) void k_lie_final(const LieBest* __restrict__ partial,
-                                                    int64_t n_blocks, int64_t j,
-                                                    const double* __restrict__ Sw,
-                                                    uint8_t* __restrict__ mask,
-                                                    LieCtl* __restrict__ ctl,
-                                                    int64_t* __restrict__ out_rows,
-                                                    int64_t* __restrict__ out_count,
-                                                    double* __restrict__ S_at_pick) {
-  __shared__ LieBest sb[kJBS];
-  // (no row was left for the pick before: the partials are the ones that said so)
-  if (j > 0 && ctl->cur < 0) return;
-  LieBest mine{0, -1};
-  for (int64_t b = threadIdx.x; b < n_blocks; b += kJBS) {
-    const LieBest p = partial[b];
-    if (lie_before(p, mine)) mine = p;
-  }
-  const LieBest best = lie_block_best(mine, sb);
-  if (threadIdx.x == 0) {
-    ctl->cur = best.row;
-    if (best.row >= 0) {
-      out_rows[j] = best.row;
-      if (S_at_pick) S_at_pick[j] = Sw[best.row];
-      mask[best.row] = 1;
-      *out_count = j + 1;
     }
   }
 }
@@ -223,7 +167,6 @@ inline LieLayout lie_layout(int64_t n_rows) {
   p.total = (p.mask + n_rows + 15) & ~(int64_t)15;
   return p;
 }
-static_assert(sizeof(LieBest) == 16 && sizeof(LieCtl) == 16, "the scratch stays 16-byte aligned");
 }  // namespace
 }  // namespace tpe
 

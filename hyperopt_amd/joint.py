@@ -177,8 +177,9 @@ product kernels, so that is one more component: O(P D) per pick.
                one is given.  The run stops when no row is left.  k = 1 is the
                plain result, bit for bit.
 
-On a conditional space the lie acts through the always-live labels only: two
-rows that differ under a ``switch`` alone get the same penalty.
+The lie of ``batch="liar"`` acts through the always-live labels; on a
+conditional space ``batch="liar-tree"`` ("Batches in a tree", below) lies inside
+the branches as well.
 ``liar_numpy`` is this definition in numpy; ``liar_device`` enqueues all k
 picks in one call (a pick's row is read on the device) and reads back the rows.
 
@@ -343,14 +344,55 @@ two tpe_joint_loo_label calls (below set, above set) and one readback of the B
 values: the choice is made on the host and steers the next call.
 ``bandwidth="loo-label"`` is resolved where ``"loo"`` is, into the mapping.
 
+Batches in a tree (``joint="tree"``, ``batch="liar-tree"``,
+csrc/tpe_joint_lie_tree.hip).  Under ``joint="tree"`` every group
+has an above mixture of its own, so a pick joins each one it is live in: two
+rows equal at the root and different under a ``switch`` get different
+penalties.  Groups g = 0 .. G - 1 are those of ``joint_groups(domain)``; the
+root, g = 0, is live in every row, group g > 0 where the ``active`` byte of its
+first label is set (the rule ``score_tree_device`` compacts on).
+
+  inputs       ``S_0[r]``, the ``joint="tree"`` score, bits unchanged; ``A_g[r]
+               = log L_above,g(r)`` for every (g, r) with g live in r -- the
+               value the tree scoring subtracts for that row, read nowhere else.
+               Per group: n_g the size of its prepared above set, ``sig_g =
+               lie_sigma(models_g, n_g, bandwidth)``, ``log W_g =
+               lie_log_total(n_g, lf, prior_weight)``.
+  lie          pick p lies in every group g live in row p: ``c_{g,p}(r) =
+               log(lie_weight) + sum_{d in g} log k_d(r_d)``, sequentially over
+               g's labels in list order from ``log(lie_weight)``; ``log k_d`` is
+               the "Factors" entry of a trial component of g's above set whose
+               observation is row p's stored value, with ``sig_g`` -- the
+               expressions of "Batches".  Defined for the rows in which g is live.
+  update       ``U_{g,0}[r] = log W_g + A_g[r]``.  After pick j, for every g live
+               in both p_j and r, ``U_{g,j}[r]`` is the join of ``U_{g,j-1}[r]``
+               and ``c_{g,p_j}(r)`` by the "Batches" rule (U's term first; m =
+               -inf gives -inf; c = -inf leaves U's bits).  Every other (g, r)
+               keeps ``U_{g,j-1}[r]``.
+  score        s = ``S_0[r]``; then, in group order over the groups live in r,
+               ``s = s - (U_{g,j}[r] - U_{g,0}[r])`` where ``U_{g,0}[r]`` is
+               finite.  A group no pick has touched subtracts exactly 0.0; a NaN
+               ``S_0`` stays NaN.
+  picks        the order, the masks, ``distinct`` and the stop of "Batches".  k =
+               1 is the plain first row of the tree S, bit for bit; on a flat
+               space (G = 1) the rows, ``S_at_pick`` and ``S_k`` have the bits of
+               ``batch="liar"`` with ``joint=True``.
+
+``liar_tree_numpy`` is this definition in numpy.  ``score_tree_device(above=)``
+keeps A_g while it scores (row 0 is the root's subtrahend itself; a group's
+dense temporary is copied to its rows by tpe_rows_scatter: the above set is not
+scored twice and the list's length stays on the device), and
+``liar_tree_device`` enqueues all k picks in one tpe_joint_lie_tree_picks.
+
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
 on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
-the context's as well).  ``batch="liar"`` under ``joint="tree"`` and
-``joint="chain"`` (it needs log L_above per group, which ``score_tree_device``
-does not keep), on a ``GridPool`` (a grid has no row values to lie with) and
-under the factorised criterion (its adaptive bandwidths depend on the sorted
-neighbours: no component can be added without a refit).  ``refine`` under
+the context's as well).  A batch under ``joint="chain"`` (C_g is a ratio: a lie
+would have to join numerator and denominator; ``batch="liar"`` itself keeps
+``joint=True``, and ``batch="liar-tree"`` ``joint="tree"``), on a ``GridPool`` (a
+grid has no row values to lie with) and under the factorised criterion (its
+adaptive bandwidths depend on the sorted neighbours: no component can be added
+without a refit).  ``refine`` under
 ``joint="tree"`` / ``"chain"`` (a group's labels move only where it is live).
 ``bandwidth="loo"`` / ``"loo-label"`` under ``joint="chain"`` (its fits are over
 ctx + g and enter as a ratio: the likelihood of a set under its own fit is not
@@ -816,6 +858,67 @@ def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0,
     return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
 
 
+def liar_tree_numpy(domain, hist, vals, k, active=None, taken=None, distinct=None,
+                    lie_weight=1.0, S0=None, A=None, prior_weight=1.0, gamma=0.25,
+                    linear_forgetting=25, bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING):
+    """The batch of module doc "Batches in a tree" in numpy: (rows, S_at_pick,
+    S_k) as ``liar_numpy`` returns them.  ``vals`` / ``active``: (P, L) stored
+    values and activity as a ``Pool`` holds them (``active`` None: where
+    ``vals`` is not NaN).  ``S0`` (P,) / ``A`` (P, G; read where the group is
+    live): the tree score and the groups' log L_above to start from where the
+    caller has them; else ``score_numpy(tree=True)``'s."""
+    domain = as_domain(domain)
+    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
+        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
+    groups = joint_groups(domain)
+    vals = np.asarray(vals, np.float64)
+    active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
+    P, G = vals.shape[0], len(groups)
+    if S0 is None or A is None:
+        S, _J, _below, above = score_numpy(domain, hist, vals, active, prior_weight, gamma,
+                                           linear_forgetting, bandwidth, cat_smoothing,
+                                           return_parts=True, tree=True)
+        S0 = S if S0 is None else S0
+        A = above if A is None else A
+    S0, A = np.asarray(S0, np.float64), np.asarray(A, np.float64).reshape(P, G)
+    isa = split_sets(hist, gamma)[1]
+    per, U0 = [], np.full((P, G), np.nan)
+    for g, grp in enumerate(groups):
+        models = label_models(domain, grp.labels)
+        cols = [m.col for m in models]
+        live = np.flatnonzero(active[:, cols[0]]) if g else np.arange(P)
+        n = int(set_rows(hist, isa, cols).size)
+        per.append((models, live, vals[live][:, cols], lie_sigma(models, n, bandwidth)))
+        U0[live, g] = lie_log_total(n, linear_forgetting, prior_weight) + A[live, g]
+    gone = np.zeros(P, bool)
+    for mask in (taken, distinct):
+        if mask is not None:
+            gone |= np.asarray(mask)[:P] != 0
+    U, S = U0.copy(), S0.copy()
+    rows, at = [], []
+    for _ in range(min(max(int(k), 0), P)):
+        p = _first_row(S, gone)
+        if p < 0:
+            break
+        rows.append(p)
+        at.append(S[p])
+        gone[p] = True
+        S = S0.copy()
+        for g, (models, live, x, sig) in enumerate(per):
+            at_p = int(np.searchsorted(live, p))
+            with np.errstate(all="ignore"):
+                if at_p < live.size and live[at_p] == p:  # (g is live in the pick)
+                    c = _lie_component(models, x, at_p, sig, cat_smoothing, math.log(lie_weight))
+                    u = U[live, g]
+                    m = np.where(c > u, c, u)
+                    both = m + np.log(np.exp(u - m) + np.exp(c - m))
+                    U[live, g] = np.where(c == -np.inf, u,
+                                          np.where(m == -np.inf, -np.inf, both))
+                fin = live[np.isfinite(U0[live, g])]
+                S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
+    return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
+
+
 # -- refining (module doc, "Refining") -------------------------------------------
 REFINE_MIN_STEP = 2.0 ** -20
 REFINE_TOL = 1e-6  # the project's relative tolerance per log-density (``info``'s bounds)
@@ -1230,7 +1333,7 @@ class JointFit(object):
     (with ``tree="chain"`` the number of context labels that lead ``dj``'s
     list, before the group's own; else 0) and the settings it was made with."""
     __slots__ = ("eng", "dj", "sets", "sp", "group", "n_ctx", "prior_weight",
-                 "linear_forgetting", "bandwidth", "cat_smoothing")
+                 "linear_forgetting", "bandwidth", "cat_smoothing", "lie_pack")
 
 
 def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting, bandwidth,
@@ -1257,7 +1360,7 @@ def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting,
     contexts = joint_contexts(domain) if tree == "chain" else [[]] * len(groups)
     for group, ctx in zip(groups, contexts):
         f = JointFit()
-        f.eng, f.group, f.n_ctx = eng, group, len(ctx)
+        f.eng, f.group, f.n_ctx, f.lie_pack = eng, group, len(ctx), None
         f.prior_weight, f.linear_forgetting = prior_weight, linear_forgetting
         f.bandwidth, f.cat_smoothing = bandwidth, cat_smoothing
         models = label_models(domain, ctx + group if ctx else group)
@@ -1281,11 +1384,13 @@ def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting,
     return fits
 
 
-def score_device(fit, d_vals, ld, n_cols, P, out, parts=None):
+def score_device(fit, d_vals, ld, n_cols, P, out, parts=None, keep_above=None):
     """J of rows [0, P) of the label-major device pool ``d_vals`` (leading
     dimension ``ld``, ``n_cols`` columns) under ``fit`` into the device vector
     ``out``.  ``parts``: a device tensor whose rows 0 and 1 (>= P long) receive
-    log L_below and log L_above."""
+    log L_below and log L_above.  ``keep_above`` (without ``parts``): a device
+    vector (>= P doubles) that takes the temporary's place, so log L_above stays
+    -- the same calls."""
     eng, dj, sets, sp = fit.eng, fit.dj, fit.sets, fit.sp
     t, lib = eng.torch, eng.lib
     D = len(dj.models)
@@ -1293,7 +1398,9 @@ def score_device(fit, d_vals, ld, n_cols, P, out, parts=None):
     win = min(max(P, 1), ROWS_PER_CALL)
     need = max(lib.tpe_joint_scratch_bytes(win, n) for _, n, _ in sets)
     scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
-    above = t.empty(win, dtype=t.float64, device=eng.device) if parts is None else None
+    above = None
+    if parts is None and keep_above is None:
+        above = t.empty(win, dtype=t.float64, device=eng.device)
 
     def score(which, r0, k, sub, dst):
         dset, n, _ = sets[which]
@@ -1305,7 +1412,10 @@ def score_device(fit, d_vals, ld, n_cols, P, out, parts=None):
         k = min(win, P - r0)
         # above first: the below call subtracts it (with ``parts`` it lands in
         # row 1 and is the subtrahend from there)
-        la = above.data_ptr() if parts is None else parts[1].data_ptr() + 8 * r0
+        if parts is not None:
+            la = parts[1].data_ptr() + 8 * r0
+        else:
+            la = above.data_ptr() if keep_above is None else keep_above.data_ptr() + 8 * r0
         score(1, r0, k, None, la)
         if parts is not None:
             # log L_below by itself costs one more call: J keeps the bits of the
@@ -1382,6 +1492,91 @@ def liar_device(fit, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weig
         taken.data_ptr(), None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
         out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
         None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp), "tpe_joint_lie_picks")
+    got = out[:k + 1].cpu().numpy()
+    rows = got[:int(got[k])].copy()
+    if not trace:
+        return rows
+    return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
+
+
+class _LiePack(object):
+    """The groups of a tree fit as tpe_joint_lie_tree_picks takes them: the
+    label records concatenated in group order (``tab_off`` counted from the
+    start of the concatenated tables) on the host and on the device, the
+    tables, ``group_off``, log W_g, the liveness columns, and the sigmas."""
+    __slots__ = ("host", "dev", "tables", "n_tables", "off", "log_w", "col", "sigma")
+
+
+def _lie_pack(fits):
+    """``_LiePack`` of ``fits`` (``fit(..., tree=True)``), made once per fit
+    list and kept on its first fit."""
+    if fits[0].lie_pack is not None:
+        return fits[0].lie_pack
+    eng = fits[0].eng
+    t = eng.torch
+    recs, tabs, sig, off, base = [], [], [], [0], 0
+    for f in fits:
+        rec = f.dj.host.copy()
+        rec["tab_off"][rec["kind"] == _L.JOINT_CAT] += base
+        recs.append(rec)
+        if f.dj.tables is not None:
+            tabs.append(f.dj.tables)
+        base += f.dj.n_tables
+        off.append(off[-1] + len(f.dj.models))
+        sig.append(lie_sigma(f.dj.models, f.sets[1][1], f.bandwidth))
+    sig = np.concatenate(sig)
+    some = sig > 0.0
+    pk = _LiePack()
+    pk.host = np.concatenate(recs)
+    pk.dev = t.from_numpy(pk.host.view(np.uint8).copy()).to(eng.device)
+    pk.tables, pk.n_tables = (t.cat(tabs) if tabs else None), base
+    pk.off = np.asarray(off, np.int32)
+    pk.log_w = np.asarray([lie_log_total(f.sets[1][1], f.linear_forgetting, f.prior_weight)
+                           for f in fits], np.float64)
+    pk.col = np.asarray([-1] + [f.dj.models[0].col for f in fits[1:]], np.int32)
+    # (no label with a bandwidth: the call takes no sigmas)
+    pk.sigma = t.from_numpy(np.concatenate(
+        [sig, np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)])
+    ).to(eng.device) if some.any() else None
+    fits[0].lie_pack = pk
+    return pk
+
+
+def liar_tree_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, taken, distinct, k, lie_weight,
+                     trace=False, rows_out=None):
+    """The batch of module doc "Batches in a tree" for rows [0, P) of the
+    label-major device pool ``d_vals`` / ``d_active``: ``liar_device`` with
+    ``fits`` the tree fits (``fit(..., tree=True)``) and ``A`` the (G, >= P)
+    device tensor ``score_tree_device(above=)`` filled.  One
+    tpe_joint_lie_tree_picks, one readback.  ValueError past
+    ``TPE_COND_MAX_LABELS`` groups, or labels over all the groups."""
+    eng, sp = fits[0].eng, fits[0].sp
+    t, lib = eng.torch, eng.lib
+    k = min(int(k), P)
+    if k <= 0 or P == 0:
+        none = np.zeros(0, np.int64)
+        return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
+    G, D_tot = len(fits), sum(len(f.dj.models) for f in fits)
+    if G > _L.COND_MAX_LABELS or D_tot > _L.COND_MAX_LABELS:
+        raise ValueError("batch='liar-tree': %d groups of %d labels in all, at most %d of either"
+                         % (G, D_tot, _L.COND_MAX_LABELS))
+    pk = _lie_pack(fits)
+    out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
+    scratch = t.empty(lib.tpe_joint_lie_tree_scratch_bytes(P, G), dtype=t.uint8,
+                      device=eng.device)
+    at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
+    S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
+    _L.check(lib.tpe_joint_lie_tree_picks(
+        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host),
+        None if pk.tables is None else pk.tables.data_ptr(), pk.n_tables, pk.off.ctypes.data,
+        pk.log_w.ctypes.data, pk.col.ctypes.data, G,
+        None if pk.sigma is None else pk.sigma.data_ptr(), d_vals.data_ptr(),
+        d_active.data_ptr(), ld, n_cols, P, S0.data_ptr(), A.data_ptr(), A.shape[1],
+        math.log(lie_weight), taken.data_ptr(),
+        None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
+        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
+        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp),
+        "tpe_joint_lie_tree_picks")
     got = out[:k + 1].cpu().numpy()
     rows = got[:int(got[k])].copy()
     if not trace:
@@ -1547,7 +1742,7 @@ def sample_tree_device(fits, seed, d_vals, ld, n_cols, row_base, n_rows):
         sample_device(f, seed, d_vals, ld, n_cols, row_base, n_rows, comp_key=key)
 
 
-def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
+def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, above=None):
     """S of ``joint="tree"`` for rows [0, P) of the label-major device pool
     ``d_vals`` / ``d_active`` (bytes; leading dimension ``ld``) under ``fits``
     (``fit(..., tree=True)``) into the device vector ``out``.  The root group
@@ -1565,10 +1760,19 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
     a context (``n_ctx`` > 0) takes tpe_joint_chain_rows in the same loop --
     log L - log L_ctx of the above set into the temporary, the below set's
     minus it added -- so row g of ``parts`` receives C_g; the list is still
-    compacted on the group's first own label, not the context's."""
+    compacted on the group's first own label, not the context's.
+
+    ``above`` (``tree=True`` fits): a (G, >= P) device tensor that receives A_g
+    = log L_above,g at the rows in which group g is live (module doc, "Batches
+    in a tree"); its other places are not written.  Row 0 is the root's
+    subtrahend itself; a group's dense temporary goes to its rows by one
+    tpe_rows_scatter per window.  None: exactly the calls above."""
     eng = fits[0].eng
     t, lib = eng.torch, eng.lib
-    score_device(fits[0], d_vals, ld, n_cols, P, out)
+    if above is None:
+        score_device(fits[0], d_vals, ld, n_cols, P, out)
+    else:
+        score_device(fits[0], d_vals, ld, n_cols, P, out, keep_above=above[0])
     if parts is not None:
         parts[0, :P].copy_(out[:P])
     if len(fits) == 1 or P == 0:
@@ -1577,7 +1781,7 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
     need = max((lib.tpe_joint_chain_scratch_bytes if f.n_ctx else lib.tpe_joint_scratch_bytes)
                (win, n) for f in fits[1:] for _, n, _ in f.sets)
     scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
-    above = t.empty(win, dtype=t.float64, device=eng.device)
+    dense = t.empty(win, dtype=t.float64, device=eng.device)
     rows = t.empty(P, dtype=t.int64, device=eng.device)
     count = t.empty(1, dtype=t.int64, device=eng.device)
     cscratch = t.empty(lib.tpe_rows_compact_scratch_bytes(P), dtype=t.uint8, device=eng.device)
@@ -1604,10 +1808,14 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None):
                 _L.check(lib.tpe_joint_score_rows(*(head + tail)), "tpe_joint_score_rows")
 
         for p0 in range(0, P, win):
-            score(1, p0, None, above.data_ptr(), 0)
+            score(1, p0, None, dense.data_ptr(), 0)
+            if above is not None:
+                _L.check(lib.tpe_rows_scatter(dense.data_ptr(), rows.data_ptr(), count.data_ptr(),
+                                              p0, min(win, P - p0), above[g].data_ptr(),
+                                              above.shape[1], sp), "tpe_rows_scatter")
             if parts is not None:  # (the same call as the one added to S: the same bits)
-                score(0, p0, above.data_ptr(), parts[g].data_ptr(), _L.JOINT_OUT_SCATTER)
-            score(0, p0, above.data_ptr(), out.data_ptr(), both)
+                score(0, p0, dense.data_ptr(), parts[g].data_ptr(), _L.JOINT_OUT_SCATTER)
+            score(0, p0, dense.data_ptr(), out.data_ptr(), both)
 
 
 # -- a grid pool: factor tables per axis ---------------------------

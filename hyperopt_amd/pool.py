@@ -57,7 +57,7 @@ mixture (csrc/tpe_joint_sample.hip); ``joint="tree"``, accepted wherever
 one per group of labels that share an activation condition (joint.py
 "Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
 interaction between labels.  ``joint="chain"`` (not on a ``GridPool``, not with
-``batch="liar"``) conditions each of those groups on the labels live around it
+a ``batch``) conditions each of those groups on the labels live around it
 (joint.py "Chains"; csrc/tpe_joint_chain.hip), so a root label interacts with a
 branch label; its sampled pools draw the rows of ``"tree"``.
 
@@ -66,7 +66,10 @@ with ``joint=True`` on a ``Pool`` / ``SampledPool``) makes the k rows of one
 call see each other: the top-k of one score is replaced by k picks made one
 after the other on the device, each joining the above mixture as the pending
 trial it is about to become (joint.py "Batches"; csrc/tpe_joint_lie.hip).  The
-host still reads back the k rows only, once.
+host still reads back the k rows only, once.  ``batch="liar-tree"`` (with
+``joint="tree"``) is that batch on a conditional space: the tree scoring keeps
+log L_above per group, and a pick lies in every group it is live in (joint.py
+"Batches in a tree"; csrc/tpe_joint_lie_tree.hip).
 """
 from __future__ import annotations
 
@@ -256,7 +259,7 @@ class _DevicePool(object):
     them --, activity (L, P) bytes, the taken mask, and per label the
     (min, max) of its live values in the scoring coordinate."""
     __slots__ = ("vals", "active", "taken", "taken_current", "ranges", "S", "terms", "rows_out",
-                 "count", "scratch", "first", "mask", "distinct_scratch", "fits", "parts")
+                 "count", "scratch", "first", "mask", "distinct_scratch", "fits", "parts", "above")
 
     def __init__(self, vals, active, taken, taken_current, ranges, S, terms=None):
         self.vals, self.active, self.ranges, self.S, self.terms = vals, active, ranges, S, terms
@@ -265,7 +268,7 @@ class _DevicePool(object):
         # the last joint scoring left (``_joint_device``)
         self.rows_out = self.count = self.scratch = None
         self.first = self.mask = self.distinct_scratch = None
-        self.fits = self.parts = None
+        self.fits = self.parts = self.above = None
 
 
 class Pool(object):
@@ -553,7 +556,8 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
     """``Pool.sample`` under the settings ``st``.  With ``st.joint`` the joint
     labels come from ``tpe_joint_sample`` and S starts from J; with ``st.lie``
     too the mirror keeps the fit and the born parts (log L_below, log L_above,
-    unused) as ``_joint_device`` leaves them."""
+    unused) as ``_joint_device`` leaves them -- under ``batch="liar-tree"`` the
+    tree fits and the groups' log L_above (``_above``)."""
     from . import tpe as T
     domain = as_domain(domain)
     labels = list(domain.params)
@@ -620,7 +624,10 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
             n_active = _rows_active(eng, domain, labels, d, P, sp)
         # S starts from J of the drawn rows; the fold below adds the other labels
         # (with the groups every label is joint: S is theirs, and nothing is folded)
-        if joint["tree"]:
+        if st.lie_tree:  # (the groups' log L_above stays)
+            d.fits, d.above = fits, _above(eng, fits, P)
+            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above)
+        elif joint["tree"]:
             _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S)
         else:
             if st.lie is not None:  # (log L_above of the born rows stays, for the batch)
@@ -1172,12 +1179,24 @@ def _parts(eng, domain, st, P):
     return t.empty((3, max(P, 1)), dtype=t.float64, device=eng.device)
 
 
+def _above(eng, fits, P):
+    """The (G, P) device tensor ``joint.score_tree_device(above=)`` leaves the
+    groups' log L_above in, for ``batch="liar-tree"``."""
+    t = eng.torch
+    return t.empty((len(fits), max(P, 1)), dtype=t.float64, device=eng.device)
+
+
 def _joint_device(eng, domain, pool, d, st, hist):
     """J (joint.py) of every pool row into ``d.S`` -- with ``tree`` the groups'
     S (``joint.score_tree_device``) -- and its parts into ``d.parts`` where
-    that is a tensor (``_parts``).  The mirror keeps the fit in ``d.fits``."""
+    that is a tensor (``_parts``).  The mirror keeps the fit in ``d.fits``, and
+    under ``batch="liar-tree"`` the groups' log L_above in ``d.above``."""
     P, L, ld = len(pool), len(pool.labels), d.vals.shape[1]
     d.fits = _fit(eng, domain, hist, L, st)
+    if st.lie_tree:
+        d.above = _above(eng, d.fits, P)
+        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts, above=d.above)
+        return
     if st.joint["tree"]:
         _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts)
         return
@@ -1192,7 +1211,8 @@ def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=Fa
     device pool).  With ``st.joint`` S starts from J and the fold adds the
     other labels' terms, and the mirror keeps the fit in ``fits`` and -- with
     ``want_parts``, and for ``batch="liar"`` -- the parts in ``parts``
-    (``_parts``); both are None otherwise."""
+    (``_parts``); both are None otherwise.  ``batch="liar-tree"`` keeps the
+    groups' log L_above in ``above`` instead (``_joint_device``)."""
     if isinstance(pool, GridPool):  # (ValueError(GRID_JOINT) on a grid without the plan)
         return _score_grid(domain, trials, pool, st, False, hist)[:2]
     _same_space(domain, pool)
@@ -1213,8 +1233,8 @@ def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=Fa
     P = len(pool)
     if want_terms and d.terms is None:
         d.terms = t.empty((len(pool.labels), max(P, 1)), dtype=t.float64, device=eng.device)
-    d.fits = d.parts = None
-    if joint is not None and (want_parts or st.lie is not None):
+    d.fits = d.parts = d.above = None
+    if joint is not None and (want_parts or (st.lie is not None and not st.lie_tree)):
         d.parts = _parts(eng, domain, st, P)
     if P == 0:
         return eng, d
@@ -1420,6 +1440,8 @@ def _joint_cols(domain, jkw):
 
 BATCH_LIAR = ("batch='liar' is supported with joint=True on a Pool or a SampledPool "
               "(suggest_from_pool, suggest_sampled, pick_batch)")
+BATCH_LIAR_TREE = ("batch='liar-tree' is supported with joint='tree' on a Pool or a SampledPool "
+                   "(suggest_from_pool, suggest_sampled, pick_batch(joint='tree'))")
 
 
 REFINE = ("refine= moves the picked rows' continuous always-live labels up the joint "
@@ -1429,13 +1451,16 @@ REFINE = ("refine= moves the picked rows' continuous always-live labels up the j
 class _Settings(object):
     """What a scoring and the picks after it run under: ``prior_weight``,
     ``gamma``, ``lf`` (linear forgetting), ``joint`` (``_joint_kw``) and
-    ``lie`` (None, or the lie's weight of ``batch="liar"``) and ``refine`` (the
-    steps the picked rows climb, joint.py "Refining"; 0: none)."""
-    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine")
+    ``lie`` (None, or the lie's weight of ``batch="liar"`` / ``"liar-tree"``),
+    ``lie_tree`` (the lie is ``"liar-tree"``'s: one per group, joint.py "Batches
+    in a tree") and ``refine`` (the steps the picked rows climb, joint.py
+    "Refining"; 0: none)."""
+    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine", "lie_tree")
 
     def __init__(self, prior_weight, gamma, lf, joint=None, lie=None, refine=0):
         self.prior_weight, self.gamma, self.lf, self.joint, self.lie, self.refine = \
             prior_weight, gamma, lf, joint, lie, refine
+        self.lie_tree = False
 
 
 def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
@@ -1443,7 +1468,8 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
               refine=None, domain=None):
     """The ``_Settings`` of a public call's keywords, after the checks:
     ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
-    ``"liar"``, on a ``lie_weight`` that is not a finite number > 0, and on
+    ``"liar"`` (needs ``joint=True``) and ``"liar-tree"`` (needs
+    ``joint="tree"``), on a ``lie_weight`` that is not a finite number > 0, and on
     what the batch is not built for (joint.py, "Not built"; ``pool``: the
     call's pool, where it has one; ``domain``: the call's space, for the keys of
     a ``bandwidth`` mapping).  A ``refine`` that is not None: ValueError
@@ -1456,17 +1482,32 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
                              "factorised criterion (joint=False) are not refined")
     if batch is None:
         return st
-    if batch != "liar":
-        raise ValueError("batch=%r: None or 'liar'" % (batch,))
+    if batch not in ("liar", "liar-tree"):
+        raise ValueError("batch=%r: None or 'liar' (joint=True) or 'liar-tree' (joint='tree')"
+                         % (batch,))
     if not lie_weight > 0.0 or not math.isfinite(lie_weight):
         raise ValueError("lie_weight=%r must be a finite number > 0" % (lie_weight,))
+    if batch == "liar-tree":
+        if st.joint is None or not st.joint["tree"]:
+            raise ValueError(BATCH_LIAR_TREE + "; with joint=True the batch is batch='liar', "
+                             "and the factorised criterion (joint=False) has none: pass "
+                             "joint='tree'")
+        if st.joint["tree"] == "chain":
+            raise ValueError(BATCH_LIAR_TREE + "; under joint='chain' a group's term is a "
+                             "ratio, and a lie would have to join numerator and denominator")
+        if isinstance(pool, GridPool):
+            raise ValueError(BATCH_LIAR_TREE + "; a GridPool has no row values to lie with "
+                             "(GridPool.to_pool())")
+        st.lie, st.lie_tree = float(lie_weight), True
+        return st
     if st.joint is None:
         raise ValueError(BATCH_LIAR + "; the factorised criterion (joint=False) has no such "
                          "update: its bandwidths depend on the sorted neighbours")
     if st.joint["tree"] == "chain":
         raise ValueError(BATCH_LIAR + "; joint='chain' keeps no log L_above per group")
     if st.joint["tree"]:
-        raise ValueError(BATCH_LIAR + "; joint='tree' keeps no log L_above per group")
+        raise ValueError(BATCH_LIAR + "; joint='tree' keeps no log L_above per group for it "
+                         "(batch='liar-tree' does, and lies in every group)")
     if isinstance(pool, GridPool):
         raise ValueError(BATCH_LIAR + "; a GridPool has no row values to lie with "
                          "(GridPool.to_pool())")
@@ -1474,11 +1515,12 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
     return st
 
 
-def _liar_device(eng, d, P, k, mask, lie_weight, trace=False):
+def _liar_device(eng, d, P, k, mask, lie_weight, trace=False, tree=False):
     """``_topk_device`` for ``batch="liar"``: the rows of ``joint.liar_device``
     on d.S, with the fit and the log L_above the scoring left in the mirror
     (``_joint_device``); ``mask``: ``distinct``'s device mask or None.  The rows
-    stay in d.rows_out."""
+    stay in d.rows_out.  ``tree`` (``st.lie_tree``, ``batch="liar-tree"``): the
+    rows of ``joint.liar_tree_device`` on the tree fits and ``d.above``."""
     t = eng.torch
     k = min(int(k), P)
     if d.rows_out is None or d.rows_out.numel() < k + 1:
@@ -1486,6 +1528,9 @@ def _liar_device(eng, d, P, k, mask, lie_weight, trace=False):
         # entry k of the rows, read back with them)
         d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
         d.count = t.zeros(1, dtype=t.int64, device=eng.device)
+    if tree:
+        return _J.liar_tree_device(d.fits, d.vals, d.active, d.vals.shape[1], d.vals.shape[0], P,
+                                   d.S, d.above, d.taken, mask, k, lie_weight, trace, d.rows_out)
     return _J.liar_device(d.fits[0], d.vals, d.vals.shape[1], d.vals.shape[0], P, d.S, d.parts[1],
                           d.taken, mask, k, lie_weight, trace, d.rows_out)
 
@@ -1501,20 +1546,24 @@ def _pick(eng, pool, d, k, hist, distinct, st, trace=False):
     mask = d.mask if distinct else None
     if st.lie is None:
         return _topk_device(eng, d, len(pool), k, mask)
-    return _liar_device(eng, d, len(pool), k, mask, st.lie, trace)
+    return _liar_device(eng, d, len(pool), k, mask, st.lie, trace, st.lie_tree)
 
 
 def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_weight=1.0,
                prior_weight=1.0, gamma=0.25, linear_forgetting=25, bandwidth=_J.BANDWIDTH,
-               cat_smoothing=_J.CAT_SMOOTHING):
+               cat_smoothing=_J.CAT_SMOOTHING, joint=True):
     """The rows ``suggest_from_pool(joint=True, batch="liar")`` would hand out
     for k ids past the startup phase, in pick order (numpy int64; joint.py,
     "Batches"), without marking anything taken.  ``return_trace``: (rows,
     S_at_pick, S_k) -- the score each row was picked at and every row's score
-    after the last pick.  A ``GridPool`` raises ValueError."""
+    after the last pick.  A ``GridPool`` raises ValueError.  ``joint="tree"``:
+    the rows of ``suggest_from_pool(joint="tree", batch="liar-tree")`` (joint.py,
+    "Batches in a tree"); any other value is judged as ``batch="liar"`` judges
+    it."""
     from . import tpe as T
     domain = as_domain(domain)
-    st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing, "liar",
+    batch = "liar-tree" if isinstance(joint, str) and joint == "tree" else "liar"
+    st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
                    lie_weight, pool, domain=domain)
     _same_space(domain, pool)
     hist = T.collect_history(trials, pool.labels)
@@ -1667,6 +1716,11 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     evaluation that does not crowd one mode.  The first document is the one
     ``batch=None`` gives; the startup phase, ``distinct`` and the taken rules
     are unchanged.  ``batch=None``: the k best rows of one score.
+    ``batch="liar-tree"`` (with ``joint="tree"``; anything else raises
+    ValueError): the same batch on a conditional space -- a pick joins the above
+    mixture of every group of labels it is live in, so rows that differ under a
+    ``switch`` alone are told apart (joint.py, "Batches in a tree").  On a flat
+    space it is ``batch="liar"`` with ``joint=True``, bit for bit.
 
     ``refine``: anything but None raises ValueError -- a fixed pool's rows are
     a closed set, and a ``GridPool`` has no row to move
@@ -1935,7 +1989,9 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     joining the above mixture with weight ``lie_weight`` (joint.py,
     "Batches"; ``suggest_from_pool``).  log L_above is the one the scoring
     leaves: the pool's born parts under ``draw="joint"``.  ``keep``,
-    ``distinct`` and the startup phase are unchanged.
+    ``distinct`` and the startup phase are unchanged.  ``batch="liar-tree"``
+    (needs ``joint="tree"``): a pick lies in every group it is live in
+    (``suggest_from_pool``).
 
     ``refine=N`` (needs ``joint=True``; ValueError otherwise, and for anything
     but an integer >= 0): the best draw lies between the mixture's peaks and

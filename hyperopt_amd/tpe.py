@@ -46,7 +46,9 @@ factor tables, again without its rows (``grid_joint_plan``).
 ``batch="liar"`` (with ``joint=True``) picks the k rows of a call one at a
 time on the device, each pick joining the above mixture as the pending trial
 it is about to become, so a batch for parallel evaluation spreads out
-(``pick_batch``: the rows alone; ``joint_liar_numpy``).
+(``pick_batch``: the rows alone; ``joint_liar_numpy``).  ``batch="liar-tree"``
+(with ``joint="tree"``) is that batch on a conditional space: a pick lies in
+every group of labels it is live in (``joint_liar_tree_numpy``).
 ``suggest_sampled(joint=True, refine=N)`` lets the picked rows climb the joint
 criterion on their continuous labels, on the device (``refine_configs``: any
 rows; ``joint_refine_numpy``).  ``bandwidth="loo"`` (with ``joint=True`` /
@@ -813,6 +815,7 @@ from .pool import (GridPool, Pool, SampledPool, distinct_rows, grid_joint_plan, 
 from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_contexts,
                     joint_groups, joint_labels, liar_numpy as joint_liar_numpy,
+                    liar_tree_numpy as joint_liar_tree_numpy,
                     loo_label_fit_numpy as joint_loo_label_fit_numpy,
                     loo_label_numpy as joint_loo_label_numpy, loo_numpy as joint_loo_numpy,
                     refine_numpy as joint_refine_numpy, score_numpy as joint_score_numpy)

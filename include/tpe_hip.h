@@ -1126,6 +1126,66 @@ int tpe_joint_lie_picks(const tpe_joint_label* host_labels, const tpe_joint_labe
                         int64_t k, int64_t* out_rows, int64_t* out_count, double* S_at_pick,
                         double* S_k, void* scratch, void* stream);
 
+/* ---- a batch whose picks lie in every group they are live in -------------------
+ * (tpe.suggest_from_pool(joint="tree", batch="liar-tree"); hyperopt_amd/joint.py,
+ * "Batches in a tree".)  Under joint="tree" every group g of labels has its own
+ * above mixture; pick p joins the mixture of every group live in row p:
+ *   U_{g,0}[r] = group_log_w[g] + A[g * ldA + r]                 (g live in r)
+ *   c_{g,p}(r) = log_lie + sum_{d in g} log k_d(r_d)             (g live in p, r)
+ *   U_{g,j}[r] = U_{g,j-1}[r] joined with c_{g,p_j}(r) by tpe_joint_lie_picks'
+ *                rule; every other (g, r) keeps U_{g,j-1}[r]
+ *   S_j[r]     = S0[r], then in group order over the groups live in r whose
+ *                U_{g,0}[r] is finite: S_j[r] = S_j[r] - (U_{g,j}[r] - U_{g,0}[r])
+ * The picks, their order, the masks and the stop are tpe_joint_lie_picks'.
+ *
+ * host_labels / labels: all groups' label records concatenated in group order,
+ * n_labels = D_tot of them, on the host and on the device; tables: the groups'
+ * discrete tables concatenated, every record's tab_off counted from the start of
+ * the concatenation.  group_off (host, n_groups + 1 entries): group g's records
+ * are [group_off[g], group_off[g + 1]) -- group_off[0] = 0, strictly ascending,
+ * group_off[n_groups] = n_labels.  group_log_w (host): log W_g, < +inf.
+ * group_col (host): the column whose `active` byte says that g is live in a row,
+ * -1 for a group live in every row; group 0 is the root, -1.  sigma (device):
+ * n_labels bandwidths in record order, then the n_labels values 1 / (sqrt(2)
+ * sigma); read for the labels with a bandwidth only (may be NULL when every
+ * label is discrete).  vals / active: the label-major pool (n_cols x ld doubles / bytes;
+ * active may be NULL when n_groups == 1); a label's value is read only in rows
+ * in which its group is live.  A (device): log L_above,g of row r at
+ * A[g * ldA + r], read where g is live in r only; ldA >= n_rows.  S0, taken,
+ * distinct, k, out_rows, out_count, S_at_pick, S_k as tpe_joint_lie_picks
+ * takes them; nothing but the outputs and the scratch is written.  scratch:
+ * tpe_joint_lie_tree_scratch_bytes(n_rows, n_groups) bytes (-1: bad
+ * arguments), 16-byte aligned.
+ *
+ * One call enqueues all k picks (a pick's row is read on the device).  A row's
+ * bits depend on the row, the records and the pick sequence only; with
+ * n_groups == 1 rows, S_at_pick and S_k have the bits of tpe_joint_lie_picks on
+ * the same inputs.  No floating-point atomics.  Limits: n_labels and n_groups
+ * <= TPE_COND_MAX_LABELS, n_cat <= TPE_JOINT_MAX_CAT, else TPE_E_UNSUPPORTED;
+ * bad arguments return TPE_E_ARG before any launch; k <= 0 or n_rows == 0
+ * writes the count 0 (and S0 to S_k where given).  Asynchronous on `stream`, no
+ * allocation.
+ *
+ * tpe_rows_scatter: dst[rows[p]] = src[p - list_begin] for the list positions p
+ * in [list_begin, min(list_begin + max_rows, *d_count)) of a device list
+ * (tpe_rows_compact's): the dense result of a tpe_joint_score_rows call with
+ * out_mode 0, put where its rows are.  d_count is read on the device only; an
+ * entry outside [0, ld) is skipped; dst holds ld doubles.  max_rows == 0 and
+ * ld == 0 are no-ops. */
+int64_t tpe_joint_lie_tree_scratch_bytes(int64_t n_rows, int n_groups);
+int tpe_joint_lie_tree_picks(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                             int n_labels, const double* tables, int64_t n_tables,
+                             const int32_t* group_off, const double* group_log_w,
+                             const int32_t* group_col, int n_groups, const double* sigma,
+                             const double* vals, const uint8_t* active, int64_t ld, int n_cols,
+                             int64_t n_rows, const double* S0, const double* A, int64_t ldA,
+                             double log_lie, const uint8_t* taken, const uint8_t* distinct,
+                             int64_t k, int64_t* out_rows, int64_t* out_count,
+                             double* S_at_pick, double* S_k, void* scratch, void* stream);
+int tpe_rows_scatter(const double* src, const int64_t* rows, const int64_t* d_count,
+                     int64_t list_begin, int64_t max_rows, double* dst, int64_t ld,
+                     void* stream);
+
 /* ---- rows that climb the joint criterion ---------------------------------------
  * (tpe.suggest_sampled(joint=True, refine=N), tpe.refine_configs;
  * hyperopt_amd/joint.py, "Refining".)  Rows [0, n_rows) of the label-major block
