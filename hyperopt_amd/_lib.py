@@ -75,6 +75,27 @@ JOINT_LOG, JOINT_BOUNDED = 1, 2
 JOINT_MAX_CAT = 65536
 JOINT_OUT_SCATTER, JOINT_OUT_ADD = 1, 2  # tpe_joint_score_rows' out_mode
 REFINE_MAX_CONT = 16  # tpe_joint_refine's continuous labels (TPE_REFINE_MAX_CONT)
+# tpe_joint_refine_tree's group record (tpe_hip.h tpe_refine_group) and its LDS
+# stage: 54 KB of doubles, the below set's place sized for 26 components
+REFINE_GROUP_DTYPE = np.dtype([
+    ("first", "<i4"), ("count", "<i4"), ("live_col", "<i4"), ("n_cont", "<i4"), ("g_off", "<i4"),
+    ("pad_", "<i4"), ("tab_off", "<i8"), ("n_below", "<i8"), ("n_above", "<i8"),
+    ("set_below", "<u8"), ("set_above", "<u8")], align=True)
+REFINE_STAGE_DOUBLES, REFINE_STAGE_BELOW = 54 * 1024 // 8, 26
+
+
+def refine_stage_components(n_labels):
+    """The largest C = n + 1 at which tpe_joint_refine_tree stages the above set
+    of a group of ``n_labels`` labels in LDS (0: never)."""
+    D = int(n_labels)
+    size = lambda C: ((C + 1) & ~1) + 2 * D * C  # noqa: E731
+    rest = REFINE_STAGE_DOUBLES - size(REFINE_STAGE_BELOW)
+    C = rest // (2 * D + 1)
+    while C > 0 and size(C) > rest:
+        C -= 1
+    return C
+
+
 LOO_MAX_GRID = 16  # tpe_joint_loo's multipliers per call (TPE_LOO_MAX_GRID)
 GRID_JOINT_STORE, GRID_JOINT_ADD = 0, 1  # tpe_grid_joint_score's out_mode
 OP_ARGS = 23
@@ -212,6 +233,10 @@ _SIGNATURES = {
     "tpe_joint_refine": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I,
                               _P, _P, _P, _P, _P]),
     "tpe_joint_refine_max_cont": (_I, []),
+    "tpe_joint_refine_tree": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I, _P, _P, _I64, _I, _I64, _I,
+                                   _P, _P, _P, _P, _P]),
+    "tpe_joint_refine_tree_stage_components": (_I64, [_I]),
+    "tpe_joint_refine_tree_group_bytes": (_I, []),
     "tpe_joint_loo_scratch_bytes": (_I64, [_I, _I, _I64, _I]),
     "tpe_joint_loo": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, ctypes.c_double,
                            ctypes.c_double, _P, _I, _P, _P, _P]),
@@ -315,6 +340,15 @@ def load():
     if lib.tpe_joint_refine_max_cont() != REFINE_MAX_CONT:
         raise ImportError("hyperopt_amd: TPE_REFINE_MAX_CONT is %d in the library, %d here"
                           % (lib.tpe_joint_refine_max_cont(), REFINE_MAX_CONT))
+    if lib.tpe_joint_refine_tree_group_bytes() != REFINE_GROUP_DTYPE.itemsize:
+        raise ImportError("hyperopt_amd: tpe_refine_group is %d bytes in the library, %d here"
+                          % (lib.tpe_joint_refine_tree_group_bytes(), REFINE_GROUP_DTYPE.itemsize))
+    for D in (1, 8, COND_MAX_LABELS):
+        if lib.tpe_joint_refine_tree_stage_components(D) != refine_stage_components(D):
+            raise ImportError("hyperopt_amd: tpe_joint_refine_tree stages %d components of %d "
+                              "labels in the library, %d here"
+                              % (lib.tpe_joint_refine_tree_stage_components(D), D,
+                                 refine_stage_components(D)))
     if lib.tpe_joint_loo_max_grid() != LOO_MAX_GRID:
         raise ImportError("hyperopt_amd: TPE_LOO_MAX_GRID is %d in the library, %d here"
                           % (lib.tpe_joint_loo_max_grid(), LOO_MAX_GRID))

@@ -274,6 +274,42 @@ row's whole climb in one launch (inside a_i the device adds the fixed labels'
 factors first, then the moving ones': its J equals the scorer's to rounding,
 and ``tpe.refine_configs`` reports J before and after from ``score_device``).
 
+Refining in a tree (``joint="tree"``, ``refine_tree=N``,
+csrc/tpe_joint_refine_tree.hip).  On a space that opens with a
+``switch`` every continuous label that matters sits inside a branch, where
+``refine`` does not reach.  Under ``joint="tree"`` S(c) = sum_g J_g(c_g) over
+disjoint label groups, so the climb separates exactly into one independent
+climb per (row, live group).
+
+  groups       those of ``joint_groups(domain)``, with the fits and sets of
+               ``joint="tree"`` (``fit(..., tree=True)``).
+  liveness     the root group is live in every row, group g > 0 where the
+               ``active`` byte of its first label is set (the rule
+               ``score_tree_device`` and ``liar_tree_*`` use).
+  climb        for every row and every group g live in it, g's ``JOINT_CONT``
+               labels -- D_c,g of them, in list order -- run the climb of
+               "Refining", unchanged: with g's two sets, J_g, g's gradient, s_d
+               from g's below set, and an h, decisions and 2^-20 stop of its
+               own.  Quantized and discrete labels stay; the selectors are
+               discrete, so liveness is constant along a climb.  Groups do not
+               see each other.
+  result       sum_g J_g never decreases; ``refine_tree=0`` is the identity bit
+               for bit; a pair whose first J_g is NaN or +-inf does not move; a
+               label that ends where it started keeps its stored bits; entries of
+               labels not live in the row are never read or written.
+  limits       D_c,g <= ``TPE_REFINE_MAX_CONT`` per group, G and D_tot <=
+               ``TPE_COND_MAX_LABELS``; ValueError otherwise.
+  identities   on a flat space (G = 1) the result has the bits of ``refine=N``
+               with ``joint=True``; on any space the root group's columns have
+               the bits ``refine=N`` / ``refine_configs`` give them, because the
+               root fit is the ``joint=True`` fit.
+
+``refine_tree_numpy`` is this definition in numpy (it and ``refine_numpy`` run
+one helper, per mixture pair and row subset); ``refine_tree_device`` runs every
+pair's whole climb in one tpe_joint_refine_tree, and
+``tpe.refine_configs(joint="tree")`` reports J_g before and after from
+``score_tree_device``'s per-group parts.
+
 Bandwidth (``bandwidth="loo"``, ``tpe.joint_bandwidth``, csrc/tpe_joint_loo.hip,
 DESIGN 3.5.11).  Every path above takes one multiplier h in ``sigma = h sigma_p
 n ** (-1 / (D + 4))``; ``BANDWIDTH`` is a guess.  ``"loo"`` takes the grid value
@@ -392,8 +428,9 @@ would have to join numerator and denominator; ``batch="liar"`` itself keeps
 ``joint=True``, and ``batch="liar-tree"`` ``joint="tree"``), on a ``GridPool`` (a
 grid has no row values to lie with) and under the factorised criterion (its
 adaptive bandwidths depend on the sorted neighbours: no component can be added
-without a refit).  ``refine`` under
-``joint="tree"`` / ``"chain"`` (a group's labels move only where it is live).
+without a refit).  ``refine`` / ``refine_tree`` under ``joint="chain"`` (a group's
+term is a ratio over ctx + g: the groups are coupled through their contexts and
+the climb does not separate).
 ``bandwidth="loo"`` / ``"loo-label"`` under ``joint="chain"`` (its fits are over
 ctx + g and enter as a ratio: the likelihood of a set under its own fit is not
 what they are ranked by) and on a ``GridPool`` (both take a float or a mapping).
@@ -986,40 +1023,24 @@ def _refine_set(models, cont, hist, rows, x, t, lf, prior_weight, bandwidth, smo
     return L, dlog, m1, K
 
 
-def refine_numpy(domain, hist, vals, refine, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
-                 bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING, return_info=False):
-    """The climb of module doc "Refining" in vectorised numpy, every row of
-    ``vals`` ((P, L) stored values as ``Pool.vals`` holds them) by itself:
-    (refined copy of ``vals``, J_start, J_end, g_end (P, D_c), accepted).
-
-    ``return_info``: one more entry, what a comparison at ``REFINE_TOL`` per
-    log-density needs, all from this reference alone: ``J_bound`` (P,) =
-    tol (|log L_below| + |log L_above|) and ``g_bound`` (P, D_c) = tol sum_i
-    r_i |mu_i - t| / sigma_i^2 over both sets, both at the last accepted point;
-    ``t_bound`` (P, D_c), the bound on t there propagated per accepted step --
-    a deviation dt of the point and dg <= g_bound of its gradient give
-    dt'_d <= dt_d + h s_d^2 (sum_e K_de dt_e + dg_d), K bounding the gradient's
-    derivative (``K`` (P, D_c, D_c), at the last accepted point; the clamp does
-    not stretch a deviation); and ``margin`` (steps, P), per decision |J(t') -
-    J(t)| over the sum of the two points' J bounds -- NaN where the row took no
-    decision, inf where t' is t itself."""
-    domain = as_domain(domain)
-    refine = check_refine(refine)
-    models = label_models(domain)
+def _refine_climb(models, sets, rows, hist, vals, refine, lf, prior_weight, bandwidth, smoothing,
+                  return_info):
+    """The climb of one mixture pair -- the labels ``models``, the two history
+    row sets ``sets`` -- for the rows ``rows`` (indices) of ``vals``, written in
+    place: (J_start, J_end, g_end, accepted, info or None) over those rows."""
     cont = moving_labels(models)
-    vals = np.array(vals, np.float64, ndmin=2)
     cols = [m.col for m in models]
-    x = vals[:, cols]
+    rows = np.asarray(rows, np.int64)
+    x = vals[np.ix_(rows, cols)]
     P, Dc = x.shape[0], len(cont)
-    sets = [set_rows(hist, mask, cols) for mask in split_sets(hist, gamma)]
     sb = bandwidths(models, sets[0].size, bandwidth)
     s2 = np.asarray([(sb[d] if sets[0].size else models[d].sigma) ** 2 for d in cont])
     t0 = np.stack([_fit(models[d], x[:, d]) for d in cont], 1) if Dc else np.zeros((P, 0))
 
     def evaluate(t):
         (Lb, db, ab, Kb), (La, da, aa, Ka) = [
-            _refine_set(models, cont, hist, rows, x, t, linear_forgetting, prior_weight,
-                        bandwidth, cat_smoothing, return_info) for rows in sets]
+            _refine_set(models, cont, hist, rows, x, t, lf, prior_weight, bandwidth,
+                        smoothing, return_info) for rows in sets]
         with np.errstate(invalid="ignore"):
             return (Lb - La, db - da, REFINE_TOL * (np.abs(Lb) + np.abs(La)),
                     REFINE_TOL * (ab + aa), Kb + Ka)
@@ -1058,11 +1079,94 @@ def refine_numpy(domain, hist, vals, refine, prior_weight=1.0, gamma=0.25, linea
         h = np.where(better, np.minimum(1.0, 2.0 * h), np.where(go, 0.5 * h, h))
     for j, d in enumerate(cont):  # (a label that did not move keeps its stored bits)
         moved = t[:, j] != t0[:, j]
-        vals[moved, cols[d]] = (np.exp(t[:, j]) if models[d].is_log else t[:, j])[moved]
-    out = (vals, J_start, J, g, acc)
-    if return_info:
-        out += (dict(J_bound=Jb, g_bound=gb, t_bound=tb, K=K, margin=margin),)
-    return out
+        vals[rows[moved], cols[d]] = (np.exp(t[:, j]) if models[d].is_log else t[:, j])[moved]
+    info = dict(J_bound=Jb, g_bound=gb, t_bound=tb, K=K, margin=margin) if return_info else None
+    return J_start, J, g, acc, info
+
+
+def refine_numpy(domain, hist, vals, refine, prior_weight=1.0, gamma=0.25, linear_forgetting=25,
+                 bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING, return_info=False):
+    """The climb of module doc "Refining" in vectorised numpy, every row of
+    ``vals`` ((P, L) stored values as ``Pool.vals`` holds them) by itself:
+    (refined copy of ``vals``, J_start, J_end, g_end (P, D_c), accepted).
+
+    ``return_info``: one more entry, what a comparison at ``REFINE_TOL`` per
+    log-density needs, all from this reference alone: ``J_bound`` (P,) =
+    tol (|log L_below| + |log L_above|) and ``g_bound`` (P, D_c) = tol sum_i
+    r_i |mu_i - t| / sigma_i^2 over both sets, both at the last accepted point;
+    ``t_bound`` (P, D_c), the bound on t there propagated per accepted step --
+    a deviation dt of the point and dg <= g_bound of its gradient give
+    dt'_d <= dt_d + h s_d^2 (sum_e K_de dt_e + dg_d), K bounding the gradient's
+    derivative (``K`` (P, D_c, D_c), at the last accepted point; the clamp does
+    not stretch a deviation); and ``margin`` (steps, P), per decision |J(t') -
+    J(t)| over the sum of the two points' J bounds -- NaN where the row took no
+    decision, inf where t' is t itself."""
+    domain = as_domain(domain)
+    refine = check_refine(refine)
+    models = label_models(domain)
+    moving_labels(models)  # (ValueError over the limit, before anything else)
+    vals = np.array(vals, np.float64, ndmin=2)
+    cols = [m.col for m in models]
+    sets = [set_rows(hist, mask, cols) for mask in split_sets(hist, gamma)]
+    out = _refine_climb(models, sets, np.arange(vals.shape[0]), hist, vals, refine,
+                        linear_forgetting, prior_weight, bandwidth, cat_smoothing, return_info)
+    return (vals,) + out[:4] + ((out[4],) if return_info else ())
+
+
+def refine_tree_numpy(domain, hist, vals, refine, active=None, prior_weight=1.0, gamma=0.25,
+                      linear_forgetting=25, bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING,
+                      return_info=False):
+    """The climb of module doc "Refining in a tree" in numpy: every (row, live
+    group) of ``vals`` by itself.  ``active`` ((P, L); None: where ``vals`` is
+    not NaN) says where a group is live, by its first label.  Returns (refined
+    copy of ``vals``, J_start (P, G), J_end (P, G), g_end (P, sum of D_c,g; group
+    g's moving labels at the offset of the groups before it), accepted (P, G)),
+    NaN / 0 where a group is not live.  ``return_info``: one more entry,
+    ``refine_numpy``'s dict with the same shapes -- ``J_bound`` (P, G),
+    ``g_bound`` / ``t_bound`` (P, sum D_c,g), ``K`` a list per group of (P,
+    D_c,g, D_c,g) (NaN rows where it is not live) and ``margin`` (steps, P, G)."""
+    domain = as_domain(domain)
+    refine = check_refine(refine)
+    groups = [label_models(domain, grp.labels) for grp in joint_groups(domain)]
+    Dc = [len(moving_labels(models)) for models in groups]
+    check_tree_limits(groups)
+    vals = np.array(vals, np.float64, ndmin=2)
+    active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
+    P, G, off = vals.shape[0], len(groups), np.concatenate([[0], np.cumsum(Dc)]).astype(int)
+    J0, J1 = np.full((P, G), np.nan), np.full((P, G), np.nan)
+    g_end, acc = np.full((P, off[-1]), np.nan), np.zeros((P, G), np.int32)
+    info = dict(J_bound=np.full((P, G), np.nan), g_bound=np.full((P, off[-1]), np.nan),
+                t_bound=np.full((P, off[-1]), np.nan), K=[],
+                margin=np.full((refine, P, G), np.nan))
+    masks = split_sets(hist, gamma)
+    for g, models in enumerate(groups):
+        cols = [m.col for m in models]
+        rows = np.arange(P) if g == 0 else np.flatnonzero(active[:, cols[0]])
+        sets = [set_rows(hist, mask, cols) for mask in masks]
+        a, b, c, d, more = _refine_climb(models, sets, rows, hist, vals, refine,
+                                         linear_forgetting, prior_weight, bandwidth,
+                                         cat_smoothing, return_info)
+        sl = slice(off[g], off[g + 1])
+        J0[rows, g], J1[rows, g], g_end[rows, sl], acc[rows, g] = a, b, c, d
+        if return_info:
+            for name in ("J_bound", "g_bound", "t_bound"):
+                info[name][rows, sl if name != "J_bound" else g] = more[name]
+            K = np.full((P, Dc[g], Dc[g]), np.nan)
+            K[rows] = more["K"]
+            info["K"].append(K)
+            info["margin"][:, rows, g] = more["margin"]
+    out = (vals, J0, J1, g_end, acc)
+    return out + (info,) if return_info else out
+
+
+def check_tree_limits(groups):
+    """ValueError where tpe_joint_refine_tree would return TPE_E_UNSUPPORTED:
+    more than ``COND_MAX_LABELS`` groups, or labels over all of them (``groups``:
+    one label-model list per group; ``moving_labels`` checks a group's D_c)."""
+    G, D_tot = len(groups), sum(len(models) for models in groups)
+    if G > _L.COND_MAX_LABELS or D_tot > _L.COND_MAX_LABELS:
+        raise ValueError("refine_tree: %d groups of %d labels in all, at most %d of either"
+                         % (G, D_tot, _L.COND_MAX_LABELS))
 
 
 # -- bandwidth (module doc, "Bandwidth") -----------------------------------------
@@ -1610,6 +1714,73 @@ def refine_device(fit, d_block, ld, n_cols, k, refine, trace=None):
                                   dj.n_tables, below.data_ptr(), nb, above.data_ptr(), na,
                                   d_block.data_ptr(), ld, n_cols, k, refine, *ptrs, sp),
              "tpe_joint_refine")
+
+
+class _RefinePack(object):
+    """The groups of a tree fit as tpe_joint_refine_tree takes them: the label
+    records one group after the other and the group table
+    (``REFINE_GROUP_DTYPE``), each on the host and on the device, the
+    concatenated tables, and D_c,g per group."""
+    __slots__ = ("host", "dev", "tables", "n_tables", "groups", "groups_dev", "n_cont")
+
+
+def _refine_pack(fits):
+    """``_RefinePack`` of ``fits`` (``fit(..., tree=True)``).  ValueError over a
+    limit of the kernel."""
+    eng = fits[0].eng
+    t = eng.torch
+    check_tree_limits([f.dj.models for f in fits])
+    pk = _RefinePack()
+    pk.n_cont = [len(moving_labels(f.dj.models)) for f in fits]
+    rec = np.zeros(len(fits), _L.REFINE_GROUP_DTYPE)
+    first = base = g_off = 0
+    for g, f in enumerate(fits):
+        r = rec[g]
+        r["first"], r["count"], r["tab_off"] = first, len(f.dj.models), base
+        r["live_col"] = -1 if g == 0 else f.dj.models[0].col
+        r["n_cont"], r["g_off"] = pk.n_cont[g], g_off
+        (below, nb, _), (above, na, _) = f.sets
+        r["n_below"], r["n_above"] = nb, na
+        r["set_below"], r["set_above"] = below.data_ptr(), above.data_ptr()
+        first, base, g_off = first + len(f.dj.models), base + f.dj.n_tables, g_off + pk.n_cont[g]
+    pk.host = np.concatenate([f.dj.host for f in fits])
+    pk.dev = t.from_numpy(pk.host.view(np.uint8).copy()).to(eng.device)
+    tabs = [f.dj.tables for f in fits if f.dj.tables is not None]
+    pk.tables, pk.n_tables = (t.cat(tabs) if tabs else None), base
+    pk.groups = rec
+    pk.groups_dev = t.from_numpy(rec.view(np.uint8).copy()).to(eng.device)
+    return pk
+
+
+def refine_tree_device(fits, d_block, d_active, ld, n_cols, k, refine, trace=None):
+    """The climb of module doc "Refining in a tree" for rows [0, k) of the
+    label-major device block ``d_block`` / ``d_active`` (bytes; leading
+    dimension ``ld``, ``n_cols`` columns; offset-free values) under ``fits``
+    (``fit(..., tree=True)``), in place: one tpe_joint_refine_tree, nothing read
+    back.  ``trace``: a dict that receives the device tensors ``J_start``,
+    ``J_end`` (k, G), ``g_end`` (k, sum of D_c,g) and ``accepted`` (k, G; int32).
+    ValueError past ``TPE_REFINE_MAX_CONT`` continuous labels in a group, or
+    ``TPE_COND_MAX_LABELS`` groups, or labels over all the groups."""
+    eng, sp = fits[0].eng, fits[0].sp
+    t, lib = eng.torch, eng.lib
+    refine = check_refine(refine)
+    pk = _refine_pack(fits)
+    k, G, Dc = int(k), len(fits), sum(pk.n_cont)
+    ptrs = [None] * 4
+    if trace is not None:
+        for name, cols, dtype in (("J_start", G, t.float64), ("J_end", G, t.float64),
+                                  ("g_end", Dc, t.float64), ("accepted", G, t.int32)):
+            trace[name] = t.empty((max(k, 1), max(cols, 1)), dtype=dtype,
+                                  device=eng.device)[:k, :cols]
+        # (g_end's rows are sum D_c,g long in the call: a narrower view would not be)
+        if Dc == 0:
+            trace["g_end"] = t.empty((k, 0), dtype=t.float64, device=eng.device)
+        ptrs = [trace[name].data_ptr() for name in ("J_start", "J_end", "g_end", "accepted")]
+    _L.check(lib.tpe_joint_refine_tree(
+        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host),
+        None if pk.tables is None else pk.tables.data_ptr(), pk.n_tables, pk.groups.ctypes.data,
+        pk.groups_dev.data_ptr(), G, d_block.data_ptr(), d_active.data_ptr(), ld, n_cols, k,
+        refine, *ptrs, sp), "tpe_joint_refine_tree")
 
 
 def loo_device(eng, domain, hist, seen, gamma, n_cols, grid=None, prior_weight=1.0,

@@ -628,6 +628,8 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
             d.fits, d.above = fits, _above(eng, fits, P)
             _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above)
         elif joint["tree"]:
+            if st.refine_tree:  # (the fits stay, for the climb)
+                d.fits = fits
             _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S)
         else:
             if st.lie is not None:  # (log L_above of the born rows stays, for the batch)
@@ -1446,6 +1448,8 @@ BATCH_LIAR_TREE = ("batch='liar-tree' is supported with joint='tree' on a Pool o
 
 REFINE = ("refine= moves the picked rows' continuous always-live labels up the joint "
           "criterion: it needs joint=True (suggest_sampled, refine_configs)")
+REFINE_TREE = ("refine_tree= moves the picked rows' continuous labels up their groups' criteria: "
+               "it needs joint='tree' (suggest_sampled, refine_configs(joint='tree'))")
 
 
 class _Settings(object):
@@ -1454,18 +1458,20 @@ class _Settings(object):
     ``lie`` (None, or the lie's weight of ``batch="liar"`` / ``"liar-tree"``),
     ``lie_tree`` (the lie is ``"liar-tree"``'s: one per group, joint.py "Batches
     in a tree") and ``refine`` (the steps the picked rows climb, joint.py
-    "Refining"; 0: none)."""
-    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine", "lie_tree")
+    "Refining"; 0: none) and ``refine_tree`` (the steps they climb per live
+    group, joint.py "Refining in a tree"; 0: none)."""
+    __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine", "lie_tree",
+                 "refine_tree")
 
     def __init__(self, prior_weight, gamma, lf, joint=None, lie=None, refine=0):
         self.prior_weight, self.gamma, self.lf, self.joint, self.lie, self.refine = \
             prior_weight, gamma, lf, joint, lie, refine
-        self.lie_tree = False
+        self.lie_tree, self.refine_tree = False, 0
 
 
 def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
               cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, pool=None,
-              refine=None, domain=None):
+              refine=None, domain=None, refine_tree=None):
     """The ``_Settings`` of a public call's keywords, after the checks:
     ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
     ``"liar"`` (needs ``joint=True``) and ``"liar-tree"`` (needs
@@ -1473,13 +1479,30 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
     what the batch is not built for (joint.py, "Not built"; ``pool``: the
     call's pool, where it has one; ``domain``: the call's space, for the keys of
     a ``bandwidth`` mapping).  A ``refine`` that is not None: ValueError
-    unless it is an integer >= 0 and ``joint`` is ``True``."""
+    unless it is an integer >= 0 and ``joint`` is ``True``.  A ``refine_tree``
+    that is not None: the same with ``joint="tree"``, and ValueError beside a
+    non-zero ``refine``."""
     st = _Settings(prior_weight, gamma, lf, _joint_kw(joint, bandwidth, cat_smoothing, domain))
+    if refine and refine_tree and _J.check_refine(refine) and refine_tree is not True:
+        raise ValueError(REFINE_TREE + "; refine= is joint=True's climb: pass one of the two")
     if refine is not None:
         st.refine = _J.check_refine(refine)
         if st.joint is None or st.joint["tree"]:
             raise ValueError(REFINE + "; the groups of joint='tree' / 'chain' and the "
-                             "factorised criterion (joint=False) are not refined")
+                             "factorised criterion (joint=False) are not refined"
+                             " (under joint='tree': refine_tree=N)")
+    if refine_tree is not None:
+        try:
+            st.refine_tree = _J.check_refine(refine_tree)
+        except ValueError:
+            raise ValueError("refine_tree=%r: None or an integer >= 0" % (refine_tree,))
+        if st.joint is None or st.joint["tree"] is not True:
+            raise ValueError(REFINE_TREE + (
+                "; under joint='chain' the groups are coupled through their contexts"
+                if st.joint is not None and st.joint["tree"] == "chain" else
+                "; with joint=True the climb is refine=N"))
+        if isinstance(pool, GridPool):
+            raise ValueError(REFINE_TREE + "; a GridPool has no row values to move")
     if batch is None:
         return st
     if batch not in ("liar", "liar-tree"):
@@ -1680,7 +1703,8 @@ def startup_rows(pool, seed, k, stale=None):
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0,
                       n_startup_jobs=20, gamma=0.25, linear_forgetting=25, verbose=True,
                       distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
-                      cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, refine=None):
+                      cat_smoothing=_J.CAT_SMOOTHING, batch=None, lie_weight=1.0, refine=None,
+                      refine_tree=None):
     """An ``algo`` for fmin (``partial(tpe.suggest_from_pool, pool=pool)``): one
     document per id, the first id the best untaken row of ``pool`` by
     ``score_configs``, the second the next best, and so on -- larger S first,
@@ -1722,9 +1746,9 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     ``switch`` alone are told apart (joint.py, "Batches in a tree").  On a flat
     space it is ``batch="liar"`` with ``joint=True``, bit for bit.
 
-    ``refine``: anything but None raises ValueError -- a fixed pool's rows are
-    a closed set, and a ``GridPool`` has no row to move
-    (``suggest_sampled(refine=N)``, ``refine_configs``)."""
+    ``refine`` / ``refine_tree``: anything but None raises ValueError -- a fixed
+    pool's rows are a closed set, and a ``GridPool`` has no row to move
+    (``suggest_sampled(refine=N)`` / ``(refine_tree=N)``, ``refine_configs``)."""
     from . import tpe as T
     if pool is None:
         raise TypeError("suggest_from_pool needs pool= (functools.partial)")
@@ -1732,6 +1756,10 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
         raise ValueError(REFINE + ("; a GridPool has no row values to move"
                                    if isinstance(pool, GridPool) else
                                    "; a fixed pool's rows are a closed set"))
+    if refine_tree is not None:
+        raise ValueError(REFINE_TREE + ("; a GridPool has no row values to move"
+                                        if isinstance(pool, GridPool) else
+                                        "; a fixed pool's rows are a closed set"))
     if distinct and isinstance(pool, GridPool):
         raise ValueError(GRID_DISTINCT)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
@@ -1811,19 +1839,27 @@ def take_rows(pool, rows_dev, k):
     return vals, active
 
 
-def _refine_rows(eng, d, k, refine):
+def _refine_rows(eng, d, k, refine, tree=False):
     """Rows ``d.rows_out[:k]`` of the mirror ``d`` climb J under the fit the
     scoring left in ``d.fits`` (``joint.refine_device``): gathered into a
     label-major block of k rows, refined there, and put back into the mirror's
-    values, where ``take_rows`` finds them.  Nothing is read back."""
+    values, where ``take_rows`` finds them.  Nothing is read back.  ``tree``:
+    every row climbs its live groups' J_g under the tree fits
+    (``joint.refine_tree_device``), with the rows' activity bytes gathered
+    beside them."""
     idx = d.rows_out[:k]
     block = d.vals.index_select(1, idx)
-    _J.refine_device(d.fits[0], block, k, d.vals.shape[0], k, refine)
+    if tree:
+        _J.refine_tree_device(d.fits, block, d.active.index_select(1, idx), k, d.vals.shape[0],
+                              k, refine)
+    else:
+        _J.refine_device(d.fits[0], block, k, d.vals.shape[0], k, refine)
     d.vals.index_copy_(1, idx, block)
 
 
 def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weight=1.0, gamma=0.25,
-                   linear_forgetting=25, bandwidth=_J.BANDWIDTH, cat_smoothing=_J.CAT_SMOOTHING):
+                   linear_forgetting=25, bandwidth=_J.BANDWIDTH, cat_smoothing=_J.CAT_SMOOTHING,
+                   joint=True):
     """The configurations ``vals`` -- (P, L) stored values in ``domain.params``
     column order, NaN where a label is not live, as ``Pool.vals`` holds them --
     after at most ``refine`` steps up the joint criterion of ``trials``
@@ -1837,11 +1873,23 @@ def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weigh
     the climb's own J is internal), the steps each row kept, and the gradient
     (P, D_c) in the fit coordinates at the point it ended on.
 
+    ``joint="tree"``: every row climbs, per group live in it, that group's J_g
+    on the group's continuous labels (joint.py, "Refining in a tree"; the fits
+    of ``joint="tree"``).  The trace then has J_before and J_after (P, G) from
+    ``score_configs(joint="tree")``'s per-group parts, accepted (P, G) and g_end
+    (P, sum of D_c,g), NaN / 0 where a group is not live.  On a flat space the
+    refined values are ``joint=True``'s, bit for bit.
+
     ValueError: a space without an always-live label, more than
-    ``TPE_REFINE_MAX_CONT`` continuous ones, a ``refine`` that is not an
-    integer >= 0."""
+    ``TPE_REFINE_MAX_CONT`` continuous ones (per group), a ``refine`` that is
+    not an integer >= 0, a ``joint`` that is neither ``True`` nor ``"tree"``."""
     from . import tpe as T
     domain = as_domain(domain)
+    if isinstance(joint, str) and joint == "tree":
+        return _refine_configs_tree(domain, trials, vals, refine, return_trace, prior_weight,
+                                    gamma, linear_forgetting, bandwidth, cat_smoothing)
+    if joint is not True:
+        raise ValueError("refine_configs: joint=True or joint='tree' (joint=%r)" % (joint,))
     st = _settings(prior_weight, gamma, linear_forgetting, True, bandwidth, cat_smoothing,
                    refine=0 if refine is None else refine, domain=domain)
     labels = list(domain.params)
@@ -1873,6 +1921,47 @@ def refine_configs(domain, trials, vals, refine, return_trace=False, prior_weigh
         return vals
     J = J.cpu().numpy()
     return (vals, J[0], J[1], trace["accepted"].cpu().numpy(), trace["g_end"].cpu().numpy())
+
+
+def _refine_configs_tree(domain, trials, vals, refine, return_trace, prior_weight, gamma,
+                         linear_forgetting, bandwidth, cat_smoothing):
+    """``refine_configs(joint="tree")``."""
+    from . import tpe as T
+    st = _settings(prior_weight, gamma, linear_forgetting, "tree", bandwidth, cat_smoothing,
+                   domain=domain, refine_tree=0 if refine is None else refine)
+    labels = list(domain.params)
+    groups = [_J.label_models(domain, grp.labels) for grp in _J.joint_groups(domain)]
+    cont = [[models[i] for i in _J.moving_labels(models)] for models in groups]
+    _J.check_tree_limits(groups)
+    G, Dc = len(groups), sum(len(c) for c in cont)
+    vals = np.array(vals, dtype=np.float64, ndmin=2)
+    pool = Pool.from_arrays(domain, vals, ~np.isnan(vals))
+    P, L = vals.shape
+    if P == 0:
+        return (vals, np.zeros((0, G)), np.zeros((0, G)), np.zeros((0, G), np.int32),
+                np.zeros((0, Dc))) if return_trace else vals
+    hist = T.collect_history(trials, labels)
+    eng = T.engine()
+    t = eng.torch
+    d = pool.device(eng)
+    ld = d.vals.shape[1]
+    fits = _fit(eng, domain, hist, L, st)
+    trace = {} if return_trace else None
+    if return_trace:
+        S = t.empty(P, dtype=t.float64, device=eng.device)
+        J = [_parts(eng, domain, st, P) for _ in range(2)]
+        _J.score_tree_device(fits, d.vals, d.active, ld, L, P, S, J[0])
+    _J.refine_tree_device(fits, d.vals, d.active, ld, L, P, st.refine_tree, trace)
+    if return_trace:
+        _J.score_tree_device(fits, d.vals, d.active, ld, L, P, S, J[1])
+    for m in [m for c in cont for m in c]:  # (continuous labels carry no offset)
+        live = ~np.isnan(vals[:, m.col])
+        vals[live, m.col] = d.vals[m.col, :P].cpu().numpy()[live]
+    if not return_trace:
+        return vals
+    return (vals, np.ascontiguousarray(J[0][:, :P].cpu().numpy().T),
+            np.ascontiguousarray(J[1][:, :P].cpu().numpy().T), trace["accepted"].cpu().numpy(),
+            trace["g_end"].cpu().numpy())
 
 
 def joint_bandwidth(domain, trials, grid=None, joint=True, prior_weight=1.0, gamma=0.25,
@@ -1932,7 +2021,7 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
                     prior_weight=1.0, n_startup_jobs=20, gamma=0.25, linear_forgetting=25,
                     verbose=True, distinct=False, joint=False, bandwidth=_J.BANDWIDTH,
                     cat_smoothing=_J.CAT_SMOOTHING, draw="factorised", batch=None,
-                    lie_weight=1.0, refine=None):
+                    lie_weight=1.0, refine=None, refine_tree=None):
     """An ``algo`` for fmin on any space: one document per id, k distinct
     points from one history (``max_queue_len=k``, asynchronous backends).
 
@@ -2001,7 +2090,18 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     ``refine_configs``): the documents carry the refined values, their
     quantized and discrete labels and every label under a ``switch`` those of
     the picked rows.  ``keep`` and ``distinct`` judge the rows as drawn.
-    ``refine=None`` or 0: the rows as they fell."""
+    ``refine=None`` or 0: the rows as they fell.
+
+    ``refine_tree=N`` (needs ``joint="tree"``; ValueError otherwise -- under
+    ``"chain"`` the groups are coupled through their contexts --, beside a
+    non-zero ``refine``, and for anything but an integer >= 0): the same climb
+    inside the branches.  After the k rows are picked (plain or
+    ``batch="liar-tree"``, either ``draw``) every row climbs, per group live in
+    it, that group's J_g on the group's continuous labels for at most N steps
+    (joint.py, "Refining in a tree"; ``refine_configs(joint="tree")``): the
+    sum of the J_g never falls, the selectors and every quantized or discrete
+    label stay, and labels not live in a row are not touched.
+    ``refine_tree=None`` or 0: the rows as they fell."""
     from . import rand
     from . import tpe as T
     t0 = time.time()
@@ -2012,11 +2112,16 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
                          "joint=True")
     domain = as_domain(domain)
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
-                   lie_weight, refine=refine, domain=domain)
+                   lie_weight, refine=refine, domain=domain, refine_tree=refine_tree)
     if st.joint is not None:
         _joint_cols(domain, st.joint)  # (ValueError on a space without a joint label)
     if st.refine:  # (ValueError over the kernel's limit of continuous labels)
         _J.moving_labels(_J.label_models(domain))
+    if st.refine_tree:  # (ValueError over the kernel's limits, per group and in all)
+        groups = [_J.label_models(domain, grp.labels) for grp in _J.joint_groups(domain)]
+        for models in groups:
+            _J.moving_labels(models)
+        _J.check_tree_limits(groups)
     labels = list(domain.params)
     n = max(int(n_EI_candidates), 0)
     hist = T.collect_history(trials, labels)
@@ -2054,6 +2159,8 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
         return []
     if st.refine:
         _refine_rows(eng, d, len(rows), st.refine)
+    if st.refine_tree:
+        _refine_rows(eng, d, len(rows), st.refine_tree, tree=True)
     vals, active = take_rows(pool, d.rows_out, len(rows))
     pool.mark_taken(rows)
     configs = [_stored_config(domain, labels, vals[i], active[i]) for i in range(len(rows))]

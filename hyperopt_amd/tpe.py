@@ -51,7 +51,10 @@ it is about to become, so a batch for parallel evaluation spreads out
 every group of labels it is live in (``joint_liar_tree_numpy``).
 ``suggest_sampled(joint=True, refine=N)`` lets the picked rows climb the joint
 criterion on their continuous labels, on the device (``refine_configs``: any
-rows; ``joint_refine_numpy``).  ``bandwidth="loo"`` (with ``joint=True`` /
+rows; ``joint_refine_numpy``); ``suggest_sampled(joint="tree", refine_tree=N)``
+is that climb inside the branches: every picked row climbs, per group of labels
+live in it, the group's own J_g (``refine_configs(joint="tree")``;
+``joint_refine_tree_numpy``).  ``bandwidth="loo"`` (with ``joint=True`` /
 ``"tree"``) fits the joint mixtures' bandwidth multiplier by leave-one-out
 likelihood on the device, once per call (``joint_bandwidth``: the float and its
 curves; ``joint_loo_numpy``); ``bandwidth="loo-label"`` one multiplier per
@@ -818,4 +821,6 @@ from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     liar_tree_numpy as joint_liar_tree_numpy,
                     loo_label_fit_numpy as joint_loo_label_fit_numpy,
                     loo_label_numpy as joint_loo_label_numpy, loo_numpy as joint_loo_numpy,
-                    refine_numpy as joint_refine_numpy, score_numpy as joint_score_numpy)
+                    refine_numpy as joint_refine_numpy,
+                    refine_tree_numpy as joint_refine_tree_numpy,
+                    score_numpy as joint_score_numpy)

@@ -1223,6 +1223,64 @@ int tpe_joint_refine(const tpe_joint_label* host_labels, const tpe_joint_label* 
 /* host: TPE_REFINE_MAX_CONT as the library was built */
 int tpe_joint_refine_max_cont(void);
 
+/* ---- rows that climb their groups under joint="tree" -----------------------------
+ * (tpe.suggest_sampled(joint="tree", refine_tree=N), tpe.refine_configs(joint="tree");
+ * hyperopt_amd/joint.py, "Refining in a tree".)  S = sum_g J_g over disjoint label
+ * groups, so the climb above runs once per (row, group live in the row), each with
+ * its group's two prepared sets, gradient, bandwidths, h, decisions and stop.
+ *
+ * `labels` are the groups' label records one after the other (n_labels in all);
+ * group g is records [first, first + count), prepared as a tpe_joint_score label
+ * list of `count` labels: its sets hold `count` labels, a TPE_JOINT_CAT record's
+ * tab_off counts from tables + tab_off of the group.  live_col: the column whose
+ * `active` byte (label-major, leading dimension ld, as `vals`) says the group is
+ * live in a row; -1: live everywhere (the root).  n_cont: its TPE_JOINT_CONT
+ * labels; g_off: the sum of n_cont over the groups before it.  The record list
+ * goes in twice, on the host (checked before any launch) and on the device (a
+ * block reads its own record: 128 of them do not fit a kernel's arguments).
+ *
+ * Outputs, each optional: J_start, J_end (n_rows x n_groups, row-major),
+ * accepted (n_rows x n_groups), g_end (n_rows x sum of n_cont; a group's entries
+ * at g_off).  A pair whose group is not live in the row gets NaN / NaN / 0 / NaN
+ * and nothing else of it is read or written: the outputs need no memset.  A
+ * group without a TPE_JOINT_CONT label is launched only where J_start, J_end or
+ * accepted is wanted.
+ *
+ * One block per (row, group), blockIdx.y over the groups of one instantiation
+ * (D_c <= 4 / 8 / 16): at most three launches.  A block copies a set of C = n + 1
+ * components into LDS -- log w and the group's JComp rows -- and walks it there
+ * for all `refine` + 1 evaluations: the below set when C <= 26, the above set
+ * when C <= tpe_joint_refine_tree_stage_components(count); any other set is
+ * streamed as tpe_joint_refine streams it.  Staged, streamed and tpe_joint_refine
+ * itself give the same bits: on one group with live_col = -1 the results are
+ * tpe_joint_refine's.  The set buffers are 16-byte aligned.
+ *
+ * Limits: n_groups and n_labels <= TPE_COND_MAX_LABELS and n_cont <=
+ * TPE_REFINE_MAX_CONT per group, else TPE_E_UNSUPPORTED; bad arguments return
+ * TPE_E_ARG before any launch.  No atomics; a pair's bits depend on the row, the
+ * group's sets and `refine` alone.  Asynchronous on `stream`, no allocation. */
+typedef struct tpe_refine_group {
+  int32_t first, count;  /* its label records */
+  int32_t live_col;      /* -1: live in every row */
+  int32_t n_cont, g_off; /* its moving labels, and where they start in a row of g_end */
+  int32_t pad_;
+  int64_t tab_off;       /* added to its labels' tab_off */
+  int64_t n_below, n_above;
+  const double* set_below;
+  const double* set_above;
+} tpe_refine_group;
+int tpe_joint_refine_tree(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
+                          int n_labels, const double* tables, int64_t n_tables,
+                          const tpe_refine_group* host_groups, const tpe_refine_group* groups,
+                          int n_groups, double* vals, const uint8_t* active, int64_t ld,
+                          int n_cols, int64_t n_rows, int refine, double* J_start, double* J_end,
+                          double* g_end, int32_t* accepted, void* stream);
+/* host: the largest C = n + 1 at which the above set of a group of n_labels labels
+ * is staged (0: never); -1 for n_labels outside [1, TPE_COND_MAX_LABELS] */
+int64_t tpe_joint_refine_tree_stage_components(int n_labels);
+/* host: sizeof(tpe_refine_group) as the library was built */
+int tpe_joint_refine_tree_group_bytes(void);
+
 /* ---- a set's leave-one-out log-likelihood over a grid of bandwidths -------------
  * (tpe.joint_bandwidth, bandwidth="loo"; hyperopt_amd/joint.py, "Bandwidth".)
  * The set is rows[0 .. n) of a label-major history, read as tpe_joint_prep reads
