@@ -221,6 +221,8 @@ _SIGNATURES = {
     "tpe_joint_chain_scratch_bytes": (_I64, [_I64, _I64]),
     "tpe_joint_chain_rows": (_I, [_P, _P, _I, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64,
                                   _I64, _P, _P, _I, _P, _P]),
+    "tpe_joint_chain_rows_keep": (_I, [_P, _P, _I, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P,
+                                       _I64, _I64, _P, _P, _I, _P, _P, _I64, _P, _P]),
     "tpe_joint_lie_scratch_bytes": (_I64, [_I64]),
     "tpe_joint_lie_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _I64, _I, _I64, _P, _P,
                                  ctypes.c_double, ctypes.c_double, _P, _P, _I64, _P, _P, _P, _P,
@@ -229,6 +231,10 @@ _SIGNATURES = {
     "tpe_joint_lie_tree_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _P, _I, _P, _P, _P, _I64, _I,
                                       _I64, _P, _P, _I64, ctypes.c_double, _P, _P, _I64, _P, _P,
                                       _P, _P, _P, _P]),
+    "tpe_joint_lie_chain_scratch_bytes": (_I64, [_I64, _I, _I]),
+    "tpe_joint_lie_chain_picks": (_I, [_P, _P, _I, _P, _I64, _P, _P, _P, _P, _I, _P, _P, _P, _I64,
+                                       _I, _I64, _P, _P, _I64, _P, _I64, ctypes.c_double, _P, _P,
+                                       _I64, _P, _P, _P, _P, _P, _P]),
     "tpe_rows_scatter": (_I, [_P, _P, _P, _I64, _I64, _P, _I64, _P]),
     "tpe_joint_refine": (_I, [_P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _I64, _I,
                               _P, _P, _P, _P, _P]),

@@ -69,11 +69,13 @@ __global__ __launch_bounds__(kJBS) void k_joint_chain_rows(
 }
 
 // both values by tpe_joint_pass.hpp's merge; (log L - log L_ctx) - sub[r] to
-// out[r], out[row] or added to out[row]
+// out[r], out[row] or added to out[row]; the two values themselves to
+// keep_full[row] / keep_ctx[row] where given (row < keep_ld)
 __global__ __launch_bounds__(kJBS) void k_joint_chain_merge(
     const double2* __restrict__ parts, int64_t n_chunks, int64_t ld,
     const int64_t* __restrict__ rows, const int64_t* __restrict__ d_count, int64_t list_begin,
-    int64_t max_rows, const double* __restrict__ sub, double* __restrict__ out, int out_mode) {
+    int64_t max_rows, const double* __restrict__ sub, double* __restrict__ out, int out_mode,
+    double* __restrict__ keep_full, double* __restrict__ keep_ctx, int64_t keep_ld) {
   const int64_t r = (int64_t)blockIdx.x * kJBS + threadIdx.x;
   if (r >= chain_window_rows(d_count, list_begin, max_rows)) return;
   const int64_t row = rows[list_begin + r];
@@ -91,6 +93,10 @@ __global__ __launch_bounds__(kJBS) void k_joint_chain_merge(
 #define TPE_JOINT_PASS_MERGE
 #include "tpe_joint_pass.hpp"
     v_ctx = v;
+  }
+  if (row < keep_ld) {
+    if (keep_full) keep_full[row] = v_full;
+    if (keep_ctx) keep_ctx[row] = v_ctx;
   }
   double v = v_full - v_ctx;
   if (sub) v = v - sub[r];
@@ -111,16 +117,19 @@ extern "C" int64_t tpe_joint_chain_scratch_bytes(int64_t n_rows, int64_t n) {
   return 2 * (int64_t)sizeof(double2) * n_rows * chain_chunks(n);
 }
 
-extern "C" int tpe_joint_chain_rows(const tpe_joint_label* host_labels,
-                                    const tpe_joint_label* labels, int n_labels, int n_ctx,
-                                    const double* tables, int64_t n_tables, const double* set,
-                                    int64_t n, const double* vals, int64_t ld, int n_cols,
-                                    const int64_t* rows, const int64_t* d_count,
-                                    int64_t list_begin, int64_t max_rows, const double* sub,
-                                    double* out, int out_mode, void* scratch, void* stream) {
+extern "C" int tpe_joint_chain_rows_keep(
+    const tpe_joint_label* host_labels, const tpe_joint_label* labels, int n_labels, int n_ctx,
+    const double* tables, int64_t n_tables, const double* set, int64_t n, const double* vals,
+    int64_t ld, int n_cols, const int64_t* rows, const int64_t* d_count, int64_t list_begin,
+    int64_t max_rows, const double* sub, double* out, int out_mode, double* keep_full,
+    double* keep_ctx, int64_t keep_ld, void* scratch, void* stream) {
   const int rc = check_joint_labels("tpe_joint_chain_rows", host_labels, n_labels, n_cols,
                                     n_tables < 0 ? 0 : n_tables);
   if (rc != TPE_OK) return rc;
+  if ((keep_full || keep_ctx) && keep_ld < 0) {
+    set_error("tpe_joint_chain_rows_keep: keep_ld=%lld", (long long)keep_ld);
+    return TPE_E_ARG;
+  }
   if (n_ctx <= 0 || n_ctx >= n_labels) {
     set_error("tpe_joint_chain_rows: n_ctx=%d of %d labels", n_ctx, n_labels);
     return TPE_E_ARG;
@@ -156,6 +165,19 @@ extern "C" int tpe_joint_chain_rows(const tpe_joint_label* host_labels,
                      st, labels, n_labels, n_ctx, tables, set, n, vals, ld, rows, d_count,
                      list_begin, max_rows, partial);
   hipLaunchKernelGGL(k_joint_chain_merge, dim3((unsigned)blocks), dim3(kJBS), 0, st, partial,
-                     chunks, ld, rows, d_count, list_begin, max_rows, sub, out, out_mode);
+                     chunks, ld, rows, d_count, list_begin, max_rows, sub, out, out_mode,
+                     keep_full, keep_ctx, keep_full || keep_ctx ? keep_ld : 0);
   return check_launch("tpe_joint_chain_rows");
+}
+
+extern "C" int tpe_joint_chain_rows(const tpe_joint_label* host_labels,
+                                    const tpe_joint_label* labels, int n_labels, int n_ctx,
+                                    const double* tables, int64_t n_tables, const double* set,
+                                    int64_t n, const double* vals, int64_t ld, int n_cols,
+                                    const int64_t* rows, const int64_t* d_count,
+                                    int64_t list_begin, int64_t max_rows, const double* sub,
+                                    double* out, int out_mode, void* scratch, void* stream) {
+  return tpe_joint_chain_rows_keep(host_labels, labels, n_labels, n_ctx, tables, n_tables, set, n,
+                                   vals, ld, n_cols, rows, d_count, list_begin, max_rows, sub, out,
+                                   out_mode, nullptr, nullptr, 0, scratch, stream);
 }

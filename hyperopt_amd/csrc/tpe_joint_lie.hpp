@@ -1,8 +1,10 @@
-// tpe_joint_lie.hpp -- what the two liar batches share (tpe_joint_lie.hip: one
-// lie per pick over the always-live labels; tpe_joint_lie_tree.hip: one lie per
-// group the pick is live in): the control word a pick's row travels in, the
-// exact (key, row) minimum of a block, and the one-block kernel that turns the
-// blocks' bests into the pick.
+// tpe_joint_lie.hpp -- what the liar batches share (tpe_joint_lie.hip: one lie
+// per pick over the always-live labels; tpe_joint_lie_tree.hip: one lie per
+// group the pick is live in; tpe_joint_lie_chain.hip: one per chain fit, in its
+// mixture and its context marginal): the control word a pick's row travels in,
+// the exact (key, row) minimum of a block, the one-block kernel that turns the
+// blocks' bests into the pick, and the factor of one record under a pick
+// (the tree's and the chain's walks).
 #pragma once
 
 #include "tpe_joint.hpp"
@@ -64,6 +66,38 @@ __global__ __launch_bounds__(kJBS) void k_lie_final(const LieBest* __restrict__ 
       *out_count = j + 1;
     }
   }
+}
+
+// log k_d of the stored value x under the pick's pair t: the factor
+// expressions of tpe_joint_pass.hpp for one trial component, as k_lie_update
+// has them.  sig is read for a label with a bandwidth only: it may be NULL
+// when every label is discrete.
+__device__ __forceinline__ double lie_factor(const tpe_joint_label& lab, double x, const JComp t,
+                                             const double* __restrict__ sig, int d, int n_labels,
+                                             const double* __restrict__ tables) {
+  if (lab.kind == TPE_JOINT_CONT) {
+    const double tx = fit_coord(x, (lab.flags & TPE_JOINT_LOG) != 0);
+    const double u = (tx - t.mu) * sig[n_labels + d];
+    return fma(-u, u, t.cst);
+  }
+  if (lab.kind == TPE_JOINT_QUANT) {
+    const bool is_log = (lab.flags & TPE_JOINT_LOG) != 0;
+    const bool bounded = (lab.flags & TPE_JOINT_BOUNDED) != 0;
+    const double lb = x - 0.5 * lab.q;
+    double tu = fit_coord(x + 0.5 * lab.q, is_log), tl = fit_coord(lb, is_log);
+    if (bounded) {
+      tu = fmin(fmax(tu, lab.lo), lab.hi);
+      tl = fmin(fmax(tl, lab.lo), lab.hi);
+    } else if (is_log && lb <= 0.0) {
+      tl = kNegInf;  // normal_cdf(-inf) is exactly 0
+    }
+    return log_mass(tu, tl, t.mu, sig[d]) + t.cst;
+  }
+  const int64_t q = llrint(x);
+  const bool in = q >= 0 && q < lab.n_cat;  // (a validated pool: always)
+  const double* __restrict__ tab = tables + lab.tab_off + (in ? q : 0);
+  const double hit = in ? tab[0] : kNegInf, miss = in ? tab[lab.n_cat] : kNegInf;
+  return t.mu == (double)q ? hit : miss;
 }
 
 static_assert(sizeof(LieBest) == 16 && sizeof(LieCtl) == 16, "the scratch stays 16-byte aligned");

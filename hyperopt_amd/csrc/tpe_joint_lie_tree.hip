@@ -87,38 +87,6 @@ __global__ __launch_bounds__(kJBS) void k_lie_tree_init(
   }
 }
 
-// log k_d of the stored value x under the pick's pair t: the factor
-// expressions of tpe_joint_pass.hpp for one trial component, as k_lie_update
-// has them.  sig is read for a label with a bandwidth only: it may be NULL
-// when every label is discrete.
-__device__ __forceinline__ double lie_factor(const tpe_joint_label& lab, double x, const JComp t,
-                                             const double* __restrict__ sig, int d, int n_labels,
-                                             const double* __restrict__ tables) {
-  if (lab.kind == TPE_JOINT_CONT) {
-    const double tx = fit_coord(x, (lab.flags & TPE_JOINT_LOG) != 0);
-    const double u = (tx - t.mu) * sig[n_labels + d];
-    return fma(-u, u, t.cst);
-  }
-  if (lab.kind == TPE_JOINT_QUANT) {
-    const bool is_log = (lab.flags & TPE_JOINT_LOG) != 0;
-    const bool bounded = (lab.flags & TPE_JOINT_BOUNDED) != 0;
-    const double lb = x - 0.5 * lab.q;
-    double tu = fit_coord(x + 0.5 * lab.q, is_log), tl = fit_coord(lb, is_log);
-    if (bounded) {
-      tu = fmin(fmax(tu, lab.lo), lab.hi);
-      tl = fmin(fmax(tl, lab.lo), lab.hi);
-    } else if (is_log && lb <= 0.0) {
-      tl = kNegInf;  // normal_cdf(-inf) is exactly 0
-    }
-    return log_mass(tu, tl, t.mu, sig[d]) + t.cst;
-  }
-  const int64_t q = llrint(x);
-  const bool in = q >= 0 && q < lab.n_cat;  // (a validated pool: always)
-  const double* __restrict__ tab = tables + lab.tab_off + (in ? q : 0);
-  const double hit = in ? tab[0] : kNegInf, miss = in ? tab[lab.n_cat] : kNegInf;
-  return t.mu == (double)q ? hit : miss;
-}
-
 __global__ __launch_bounds__(kJBS) void k_lie_tree_update(
     const LieGroups grp, const tpe_joint_label* __restrict__ labels, int n_labels,
     const double* __restrict__ tables, const double* __restrict__ sig,

@@ -420,12 +420,69 @@ dense temporary is copied to its rows by tpe_rows_scatter: the above set is not
 scored twice and the list's length stays on the device), and
 ``liar_tree_device`` enqueues all k picks in one tpe_joint_lie_tree_picks.
 
+Batches in a chain (``joint="chain"``, ``batch="liar-chain"``,
+csrc/tpe_joint_lie_chain.hip).  C_g is a ratio, but of one
+mixture: a pending trial joins the above mixture of every chain fit it is live
+in, and that mixture's context marginal is the same mixture with g's factors
+dropped -- so the lie joins numerator and denominator, and one walk over the
+fit's labels gives both contributions.
+
+  groups       g = 0 .. G - 1 and their fits are those of ``fit(...,
+               tree="chain")``: fit g covers the labels ``ctx(g) + g``, the
+               ``n_ctx`` context labels first; the root has ``n_ctx = 0``, and so
+               has any group with an empty context.  The root is live in every
+               row, group g > 0 where the ``active`` byte of its first own label
+               (``models[n_ctx]``) is set -- the rule ``score_tree_device``
+               compacts on.  Where g is live, all of ctx(g) is (the definition
+               of a context).
+  inputs       ``S_0[r]``, the ``joint="chain"`` score, bits unchanged; ``A_g[r] =
+               log L_above`` of fit g at row r for every (g, r) with g live in r,
+               and ``B_g[r] = log L_ctx,above`` for the fits with ``n_ctx > 0``:
+               the two values whose difference the chain scoring subtracts.  Per
+               fit: n_g the size of its prepared above set, ``sig_g =
+               lie_sigma(models_g, n_g, bandwidth)`` over all of ``ctx + g``,
+               ``log W_g = lie_log_total(n_g, lf, prior_weight)``.
+  lie          pick p lies in every g live in row p.  The walk runs over fit g's
+               labels in list order from ``log(lie_weight)`` and adds ``log
+               k_d(r_d)``, the "Factors" entry of a trial component whose
+               observation is row p's stored value, with ``sig_g`` -- the
+               expressions of "Batches".  The sum after the first ``n_ctx`` labels
+               is ``c^ctx_{g,p}(r)``, the sum after all of them ``c_{g,p}(r)``.
+  update       ``U_{g,0} = log W_g + A_g``, ``V_{g,0} = log W_g + B_g``.  After
+               pick j, for every g live in both p_j and r, U joins ``c`` and V
+               joins ``c^ctx`` by the "Batches" rule (the running term first; m =
+               -inf gives -inf; c = -inf leaves the bits).  Every other (g, r)
+               keeps its bits.
+  score        s = ``S_0[r]``; then, in group order over the groups live in r: a
+               group with ``n_ctx = 0`` gives ``s = s - (U_j - U_0)`` where U_0 is
+               finite; one with ``n_ctx > 0`` gives ``s = s - ((U_j - U_0) - (V_j
+               - V_0))`` where U_0 and V_0 are both finite, in that order of
+               operations.  A group no pick has touched subtracts exactly 0.0; a
+               NaN ``S_0`` stays NaN.
+  picks        the order, the masks, ``distinct`` and the stop of "Batches".  k =
+               1 is the first row of the chain S, bit for bit; a space whose
+               groups all have empty contexts gives the rows, ``S_at_pick`` and
+               ``S_k`` of ``batch="liar-tree"``, and a flat space those of
+               ``batch="liar"``, bit for bit.
+
+A group's penalty under ``"chain"`` is the change of a *conditional* log density,
+and it may be negative: a row that shares the pick's context but lies far from it
+inside g gains, because the pending trial raises the marginal at that context
+more than the joint density there.  Over a row's groups the penalties sum to the
+change of the log of the chain-rule above density -- the object a pending trial
+in the history would change.
+
+``liar_chain_numpy`` is this definition in numpy.  ``score_tree_device(above=,
+above_ctx=)`` keeps A_g and B_g while it scores: a fit with a context writes both
+from the merge that forms them (tpe_joint_chain_rows_keep; no scatter launch, the
+above set is not scored twice), a fit without one fills ``above`` as under
+``"tree"``.  ``liar_chain_device`` enqueues all k picks in one
+tpe_joint_lie_chain_picks.
+
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
 on a ``GridPool`` (the factor tables hold one group's axes; a chain term needs
-the context's as well).  A batch under ``joint="chain"`` (C_g is a ratio: a lie
-would have to join numerator and denominator; ``batch="liar"`` itself keeps
-``joint=True``, and ``batch="liar-tree"`` ``joint="tree"``), on a ``GridPool`` (a
+the context's as well).  A batch on a ``GridPool`` (a
 grid has no row values to lie with) and under the factorised criterion (its
 adaptive bandwidths depend on the sorted neighbours: no component can be added
 without a refit).  ``refine`` / ``refine_tree`` under ``joint="chain"`` (a group's
@@ -819,9 +876,11 @@ def lie_log_total(n, lf, prior_weight):
     return math.log(forgetting_weights(n, lf).sum() + float(prior_weight))
 
 
-def _lie_component(models, x, p, sig, smoothing, log_lie):
-    """c_p(r) for every row r of ``x`` (P, D; stored values)."""
-    c = np.full(x.shape[0], log_lie)
+def _lie_component(models, x, p, sig, smoothing, log_lie, start=None):
+    """c_p(r) for every row r of ``x`` (P, D; stored values).  ``start``: the
+    running sums to go on from in place of ``log_lie`` (a chain fit's own labels
+    after its context's)."""
+    c = np.full(x.shape[0], log_lie) if start is None else start
     for d, m in enumerate(models):
         xd = x[:, d]
         if m.kind == _L.JOINT_CAT:
@@ -954,6 +1013,88 @@ def liar_tree_numpy(domain, hist, vals, k, active=None, taken=None, distinct=Non
                 fin = live[np.isfinite(U0[live, g])]
                 S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
     return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
+
+
+def _lie_join(u, c):
+    """``u`` joined with ``c`` by the "Batches" rule, elementwise."""
+    with np.errstate(all="ignore"):
+        m = np.where(c > u, c, u)
+        both = m + np.log(np.exp(u - m) + np.exp(c - m))
+        return np.where(c == -np.inf, u, np.where(m == -np.inf, -np.inf, both))
+
+
+def liar_chain_numpy(domain, hist, vals, k, active=None, taken=None, distinct=None,
+                     lie_weight=1.0, S0=None, A=None, B=None, prior_weight=1.0, gamma=0.25,
+                     linear_forgetting=25, bandwidth=BANDWIDTH, cat_smoothing=CAT_SMOOTHING,
+                     return_state=False):
+    """The batch of module doc "Batches in a chain" in numpy: (rows, S_at_pick,
+    S_k) as ``liar_numpy`` returns them.  ``vals`` / ``active`` as
+    ``liar_tree_numpy`` takes them.  ``S0`` (P,) / ``A`` / ``B`` (P, G; read where
+    the group is live, ``B`` where it has a context too): the chain score and the
+    fits' log L_above and log L_ctx,above to start from where the caller has
+    them; else ``score_numpy(tree="chain")``'s.  ``return_state``: also (U_0,
+    U_k, V_0, V_k), (P, G), NaN where nothing is kept."""
+    domain = as_domain(domain)
+    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
+        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
+    groups, contexts = joint_groups(domain), joint_contexts(domain)
+    vals = np.asarray(vals, np.float64)
+    active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
+    P, G = vals.shape[0], len(groups)
+    if S0 is None or A is None or B is None:
+        parts = score_numpy(domain, hist, vals, active, prior_weight, gamma, linear_forgetting,
+                            bandwidth, cat_smoothing, return_parts=True, tree="chain")
+        S0 = parts[0] if S0 is None else S0
+        A = parts[3] if A is None else A
+        B = parts[5] if B is None else B
+    S0 = np.asarray(S0, np.float64)
+    A, B = np.asarray(A, np.float64).reshape(P, G), np.asarray(B, np.float64).reshape(P, G)
+    isa = split_sets(hist, gamma)[1]
+    per, U0, V0 = [], np.full((P, G), np.nan), np.full((P, G), np.nan)
+    for g, (grp, ctx) in enumerate(zip(groups, contexts)):
+        models = label_models(domain, ctx + grp.labels)
+        cols = [m.col for m in models]
+        live = np.flatnonzero(active[:, cols[len(ctx)]]) if g else np.arange(P)
+        n = int(set_rows(hist, isa, cols).size)
+        per.append((models, len(ctx), live, vals[live][:, cols], lie_sigma(models, n, bandwidth)))
+        log_w = lie_log_total(n, linear_forgetting, prior_weight)
+        U0[live, g] = log_w + A[live, g]
+        if ctx:
+            V0[live, g] = log_w + B[live, g]
+    gone = np.zeros(P, bool)
+    for mask in (taken, distinct):
+        if mask is not None:
+            gone |= np.asarray(mask)[:P] != 0
+    U, V, S = U0.copy(), V0.copy(), S0.copy()
+    rows, at = [], []
+    log_lie = math.log(lie_weight)
+    for _ in range(min(max(int(k), 0), P)):
+        p = _first_row(S, gone)
+        if p < 0:
+            break
+        rows.append(p)
+        at.append(S[p])
+        gone[p] = True
+        S = S0.copy()
+        for g, (models, n_ctx, live, x, sig) in enumerate(per):
+            at_p = int(np.searchsorted(live, p))
+            with np.errstate(all="ignore"):
+                if at_p < live.size and live[at_p] == p:  # (g is live in the pick)
+                    c = _lie_component(models[:n_ctx], x[:, :n_ctx], at_p, sig[:n_ctx],
+                                       cat_smoothing, log_lie)
+                    if n_ctx:  # (the label boundary: c is c^ctx)
+                        V[live, g] = _lie_join(V[live, g], c)
+                    c = _lie_component(models[n_ctx:], x[:, n_ctx:], at_p, sig[n_ctx:],
+                                       cat_smoothing, log_lie, start=c)
+                    U[live, g] = _lie_join(U[live, g], c)
+                if n_ctx:
+                    fin = live[np.isfinite(U0[live, g]) & np.isfinite(V0[live, g])]
+                    S[fin] = S[fin] - ((U[fin, g] - U0[fin, g]) - (V[fin, g] - V0[fin, g]))
+                else:
+                    fin = live[np.isfinite(U0[live, g])]
+                    S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
+    out = (np.asarray(rows, np.int64), np.asarray(at, np.float64), S)
+    return out + (U0, U, V0, V) if return_state else out
 
 
 # -- refining (module doc, "Refining") -------------------------------------------
@@ -1607,13 +1748,16 @@ class _LiePack(object):
     """The groups of a tree fit as tpe_joint_lie_tree_picks takes them: the
     label records concatenated in group order (``tab_off`` counted from the
     start of the concatenated tables) on the host and on the device, the
-    tables, ``group_off``, log W_g, the liveness columns, and the sigmas."""
-    __slots__ = ("host", "dev", "tables", "n_tables", "off", "log_w", "col", "sigma")
+    tables, ``group_off``, log W_g, the liveness columns, and the sigmas.  Chain
+    fits (tpe_joint_lie_chain_picks) pack the same way: a fit's records are its
+    context's, then its own, ``n_ctx`` says how many lead, and the liveness column
+    is the first own label's."""
+    __slots__ = ("host", "dev", "tables", "n_tables", "off", "log_w", "col", "sigma", "n_ctx")
 
 
 def _lie_pack(fits):
-    """``_LiePack`` of ``fits`` (``fit(..., tree=True)``), made once per fit
-    list and kept on its first fit."""
+    """``_LiePack`` of ``fits`` (``fit(..., tree=True)`` or ``tree="chain"``),
+    made once per fit list and kept on its first fit."""
     if fits[0].lie_pack is not None:
         return fits[0].lie_pack
     eng = fits[0].eng
@@ -1637,7 +1781,8 @@ def _lie_pack(fits):
     pk.off = np.asarray(off, np.int32)
     pk.log_w = np.asarray([lie_log_total(f.sets[1][1], f.linear_forgetting, f.prior_weight)
                            for f in fits], np.float64)
-    pk.col = np.asarray([-1] + [f.dj.models[0].col for f in fits[1:]], np.int32)
+    pk.n_ctx = np.asarray([f.n_ctx for f in fits], np.int32)
+    pk.col = np.asarray([-1] + [f.dj.models[f.n_ctx].col for f in fits[1:]], np.int32)
     # (no label with a bandwidth: the call takes no sigmas)
     pk.sigma = t.from_numpy(np.concatenate(
         [sig, np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)])
@@ -1681,6 +1826,60 @@ def liar_tree_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, taken, distin
         out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
         None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp),
         "tpe_joint_lie_tree_picks")
+    got = out[:k + 1].cpu().numpy()
+    rows = got[:int(got[k])].copy()
+    if not trace:
+        return rows
+    return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
+
+
+def check_chain_lie_limits(groups, contexts):
+    """ValueError where ``batch="liar-chain"`` does not reach: more than
+    ``TPE_COND_MAX_LABELS`` groups, or records (every fit's context and own
+    labels) over all the fits."""
+    G, D_tot = len(groups), sum(len(c) + len(g) for g, c in zip(groups, contexts))
+    if G > _L.COND_MAX_LABELS or D_tot > _L.COND_MAX_LABELS:
+        raise ValueError("batch='liar-chain': %d groups of %d labels in all, their contexts "
+                         "counted once per group, at most %d of either"
+                         % (G, D_tot, _L.COND_MAX_LABELS))
+
+
+def liar_chain_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, B, taken, distinct, k,
+                      lie_weight, trace=False, rows_out=None):
+    """The batch of module doc "Batches in a chain" for rows [0, P) of the
+    label-major device pool ``d_vals`` / ``d_active``: ``liar_tree_device`` with
+    ``fits`` the chain fits (``fit(..., tree="chain")``) and ``A`` / ``B`` the (G,
+    >= P) device tensors ``score_tree_device(above=, above_ctx=)`` filled.  One
+    tpe_joint_lie_chain_picks, one readback.  ValueError past
+    ``TPE_COND_MAX_LABELS`` groups, or records over all the fits, before
+    anything is packed."""
+    eng, sp = fits[0].eng, fits[0].sp
+    t, lib = eng.torch, eng.lib
+    k = min(int(k), P)
+    if k <= 0 or P == 0:
+        none = np.zeros(0, np.int64)
+        return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
+    check_chain_lie_limits([f.dj.models[f.n_ctx:] for f in fits],
+                           [f.dj.models[:f.n_ctx] for f in fits])
+    pk = _lie_pack(fits)
+    G, n_v = len(fits), int((pk.n_ctx > 0).sum())
+    out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
+    scratch = t.empty(lib.tpe_joint_lie_chain_scratch_bytes(P, G, n_v), dtype=t.uint8,
+                      device=eng.device)
+    at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
+    S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
+    _L.check(lib.tpe_joint_lie_chain_picks(
+        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host),
+        None if pk.tables is None else pk.tables.data_ptr(), pk.n_tables, pk.off.ctypes.data,
+        pk.log_w.ctypes.data, pk.col.ctypes.data, pk.n_ctx.ctypes.data, G,
+        None if pk.sigma is None else pk.sigma.data_ptr(), d_vals.data_ptr(),
+        d_active.data_ptr(), ld, n_cols, P, S0.data_ptr(), A.data_ptr(), A.shape[1],
+        B.data_ptr() if n_v else None, B.shape[1] if n_v else 0,
+        math.log(lie_weight), taken.data_ptr(),
+        None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
+        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
+        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp),
+        "tpe_joint_lie_chain_picks")
     got = out[:k + 1].cpu().numpy()
     rows = got[:int(got[k])].copy()
     if not trace:
@@ -1913,7 +2112,8 @@ def sample_tree_device(fits, seed, d_vals, ld, n_cols, row_base, n_rows):
         sample_device(f, seed, d_vals, ld, n_cols, row_base, n_rows, comp_key=key)
 
 
-def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, above=None):
+def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, above=None,
+                      above_ctx=None):
     """S of ``joint="tree"`` for rows [0, P) of the label-major device pool
     ``d_vals`` / ``d_active`` (bytes; leading dimension ``ld``) under ``fits``
     (``fit(..., tree=True)``) into the device vector ``out``.  The root group
@@ -1937,7 +2137,14 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, ab
     = log L_above,g at the rows in which group g is live (module doc, "Batches
     in a tree"); its other places are not written.  Row 0 is the root's
     subtrahend itself; a group's dense temporary goes to its rows by one
-    tpe_rows_scatter per window.  None: exactly the calls above."""
+    tpe_rows_scatter per window.  None: exactly the calls above.
+
+    ``above_ctx`` (``tree="chain"`` fits, beside ``above``): a (G, >= P) device
+    tensor; a fit with a context leaves A_g = log L_above in ``above[g]`` and B_g =
+    log L_ctx,above in ``above_ctx[g]`` at its live rows (module doc, "Batches in
+    a chain") from the merge that forms them, tpe_joint_chain_rows_keep in
+    tpe_joint_chain_rows' place and no scatter; a fit without one fills
+    ``above[g]`` as above.  Both None: exactly the calls above."""
     eng = fits[0].eng
     t, lib = eng.torch, eng.lib
     if above is None:
@@ -1957,6 +2164,9 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, ab
     count = t.empty(1, dtype=t.int64, device=eng.device)
     cscratch = t.empty(lib.tpe_rows_compact_scratch_bytes(P), dtype=t.uint8, device=eng.device)
     both = _L.JOINT_OUT_SCATTER | _L.JOINT_OUT_ADD
+    # (the kept vectors' common length: no row past either is written)
+    keep_ld = min(m.shape[1] for m in (above, above_ctx) if m is not None) if above is not None \
+        else 0
     for g, f in enumerate(fits[1:], 1):
         dj, sets, sp = f.dj, f.sets, f.sp
         D = len(dj.models)
@@ -1966,13 +2176,20 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, ab
         _L.check(lib.tpe_rows_compact(flags, P, rows.data_ptr(), count.data_ptr(),
                                       cscratch.data_ptr(), sp), "tpe_rows_compact")
 
+        keep = above is not None and n_ctx
+
         def score(which, p0, sub, dst, mode):
             dset, n, _ = sets[which]
             head = (dj.host.ctypes.data, dj.dev.data_ptr(), D)
             tail = (tab, dj.n_tables, dset.data_ptr(), n, d_vals.data_ptr(), ld, n_cols,
                     rows.data_ptr(), count.data_ptr(), p0, min(win, P - p0), sub, dst, mode,
                     scratch.data_ptr(), sp)
-            if n_ctx:
+            if keep and which == 1:  # (the two values the merge subtracts stay)
+                kept = (above[g].data_ptr(),
+                        None if above_ctx is None else above_ctx[g].data_ptr(), keep_ld)
+                _L.check(lib.tpe_joint_chain_rows_keep(*(head + (n_ctx,) + tail[:-2] + kept +
+                                                         tail[-2:])), "tpe_joint_chain_rows_keep")
+            elif n_ctx:
                 _L.check(lib.tpe_joint_chain_rows(*(head + (n_ctx,) + tail)),
                          "tpe_joint_chain_rows")
             else:
@@ -1980,7 +2197,7 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, ab
 
         for p0 in range(0, P, win):
             score(1, p0, None, dense.data_ptr(), 0)
-            if above is not None:
+            if above is not None and not keep:
                 _L.check(lib.tpe_rows_scatter(dense.data_ptr(), rows.data_ptr(), count.data_ptr(),
                                               p0, min(win, P - p0), above[g].data_ptr(),
                                               above.shape[1], sp), "tpe_rows_scatter")

@@ -56,10 +56,10 @@ mixture (csrc/tpe_joint_sample.hip); ``joint="tree"``, accepted wherever
 ``joint=True`` is, gives the labels under a ``switch`` joint mixtures as well,
 one per group of labels that share an activation condition (joint.py
 "Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
-interaction between labels.  ``joint="chain"`` (not on a ``GridPool``, not with
-a ``batch``) conditions each of those groups on the labels live around it
-(joint.py "Chains"; csrc/tpe_joint_chain.hip), so a root label interacts with a
-branch label; its sampled pools draw the rows of ``"tree"``.
+interaction between labels.  ``joint="chain"`` (not on a ``GridPool``; its
+batch is ``batch="liar-chain"``) conditions each of those groups on the labels
+live around it (joint.py "Chains"; csrc/tpe_joint_chain.hip), so a root label
+interacts with a branch label; its sampled pools draw the rows of ``"tree"``.
 
 ``batch="liar"`` (``suggest_from_pool``, ``suggest_sampled``, ``pick_batch``;
 with ``joint=True`` on a ``Pool`` / ``SampledPool``) makes the k rows of one
@@ -69,7 +69,11 @@ trial it is about to become (joint.py "Batches"; csrc/tpe_joint_lie.hip).  The
 host still reads back the k rows only, once.  ``batch="liar-tree"`` (with
 ``joint="tree"``) is that batch on a conditional space: the tree scoring keeps
 log L_above per group, and a pick lies in every group it is live in (joint.py
-"Batches in a tree"; csrc/tpe_joint_lie_tree.hip).
+"Batches in a tree"; csrc/tpe_joint_lie_tree.hip).  ``batch="liar-chain"`` (with
+``joint="chain"``) is the batch under the chain criterion: the scoring keeps log
+L_above and log L_ctx,above per chain fit, and a pick joins each fit's mixture and
+its context marginal at once (joint.py "Batches in a chain";
+csrc/tpe_joint_lie_chain.hip).
 """
 from __future__ import annotations
 
@@ -259,7 +263,8 @@ class _DevicePool(object):
     them --, activity (L, P) bytes, the taken mask, and per label the
     (min, max) of its live values in the scoring coordinate."""
     __slots__ = ("vals", "active", "taken", "taken_current", "ranges", "S", "terms", "rows_out",
-                 "count", "scratch", "first", "mask", "distinct_scratch", "fits", "parts", "above")
+                 "count", "scratch", "first", "mask", "distinct_scratch", "fits", "parts", "above",
+                 "above_ctx")
 
     def __init__(self, vals, active, taken, taken_current, ranges, S, terms=None):
         self.vals, self.active, self.ranges, self.S, self.terms = vals, active, ranges, S, terms
@@ -268,7 +273,7 @@ class _DevicePool(object):
         # the last joint scoring left (``_joint_device``)
         self.rows_out = self.count = self.scratch = None
         self.first = self.mask = self.distinct_scratch = None
-        self.fits = self.parts = self.above = None
+        self.fits = self.parts = self.above = self.above_ctx = None
 
 
 class Pool(object):
@@ -557,7 +562,8 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
     labels come from ``tpe_joint_sample`` and S starts from J; with ``st.lie``
     too the mirror keeps the fit and the born parts (log L_below, log L_above,
     unused) as ``_joint_device`` leaves them -- under ``batch="liar-tree"`` the
-    tree fits and the groups' log L_above (``_above``)."""
+    tree fits and the groups' log L_above (``_above``), under
+    ``batch="liar-chain"`` the chain fits, log L_above and log L_ctx,above."""
     from . import tpe as T
     domain = as_domain(domain)
     labels = list(domain.params)
@@ -624,7 +630,11 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
             n_active = _rows_active(eng, domain, labels, d, P, sp)
         # S starts from J of the drawn rows; the fold below adds the other labels
         # (with the groups every label is joint: S is theirs, and nothing is folded)
-        if st.lie_tree:  # (the groups' log L_above stays)
+        if st.lie_chain:  # (the fits' log L_above and log L_ctx,above stay)
+            d.fits, d.above, d.above_ctx = fits, _above(eng, fits, P), _above(eng, fits, P)
+            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above,
+                                 above_ctx=d.above_ctx)
+        elif st.lie_tree:  # (the groups' log L_above stays)
             d.fits, d.above = fits, _above(eng, fits, P)
             _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above)
         elif joint["tree"]:
@@ -1183,7 +1193,8 @@ def _parts(eng, domain, st, P):
 
 def _above(eng, fits, P):
     """The (G, P) device tensor ``joint.score_tree_device(above=)`` leaves the
-    groups' log L_above in, for ``batch="liar-tree"``."""
+    groups' log L_above in, for ``batch="liar-tree"``; for ``batch="liar-chain"``
+    one for ``above=`` and one for ``above_ctx=``."""
     t = eng.torch
     return t.empty((len(fits), max(P, 1)), dtype=t.float64, device=eng.device)
 
@@ -1192,9 +1203,16 @@ def _joint_device(eng, domain, pool, d, st, hist):
     """J (joint.py) of every pool row into ``d.S`` -- with ``tree`` the groups'
     S (``joint.score_tree_device``) -- and its parts into ``d.parts`` where
     that is a tensor (``_parts``).  The mirror keeps the fit in ``d.fits``, and
-    under ``batch="liar-tree"`` the groups' log L_above in ``d.above``."""
+    under ``batch="liar-tree"`` the groups' log L_above in ``d.above``, under
+    ``batch="liar-chain"`` the chain fits' in ``d.above`` and their log
+    L_ctx,above in ``d.above_ctx``."""
     P, L, ld = len(pool), len(pool.labels), d.vals.shape[1]
     d.fits = _fit(eng, domain, hist, L, st)
+    if st.lie_chain:
+        d.above, d.above_ctx = _above(eng, d.fits, P), _above(eng, d.fits, P)
+        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts, above=d.above,
+                             above_ctx=d.above_ctx)
+        return
     if st.lie_tree:
         d.above = _above(eng, d.fits, P)
         _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts, above=d.above)
@@ -1214,7 +1232,8 @@ def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=Fa
     other labels' terms, and the mirror keeps the fit in ``fits`` and -- with
     ``want_parts``, and for ``batch="liar"`` -- the parts in ``parts``
     (``_parts``); both are None otherwise.  ``batch="liar-tree"`` keeps the
-    groups' log L_above in ``above`` instead (``_joint_device``)."""
+    groups' log L_above in ``above`` instead, ``batch="liar-chain"`` the chain
+    fits' in ``above`` and ``above_ctx`` (``_joint_device``)."""
     if isinstance(pool, GridPool):  # (ValueError(GRID_JOINT) on a grid without the plan)
         return _score_grid(domain, trials, pool, st, False, hist)[:2]
     _same_space(domain, pool)
@@ -1235,8 +1254,9 @@ def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=Fa
     P = len(pool)
     if want_terms and d.terms is None:
         d.terms = t.empty((len(pool.labels), max(P, 1)), dtype=t.float64, device=eng.device)
-    d.fits = d.parts = d.above = None
-    if joint is not None and (want_parts or (st.lie is not None and not st.lie_tree)):
+    d.fits = d.parts = d.above = d.above_ctx = None
+    if joint is not None and (want_parts or (st.lie is not None and not st.lie_tree
+                                             and not st.lie_chain)):
         d.parts = _parts(eng, domain, st, P)
     if P == 0:
         return eng, d
@@ -1444,6 +1464,9 @@ BATCH_LIAR = ("batch='liar' is supported with joint=True on a Pool or a SampledP
               "(suggest_from_pool, suggest_sampled, pick_batch)")
 BATCH_LIAR_TREE = ("batch='liar-tree' is supported with joint='tree' on a Pool or a SampledPool "
                    "(suggest_from_pool, suggest_sampled, pick_batch(joint='tree'))")
+BATCH_LIAR_CHAIN = ("batch='liar-chain' is supported with joint='chain' on a Pool or a "
+                    "SampledPool (suggest_from_pool, suggest_sampled, pick_batch(joint='chain', "
+                    "batch='liar-chain'))")
 
 
 REFINE = ("refine= moves the picked rows' continuous always-live labels up the joint "
@@ -1455,18 +1478,20 @@ REFINE_TREE = ("refine_tree= moves the picked rows' continuous labels up their g
 class _Settings(object):
     """What a scoring and the picks after it run under: ``prior_weight``,
     ``gamma``, ``lf`` (linear forgetting), ``joint`` (``_joint_kw``) and
-    ``lie`` (None, or the lie's weight of ``batch="liar"`` / ``"liar-tree"``),
-    ``lie_tree`` (the lie is ``"liar-tree"``'s: one per group, joint.py "Batches
-    in a tree") and ``refine`` (the steps the picked rows climb, joint.py
-    "Refining"; 0: none) and ``refine_tree`` (the steps they climb per live
-    group, joint.py "Refining in a tree"; 0: none)."""
+    ``lie`` (None, or the lie's weight of ``batch="liar"`` / ``"liar-tree"`` /
+    ``"liar-chain"``), ``lie_tree`` (the lie is ``"liar-tree"``'s: one per
+    group, joint.py "Batches in a tree"), ``lie_chain`` (it is
+    ``"liar-chain"``'s: one per chain fit, joint.py "Batches in a chain") and
+    ``refine`` (the steps the picked rows climb, joint.py "Refining"; 0: none)
+    and ``refine_tree`` (the steps they climb per live group, joint.py
+    "Refining in a tree"; 0: none)."""
     __slots__ = ("prior_weight", "gamma", "lf", "joint", "lie", "refine", "lie_tree",
-                 "refine_tree")
+                 "refine_tree", "lie_chain")
 
     def __init__(self, prior_weight, gamma, lf, joint=None, lie=None, refine=0):
         self.prior_weight, self.gamma, self.lf, self.joint, self.lie, self.refine = \
             prior_weight, gamma, lf, joint, lie, refine
-        self.lie_tree, self.refine_tree = False, 0
+        self.lie_tree, self.refine_tree, self.lie_chain = False, 0, False
 
 
 def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
@@ -1474,11 +1499,12 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
               refine=None, domain=None, refine_tree=None):
     """The ``_Settings`` of a public call's keywords, after the checks:
     ``_joint_kw``'s, then for a ``batch`` ValueError on any string but
-    ``"liar"`` (needs ``joint=True``) and ``"liar-tree"`` (needs
-    ``joint="tree"``), on a ``lie_weight`` that is not a finite number > 0, and on
-    what the batch is not built for (joint.py, "Not built"; ``pool``: the
-    call's pool, where it has one; ``domain``: the call's space, for the keys of
-    a ``bandwidth`` mapping).  A ``refine`` that is not None: ValueError
+    ``"liar"`` (needs ``joint=True``), ``"liar-tree"`` (needs
+    ``joint="tree"``) and ``"liar-chain"`` (needs ``joint="chain"``), on a
+    ``lie_weight`` that is not a finite number > 0, and on what the batch is not
+    built for (joint.py, "Not built"; ``pool``: the call's pool, where it has
+    one; ``domain``: the call's space, for the keys of a ``bandwidth``
+    mapping).  A ``refine`` that is not None: ValueError
     unless it is an integer >= 0 and ``joint`` is ``True``.  A ``refine_tree``
     that is not None: the same with ``joint="tree"``, and ValueError beside a
     non-zero ``refine``."""
@@ -1505,11 +1531,22 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
             raise ValueError(REFINE_TREE + "; a GridPool has no row values to move")
     if batch is None:
         return st
-    if batch not in ("liar", "liar-tree"):
-        raise ValueError("batch=%r: None or 'liar' (joint=True) or 'liar-tree' (joint='tree')"
-                         % (batch,))
+    if batch not in ("liar", "liar-tree", "liar-chain"):
+        raise ValueError("batch=%r: None or 'liar' (joint=True) or 'liar-tree' (joint='tree') or "
+                         "'liar-chain' (joint='chain')" % (batch,))
     if not lie_weight > 0.0 or not math.isfinite(lie_weight):
         raise ValueError("lie_weight=%r must be a finite number > 0" % (lie_weight,))
+    if batch == "liar-chain":
+        if st.joint is None or st.joint["tree"] != "chain":
+            raise ValueError(BATCH_LIAR_CHAIN + "; with joint=True the batch is batch='liar', with "
+                             "joint='tree' batch='liar-tree', and the factorised criterion "
+                             "(joint=False) has none: pass joint='chain'")
+        if isinstance(pool, GridPool):  # (joint='chain' itself is not built on one)
+            raise ValueError(BATCH_LIAR_CHAIN + "; a GridPool has no row values to lie with "
+                             "(GridPool.to_pool())")
+        # (refine= / refine_tree= beside joint='chain' have raised above)
+        st.lie, st.lie_chain = float(lie_weight), True
+        return st
     if batch == "liar-tree":
         if st.joint is None or not st.joint["tree"]:
             raise ValueError(BATCH_LIAR_TREE + "; with joint=True the batch is batch='liar', "
@@ -1558,10 +1595,25 @@ def _liar_device(eng, d, P, k, mask, lie_weight, trace=False, tree=False):
                           d.taken, mask, k, lie_weight, trace, d.rows_out)
 
 
+def _liar_chain_device(eng, d, P, k, mask, lie_weight, trace=False):
+    """``_liar_device`` for ``batch="liar-chain"``: the rows of
+    ``joint.liar_chain_device`` on d.S, with the chain fits, ``d.above`` and
+    ``d.above_ctx`` the scoring left in the mirror.  The rows stay in d.rows_out."""
+    t = eng.torch
+    k = min(int(k), P)
+    if d.rows_out is None or d.rows_out.numel() < k + 1:
+        d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
+        d.count = t.zeros(1, dtype=t.int64, device=eng.device)
+    return _J.liar_chain_device(d.fits, d.vals, d.active, d.vals.shape[1], d.vals.shape[0], P, d.S,
+                                d.above, d.above_ctx, d.taken, mask, k, lie_weight, trace,
+                                d.rows_out)
+
+
 def _pick(eng, pool, d, k, hist, distinct, st, trace=False):
     """The k rows to hand out, by the scores in the mirror ``d``: the first k
     untaken rows by d.S (``_topk_device``), or with ``st.lie`` the liar batch
-    (``_liar_device``; ``trace``: its (rows, S_at_pick, S_k)).  ``distinct``:
+    (``_liar_device``, under ``st.lie_chain`` ``_liar_chain_device``; ``trace``:
+    its (rows, S_at_pick, S_k)).  ``distinct``:
     fresh rows only (``_distinct_device`` against ``hist``).  The rows stay in
     d.rows_out."""
     if distinct:
@@ -1569,12 +1621,14 @@ def _pick(eng, pool, d, k, hist, distinct, st, trace=False):
     mask = d.mask if distinct else None
     if st.lie is None:
         return _topk_device(eng, d, len(pool), k, mask)
+    if st.lie_chain:
+        return _liar_chain_device(eng, d, len(pool), k, mask, st.lie, trace)
     return _liar_device(eng, d, len(pool), k, mask, st.lie, trace, st.lie_tree)
 
 
 def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_weight=1.0,
                prior_weight=1.0, gamma=0.25, linear_forgetting=25, bandwidth=_J.BANDWIDTH,
-               cat_smoothing=_J.CAT_SMOOTHING, joint=True):
+               cat_smoothing=_J.CAT_SMOOTHING, joint=True, batch=None):
     """The rows ``suggest_from_pool(joint=True, batch="liar")`` would hand out
     for k ids past the startup phase, in pick order (numpy int64; joint.py,
     "Batches"), without marking anything taken.  ``return_trace``: (rows,
@@ -1582,10 +1636,13 @@ def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_
     after the last pick.  A ``GridPool`` raises ValueError.  ``joint="tree"``:
     the rows of ``suggest_from_pool(joint="tree", batch="liar-tree")`` (joint.py,
     "Batches in a tree"); any other value is judged as ``batch="liar"`` judges
-    it."""
+    it.  ``batch``: None, that choice, or the batch by name -- ``joint="chain",
+    batch="liar-chain"`` gives the rows of ``suggest_from_pool`` under that pair
+    (joint.py, "Batches in a chain")."""
     from . import tpe as T
     domain = as_domain(domain)
-    batch = "liar-tree" if isinstance(joint, str) and joint == "tree" else "liar"
+    if batch is None:
+        batch = "liar-tree" if isinstance(joint, str) and joint == "tree" else "liar"
     st = _settings(prior_weight, gamma, linear_forgetting, joint, bandwidth, cat_smoothing, batch,
                    lie_weight, pool, domain=domain)
     _same_space(domain, pool)
@@ -1745,6 +1802,12 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None, prior_weight=1.0
     mixture of every group of labels it is live in, so rows that differ under a
     ``switch`` alone are told apart (joint.py, "Batches in a tree").  On a flat
     space it is ``batch="liar"`` with ``joint=True``, bit for bit.
+    ``batch="liar-chain"`` (with ``joint="chain"``; anything else raises
+    ValueError): the batch under the chain criterion -- a pick joins the above
+    mixture of every chain fit it is live in and that mixture's context marginal,
+    so a group's penalty is the change of its conditional density (joint.py,
+    "Batches in a chain").  On a space whose groups all have empty contexts it is
+    ``batch="liar-tree"`` with ``joint="tree"``, bit for bit.
 
     ``refine`` / ``refine_tree``: anything but None raises ValueError -- a fixed
     pool's rows are a closed set, and a ``GridPool`` has no row to move
@@ -2080,7 +2143,10 @@ def suggest_sampled(new_ids, domain, trials, seed, n_EI_candidates=4096, keep=No
     leaves: the pool's born parts under ``draw="joint"``.  ``keep``,
     ``distinct`` and the startup phase are unchanged.  ``batch="liar-tree"``
     (needs ``joint="tree"``): a pick lies in every group it is live in
-    (``suggest_from_pool``).
+    (``suggest_from_pool``).  ``batch="liar-chain"`` (needs ``joint="chain"``,
+    either ``draw``): a pick joins every chain fit it is live in, mixture and
+    context marginal (``suggest_from_pool``); under ``draw="joint"`` the pool is
+    born with the values the batch starts from.
 
     ``refine=N`` (needs ``joint=True``; ValueError otherwise, and for anything
     but an integer >= 0): the best draw lies between the mixture's peaks and

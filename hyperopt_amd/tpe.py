@@ -48,7 +48,10 @@ time on the device, each pick joining the above mixture as the pending trial
 it is about to become, so a batch for parallel evaluation spreads out
 (``pick_batch``: the rows alone; ``joint_liar_numpy``).  ``batch="liar-tree"``
 (with ``joint="tree"``) is that batch on a conditional space: a pick lies in
-every group of labels it is live in (``joint_liar_tree_numpy``).
+every group of labels it is live in (``joint_liar_tree_numpy``);
+``batch="liar-chain"`` (with ``joint="chain"``) is the batch under the chain
+criterion: a pick joins every chain fit it is live in, its mixture and its
+context marginal at once (``joint_liar_chain_numpy``).
 ``suggest_sampled(joint=True, refine=N)`` lets the picked rows climb the joint
 criterion on their continuous labels, on the device (``refine_configs``: any
 rows; ``joint_refine_numpy``); ``suggest_sampled(joint="tree", refine_tree=N)``
@@ -819,6 +822,7 @@ from .joint import (component_key as joint_component_key,  # noqa: E402,F401
                     group_component_key as joint_group_component_key, joint_contexts,
                     joint_groups, joint_labels, liar_numpy as joint_liar_numpy,
                     liar_tree_numpy as joint_liar_tree_numpy,
+                    liar_chain_numpy as joint_liar_chain_numpy,
                     loo_label_fit_numpy as joint_loo_label_fit_numpy,
                     loo_label_numpy as joint_loo_label_numpy, loo_numpy as joint_loo_numpy,
                     refine_numpy as joint_refine_numpy,
