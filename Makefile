@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := hyperopt_amd/csrc
-SRCS := $(CSRC)/tpe_fit.hip $(CSRC)/tpe_parzen.hip $(CSRC)/tpe_score.hip $(CSRC)/tpe_quantized.hip $(CSRC)/tpe_categorical.hip $(CSRC)/tpe_table.hip $(CSRC)/tpe_table_score.hip $(CSRC)/tpe_band.hip $(CSRC)/tpe_pruned64.hip $(CSRC)/tpe_history.hip $(CSRC)/tpe_sorted.hip $(CSRC)/tpe_prior.hip $(CSRC)/tpe_anneal.hip $(CSRC)/tpe_pool.hip $(CSRC)/tpe_sampled.hip $(CSRC)/tpe_distinct.hip $(CSRC)/tpe_grid.hip $(CSRC)/tpe_grid_joint.hip $(CSRC)/tpe_joint.hip $(CSRC)/tpe_joint_sample.hip $(CSRC)/tpe_joint_tree.hip $(CSRC)/tpe_joint_chain.hip $(CSRC)/tpe_joint_lie.hip $(CSRC)/tpe_joint_lie_tree.hip $(CSRC)/tpe_joint_lie_chain.hip $(CSRC)/tpe_joint_refine.hip $(CSRC)/tpe_joint_refine_tree.hip $(CSRC)/tpe_joint_loo.hip $(CSRC)/tpe_joint_loo_label.hip $(CSRC)/tpe_dist.hip $(CSRC)/tpe_util.hip $(CSRC)/tpe_ops.hip
+SRCS := $(CSRC)/tpe_fit.hip $(CSRC)/tpe_parzen.hip $(CSRC)/tpe_score.hip $(CSRC)/tpe_quantized.hip $(CSRC)/tpe_categorical.hip $(CSRC)/tpe_table.hip $(CSRC)/tpe_table_score.hip $(CSRC)/tpe_band.hip $(CSRC)/tpe_pruned64.hip $(CSRC)/tpe_history.hip $(CSRC)/tpe_sorted.hip $(CSRC)/tpe_prior.hip $(CSRC)/tpe_anneal.hip $(CSRC)/tpe_pool.hip $(CSRC)/tpe_sampled.hip $(CSRC)/tpe_distinct.hip $(CSRC)/tpe_grid.hip $(CSRC)/tpe_grid_joint.hip $(CSRC)/tpe_joint.hip $(CSRC)/tpe_joint_sample.hip $(CSRC)/tpe_joint_tree.hip $(CSRC)/tpe_joint_chain.hip $(CSRC)/tpe_joint_lie.hip $(CSRC)/tpe_joint_refine.hip $(CSRC)/tpe_joint_refine_tree.hip $(CSRC)/tpe_joint_loo.hip $(CSRC)/tpe_joint_loo_label.hip $(CSRC)/tpe_dist.hip $(CSRC)/tpe_util.hip $(CSRC)/tpe_ops.hip
 OBJS := $(SRCS:.hip=.o)
 LIB := hyperopt_amd/libtpe_hip.so
 # -ffp-contract=off: no implicit FMA fusion, so expressions written to
@@ -15,7 +15,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function 
 all: $(LIB)
 
 # fp64 throughout: the packed fp32 forms are kept out of its code outright
-$(CSRC)/tpe_joint_loo.o $(CSRC)/tpe_joint_loo_label.o $(CSRC)/tpe_joint_lie_tree.o $(CSRC)/tpe_joint_lie_chain.o: FILE_FLAGS := -Xclang -target-feature -Xclang -packed-fp32-ops
+$(CSRC)/tpe_joint_loo.o $(CSRC)/tpe_joint_loo_label.o $(CSRC)/tpe_joint_lie.o: FILE_FLAGS := -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/tpe_hip.h
 	$(HIPCC) $(FLAGS) $(FILE_FLAGS) -c $< -o $@

@@ -22,6 +22,9 @@
 //                         over the chunk and the merge are tpe_joint.hip's own
 //                         statements (tpe_joint_pass.hpp), so log L of a row
 //                         has the bits tpe_joint_score gives it.
+//   tpe_rows_scatter      dst[rows[p]] = src[p - list_begin] over a window of
+//                         that list: how score_tree_device keeps the log L_above
+//                         it has just computed for a liar batch.
 #include "tpe_joint.hpp"
 #include "tpe_wave.hpp"
 
@@ -140,6 +143,21 @@ __global__ __launch_bounds__(kJBS) void k_joint_merge_rows(
     out[row] = v;
 }
 
+// dst[rows[p]] = src[p - list_begin] for the list positions of the window, with
+// k_joint_merge_rows' guards: the count stays on the device, an entry outside
+// [0, ld) is skipped
+__global__ __launch_bounds__(kJBS) void k_rows_scatter(const double* __restrict__ src,
+                                                       const int64_t* __restrict__ rows,
+                                                       const int64_t* __restrict__ d_count,
+                                                       int64_t list_begin, int64_t max_rows,
+                                                       double* __restrict__ dst, int64_t ld) {
+  const int64_t r = (int64_t)blockIdx.x * kJBS + threadIdx.x;
+  if (r >= window_rows(d_count, list_begin, max_rows)) return;
+  const int64_t row = rows[list_begin + r];
+  if (row < 0 || row >= ld) return;
+  dst[row] = src[r];
+}
+
 inline int64_t compact_blocks(int64_t n_rows) { return (n_rows + kCRows - 1) / kCRows; }
 }  // namespace
 }  // namespace tpe
@@ -224,4 +242,24 @@ extern "C" int tpe_joint_score_rows(const tpe_joint_label* host_labels,
   hipLaunchKernelGGL(k_joint_merge_rows, dim3((unsigned)blocks), dim3(kJBS), 0, st, partial,
                      chunks, ld, rows, d_count, list_begin, max_rows, sub, out, out_mode);
   return check_launch("tpe_joint_score_rows");
+}
+
+extern "C" int tpe_rows_scatter(const double* src, const int64_t* rows, const int64_t* d_count,
+                                int64_t list_begin, int64_t max_rows, double* dst, int64_t ld,
+                                void* stream) {
+  if (list_begin < 0 || max_rows < 0 || ld < 0 || list_begin >= ((int64_t)1 << 40) ||
+      max_rows > (int64_t)2147483647 * kJBS) {
+    set_error("tpe_rows_scatter: list [%lld, +%lld) ld=%lld", (long long)list_begin,
+              (long long)max_rows, (long long)ld);
+    return TPE_E_ARG;
+  }
+  if (max_rows == 0 || ld == 0) return TPE_OK;  // (ld == 0: no row is inside [0, ld))
+  if (!src || !rows || !d_count || !dst) {
+    set_error("tpe_rows_scatter: null pointer");
+    return TPE_E_ARG;
+  }
+  const int64_t blocks = (max_rows + kJBS - 1) / kJBS;
+  hipLaunchKernelGGL(k_rows_scatter, dim3((unsigned)blocks), dim3(kJBS), 0,
+                     (hipStream_t)stream, src, rows, d_count, list_begin, max_rows, dst, ld);
+  return check_launch("tpe_rows_scatter");
 }

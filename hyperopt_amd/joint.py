@@ -183,6 +183,17 @@ the branches as well.
 ``liar_numpy`` is this definition in numpy; ``liar_device`` enqueues all k
 picks in one call (a pick's row is read on the device) and reads back the rows.
 
+One engine, three entry modes.  This batch, "Batches in a tree" and "Batches in
+a chain" (below) are a strict hierarchy: a flat space is a tree of one group
+(the joint labels' fit, live in every row), a tree a chain whose contexts are
+all empty.  The code has each thing once: ``_liar_numpy`` is the one pick loop
+over a list of fits (``_lie_fits``), which ``liar_numpy``, ``liar_tree_numpy``
+and ``liar_chain_numpy`` build for their mode; ``_liar_picks_device`` packs the
+fits (``_lie_pack``) and makes the one call, tpe_joint_lie_chain_picks, for
+``liar_device``, ``liar_tree_device`` and ``liar_chain_device``; and
+csrc/tpe_joint_lie.hip holds one driver and one kernel pair behind the three C
+entries.  The three model texts are the specification of their mode.
+
 Chains (``joint="chain"``, csrc/tpe_joint_chain.hip).  The
 groups above are independent mixtures: a label at the root (a tile size) that
 is good only together with a label inside one branch (that variant's unroll
@@ -381,7 +392,7 @@ values: the choice is made on the host and steers the next call.
 ``bandwidth="loo-label"`` is resolved where ``"loo"`` is, into the mapping.
 
 Batches in a tree (``joint="tree"``, ``batch="liar-tree"``,
-csrc/tpe_joint_lie_tree.hip).  Under ``joint="tree"`` every group
+csrc/tpe_joint_lie.hip).  Under ``joint="tree"`` every group
 has an above mixture of its own, so a pick joins each one it is live in: two
 rows equal at the root and different under a ``switch`` get different
 penalties.  Groups g = 0 .. G - 1 are those of ``joint_groups(domain)``; the
@@ -418,10 +429,10 @@ first label is set (the rule ``score_tree_device`` compacts on).
 keeps A_g while it scores (row 0 is the root's subtrahend itself; a group's
 dense temporary is copied to its rows by tpe_rows_scatter: the above set is not
 scored twice and the list's length stays on the device), and
-``liar_tree_device`` enqueues all k picks in one tpe_joint_lie_tree_picks.
+``liar_tree_device`` enqueues all k picks in one call.
 
 Batches in a chain (``joint="chain"``, ``batch="liar-chain"``,
-csrc/tpe_joint_lie_chain.hip).  C_g is a ratio, but of one
+csrc/tpe_joint_lie.hip).  C_g is a ratio, but of one
 mixture: a pending trial joins the above mixture of every chain fit it is live
 in, and that mixture's context marginal is the same mixture with g's factors
 dropped -- so the lie joins numerator and denominator, and one walk over the
@@ -476,8 +487,7 @@ in the history would change.
 above_ctx=)`` keeps A_g and B_g while it scores: a fit with a context writes both
 from the merge that forms them (tpe_joint_chain_rows_keep; no scatter launch, the
 above set is not scored twice), a fit without one fills ``above`` as under
-``"tree"``.  ``liar_chain_device`` enqueues all k picks in one
-tpe_joint_lie_chain_picks.
+``"tree"``.  ``liar_chain_device`` enqueues all k picks in one call.
 
 Not built: a draw conditioned on the row's context (component weights ``w_i *
 prod_ctx k``: ``joint="chain"`` draws as ``"tree"`` does).  ``joint="chain"``
@@ -904,6 +914,86 @@ def _first_row(S, gone):
     return int(free[np.argmax(nan)] if nan.any() else free[np.argmax(s)])
 
 
+def _lie_join(u, c):
+    """``u`` joined with ``c`` by the "Batches" rule, elementwise."""
+    with np.errstate(all="ignore"):
+        m = np.where(c > u, c, u)
+        both = m + np.log(np.exp(u - m) + np.exp(c - m))
+        return np.where(c == -np.inf, u, np.where(m == -np.inf, -np.inf, both))
+
+
+def _lie_fits(domain, hist, vals, active, groups, gamma, lf, prior_weight, bandwidth):
+    """The fits a batch lies in, for ``_liar_numpy``: per (labels, n_ctx) of
+    ``groups`` (the root first; its rows are all live, a later fit's those where
+    its first own label is active) the record (models, n_ctx, live rows, their
+    stored values, sigma, log W)."""
+    isa = split_sets(hist, gamma)[1]
+    per = []
+    for g, (labels, n_ctx) in enumerate(groups):
+        models = label_models(domain, labels)
+        cols = [m.col for m in models]
+        live = np.flatnonzero(active[:, cols[n_ctx]]) if g else np.arange(vals.shape[0])
+        n = int(set_rows(hist, isa, cols).size)
+        per.append((models, n_ctx, live, vals[live][:, cols], lie_sigma(models, n, bandwidth),
+                    lie_log_total(n, lf, prior_weight)))
+    return per
+
+
+def _log_lie(lie_weight):
+    """log(lie_weight); ValueError unless it is > 0 and finite."""
+    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
+        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
+    return math.log(lie_weight)
+
+
+def _liar_numpy(per, S0, A, B, taken, distinct, k, log_lie, smoothing):
+    """The pick loop of module doc "Batches in a chain" -- with every ``n_ctx``
+    0 that of "Batches in a tree", with one fit that of "Batches" -- over the
+    fits ``per`` (``_lie_fits``): (rows, S_at_pick, S_k, (U_0, U_k, V_0, V_k)),
+    the state (P, G), NaN where nothing is kept.  ``A`` / ``B``: (P, G), ``B``
+    read where a fit has a context."""
+    S0 = np.asarray(S0, np.float64)
+    P, G = S0.shape[0], len(per)
+    A = np.asarray(A, np.float64).reshape(P, G)
+    U0, V0 = np.full((P, G), np.nan), np.full((P, G), np.nan)
+    for g, (_models, n_ctx, live, _x, _sig, log_w) in enumerate(per):
+        U0[live, g] = log_w + A[live, g]
+        if n_ctx:
+            V0[live, g] = log_w + np.asarray(B, np.float64).reshape(P, G)[live, g]
+    gone = np.zeros(P, bool)
+    for mask in (taken, distinct):
+        if mask is not None:
+            gone |= np.asarray(mask)[:P] != 0
+    U, V, S = U0.copy(), V0.copy(), S0.copy()
+    rows, at = [], []
+    for _ in range(min(max(int(k), 0), P)):
+        p = _first_row(S, gone)
+        if p < 0:
+            break
+        rows.append(p)
+        at.append(S[p])
+        gone[p] = True
+        S = S0.copy()
+        for g, (models, n_ctx, live, x, sig, _log_w) in enumerate(per):
+            at_p = int(np.searchsorted(live, p))
+            with np.errstate(all="ignore"):
+                if at_p < live.size and live[at_p] == p:  # (g is live in the pick)
+                    c = _lie_component(models[:n_ctx], x[:, :n_ctx], at_p, sig[:n_ctx],
+                                       smoothing, log_lie)
+                    if n_ctx:  # (the label boundary: c is c^ctx)
+                        V[live, g] = _lie_join(V[live, g], c)
+                    c = _lie_component(models[n_ctx:], x[:, n_ctx:], at_p, sig[n_ctx:],
+                                       smoothing, log_lie, start=c)
+                    U[live, g] = _lie_join(U[live, g], c)
+                if n_ctx:
+                    fin = live[np.isfinite(U0[live, g]) & np.isfinite(V0[live, g])]
+                    S[fin] = S[fin] - ((U[fin, g] - U0[fin, g]) - (V[fin, g] - V0[fin, g]))
+                else:
+                    fin = live[np.isfinite(U0[live, g])]
+                    S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
+    return np.asarray(rows, np.int64), np.asarray(at, np.float64), S, (U0, U, V0, V)
+
+
 def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0, S0=None, A0=None,
                prior_weight=1.0, gamma=0.25, linear_forgetting=25, bandwidth=BANDWIDTH,
                cat_smoothing=CAT_SMOOTHING):
@@ -913,45 +1003,19 @@ def liar_numpy(domain, hist, vals, k, taken=None, distinct=None, lie_weight=1.0,
     as ``Pool.vals`` holds them; ``taken`` / ``distinct``: row masks (nonzero:
     not to be picked).  ``S0`` / ``A0``: the score and log L_above to start
     from where the caller has them (a device's, or S with the folded terms of
-    a conditional space); else ``score_numpy``'s J and log L_above."""
-    domain = as_domain(domain)
-    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
-        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
-    models = label_models(domain)
+    a conditional space: the always-live labels alone lie); else
+    ``score_numpy``'s J and log L_above."""
+    domain, log_lie = as_domain(domain), _log_lie(lie_weight)
     vals = np.asarray(vals, np.float64)
-    P = vals.shape[0]
-    cols = [m.col for m in models]
     if S0 is None or A0 is None:
         J, _below, above = score_numpy(domain, hist, vals, None, prior_weight, gamma,
                                        linear_forgetting, bandwidth, cat_smoothing,
                                        return_parts=True)
         S0 = J if S0 is None else S0
         A0 = above if A0 is None else A0
-    S0, A0 = np.asarray(S0, np.float64), np.asarray(A0, np.float64)
-    n = int(set_rows(hist, split_sets(hist, gamma)[1], cols).size)
-    sig = lie_sigma(models, n, bandwidth)
-    x = vals[:, cols]
-    gone = np.zeros(P, bool)
-    for mask in (taken, distinct):
-        if mask is not None:
-            gone |= np.asarray(mask)[:P] != 0
-    U0 = lie_log_total(n, linear_forgetting, prior_weight) + A0
-    U, S = U0.copy(), S0.copy()
-    rows, at = [], []
-    for _ in range(min(max(int(k), 0), P)):
-        p = _first_row(S, gone)
-        if p < 0:
-            break
-        rows.append(p)
-        at.append(S[p])
-        gone[p] = True
-        c = _lie_component(models, x, p, sig, cat_smoothing, math.log(lie_weight))
-        with np.errstate(all="ignore"):
-            m = np.where(c > U, c, U)
-            both = m + np.log(np.exp(U - m) + np.exp(c - m))
-            U = np.where(c == -np.inf, U, np.where(m == -np.inf, -np.inf, both))
-            S = np.where(np.isfinite(U0), S0 - (U - U0), S0)
-    return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
+    per = _lie_fits(domain, hist, vals, None, [(None, 0)], gamma, linear_forgetting, prior_weight,
+                    bandwidth)
+    return _liar_numpy(per, S0, A0, None, taken, distinct, k, log_lie, cat_smoothing)[:3]
 
 
 def liar_tree_numpy(domain, hist, vals, k, active=None, taken=None, distinct=None,
@@ -963,64 +1027,18 @@ def liar_tree_numpy(domain, hist, vals, k, active=None, taken=None, distinct=Non
     ``vals`` is not NaN).  ``S0`` (P,) / ``A`` (P, G; read where the group is
     live): the tree score and the groups' log L_above to start from where the
     caller has them; else ``score_numpy(tree=True)``'s."""
-    domain = as_domain(domain)
-    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
-        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
-    groups = joint_groups(domain)
+    domain, log_lie = as_domain(domain), _log_lie(lie_weight)
     vals = np.asarray(vals, np.float64)
     active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
-    P, G = vals.shape[0], len(groups)
     if S0 is None or A is None:
         S, _J, _below, above = score_numpy(domain, hist, vals, active, prior_weight, gamma,
                                            linear_forgetting, bandwidth, cat_smoothing,
                                            return_parts=True, tree=True)
         S0 = S if S0 is None else S0
         A = above if A is None else A
-    S0, A = np.asarray(S0, np.float64), np.asarray(A, np.float64).reshape(P, G)
-    isa = split_sets(hist, gamma)[1]
-    per, U0 = [], np.full((P, G), np.nan)
-    for g, grp in enumerate(groups):
-        models = label_models(domain, grp.labels)
-        cols = [m.col for m in models]
-        live = np.flatnonzero(active[:, cols[0]]) if g else np.arange(P)
-        n = int(set_rows(hist, isa, cols).size)
-        per.append((models, live, vals[live][:, cols], lie_sigma(models, n, bandwidth)))
-        U0[live, g] = lie_log_total(n, linear_forgetting, prior_weight) + A[live, g]
-    gone = np.zeros(P, bool)
-    for mask in (taken, distinct):
-        if mask is not None:
-            gone |= np.asarray(mask)[:P] != 0
-    U, S = U0.copy(), S0.copy()
-    rows, at = [], []
-    for _ in range(min(max(int(k), 0), P)):
-        p = _first_row(S, gone)
-        if p < 0:
-            break
-        rows.append(p)
-        at.append(S[p])
-        gone[p] = True
-        S = S0.copy()
-        for g, (models, live, x, sig) in enumerate(per):
-            at_p = int(np.searchsorted(live, p))
-            with np.errstate(all="ignore"):
-                if at_p < live.size and live[at_p] == p:  # (g is live in the pick)
-                    c = _lie_component(models, x, at_p, sig, cat_smoothing, math.log(lie_weight))
-                    u = U[live, g]
-                    m = np.where(c > u, c, u)
-                    both = m + np.log(np.exp(u - m) + np.exp(c - m))
-                    U[live, g] = np.where(c == -np.inf, u,
-                                          np.where(m == -np.inf, -np.inf, both))
-                fin = live[np.isfinite(U0[live, g])]
-                S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
-    return np.asarray(rows, np.int64), np.asarray(at, np.float64), S
-
-
-def _lie_join(u, c):
-    """``u`` joined with ``c`` by the "Batches" rule, elementwise."""
-    with np.errstate(all="ignore"):
-        m = np.where(c > u, c, u)
-        both = m + np.log(np.exp(u - m) + np.exp(c - m))
-        return np.where(c == -np.inf, u, np.where(m == -np.inf, -np.inf, both))
+    per = _lie_fits(domain, hist, vals, active, [(grp.labels, 0) for grp in joint_groups(domain)],
+                    gamma, linear_forgetting, prior_weight, bandwidth)
+    return _liar_numpy(per, S0, A, None, taken, distinct, k, log_lie, cat_smoothing)[:3]
 
 
 def liar_chain_numpy(domain, hist, vals, k, active=None, taken=None, distinct=None,
@@ -1034,67 +1052,21 @@ def liar_chain_numpy(domain, hist, vals, k, active=None, taken=None, distinct=No
     fits' log L_above and log L_ctx,above to start from where the caller has
     them; else ``score_numpy(tree="chain")``'s.  ``return_state``: also (U_0,
     U_k, V_0, V_k), (P, G), NaN where nothing is kept."""
-    domain = as_domain(domain)
-    if not lie_weight > 0.0 or not np.isfinite(lie_weight):
-        raise ValueError("lie_weight=%r must be > 0 and finite" % (lie_weight,))
-    groups, contexts = joint_groups(domain), joint_contexts(domain)
+    domain, log_lie = as_domain(domain), _log_lie(lie_weight)
     vals = np.asarray(vals, np.float64)
     active = ~np.isnan(vals) if active is None else np.asarray(active, bool)
-    P, G = vals.shape[0], len(groups)
     if S0 is None or A is None or B is None:
         parts = score_numpy(domain, hist, vals, active, prior_weight, gamma, linear_forgetting,
                             bandwidth, cat_smoothing, return_parts=True, tree="chain")
         S0 = parts[0] if S0 is None else S0
         A = parts[3] if A is None else A
         B = parts[5] if B is None else B
-    S0 = np.asarray(S0, np.float64)
-    A, B = np.asarray(A, np.float64).reshape(P, G), np.asarray(B, np.float64).reshape(P, G)
-    isa = split_sets(hist, gamma)[1]
-    per, U0, V0 = [], np.full((P, G), np.nan), np.full((P, G), np.nan)
-    for g, (grp, ctx) in enumerate(zip(groups, contexts)):
-        models = label_models(domain, ctx + grp.labels)
-        cols = [m.col for m in models]
-        live = np.flatnonzero(active[:, cols[len(ctx)]]) if g else np.arange(P)
-        n = int(set_rows(hist, isa, cols).size)
-        per.append((models, len(ctx), live, vals[live][:, cols], lie_sigma(models, n, bandwidth)))
-        log_w = lie_log_total(n, linear_forgetting, prior_weight)
-        U0[live, g] = log_w + A[live, g]
-        if ctx:
-            V0[live, g] = log_w + B[live, g]
-    gone = np.zeros(P, bool)
-    for mask in (taken, distinct):
-        if mask is not None:
-            gone |= np.asarray(mask)[:P] != 0
-    U, V, S = U0.copy(), V0.copy(), S0.copy()
-    rows, at = [], []
-    log_lie = math.log(lie_weight)
-    for _ in range(min(max(int(k), 0), P)):
-        p = _first_row(S, gone)
-        if p < 0:
-            break
-        rows.append(p)
-        at.append(S[p])
-        gone[p] = True
-        S = S0.copy()
-        for g, (models, n_ctx, live, x, sig) in enumerate(per):
-            at_p = int(np.searchsorted(live, p))
-            with np.errstate(all="ignore"):
-                if at_p < live.size and live[at_p] == p:  # (g is live in the pick)
-                    c = _lie_component(models[:n_ctx], x[:, :n_ctx], at_p, sig[:n_ctx],
-                                       cat_smoothing, log_lie)
-                    if n_ctx:  # (the label boundary: c is c^ctx)
-                        V[live, g] = _lie_join(V[live, g], c)
-                    c = _lie_component(models[n_ctx:], x[:, n_ctx:], at_p, sig[n_ctx:],
-                                       cat_smoothing, log_lie, start=c)
-                    U[live, g] = _lie_join(U[live, g], c)
-                if n_ctx:
-                    fin = live[np.isfinite(U0[live, g]) & np.isfinite(V0[live, g])]
-                    S[fin] = S[fin] - ((U[fin, g] - U0[fin, g]) - (V[fin, g] - V0[fin, g]))
-                else:
-                    fin = live[np.isfinite(U0[live, g])]
-                    S[fin] = S[fin] - (U[fin, g] - U0[fin, g])
-    out = (np.asarray(rows, np.int64), np.asarray(at, np.float64), S)
-    return out + (U0, U, V0, V) if return_state else out
+    groups = [(ctx + grp.labels, len(ctx))
+              for grp, ctx in zip(joint_groups(domain), joint_contexts(domain))]
+    per = _lie_fits(domain, hist, vals, active, groups, gamma, linear_forgetting, prior_weight,
+                    bandwidth)
+    out = _liar_numpy(per, S0, A, B, taken, distinct, k, log_lie, cat_smoothing)
+    return out[:3] + out[3] if return_state else out[:3]
 
 
 # -- refining (module doc, "Refining") -------------------------------------------
@@ -1549,6 +1521,14 @@ def stream_ptr(eng):
     return ctypes.c_void_p(eng.torch.cuda.current_stream(eng.device).cuda_stream)
 
 
+def _inv_sqrt2_sigma(sig):
+    """1 / (sqrt(2) sigma) per entry of ``sig``, and 0 where sigma is 0 (a
+    discrete label, and every label of an empty set, has no bandwidth: never an
+    infinity)."""
+    some = sig > 0.0
+    return np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)
+
+
 def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp):
     """One set on the device: (set tensor, n, row list).  ``seen``: the history
     on the device (``fit``); ``rows``: the set's rows as rows of that mirror."""
@@ -1556,11 +1536,7 @@ def _prepare_set(eng, dj, seen, hist_cols, rows, lf, prior_weight, bandwidth, sp
     _alive, sv, sa, sld, _srows, _n = seen
     D, n = len(dj.models), int(rows.size)
     sig = bandwidths(dj.models, n, bandwidth)
-    # (a discrete label, and every label of an empty set, has no bandwidth:
-    # 0 goes up for its 1 / (sqrt(2) sigma), never an infinity)
-    some = sig > 0.0
-    r = np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)
-    head = np.concatenate([log_weights(n, lf, prior_weight), sig, r])
+    head = np.concatenate([log_weights(n, lf, prior_weight), sig, _inv_sqrt2_sigma(sig)])
     dset = t.empty(lib.tpe_joint_set_doubles(D, n), dtype=t.float64, device=eng.device)
     dset[:head.size].copy_(t.from_numpy(head))
     drows = t.from_numpy(np.ascontiguousarray(rows, np.int32)).to(eng.device) if n else None
@@ -1697,69 +1673,23 @@ def sample_device(fit, seed, d_vals, ld, n_cols, row_base, n_rows, comp_out=None
              "tpe_joint_sample")
 
 
-def liar_device(fit, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weight, trace=False,
-                rows_out=None):
-    """The batch of module doc "Batches" for rows [0, P) of the label-major
-    device pool ``d_vals``: the picks in order (numpy int64, at most k), all
-    enqueued by one tpe_joint_lie_picks and read back once.  ``fit``: the
-    joint labels' fit, whose above set lends its bandwidths; ``S0`` /
-    ``A0``: device vectors (>= P doubles) of the score and of log L_above;
-    ``taken`` / ``distinct``: device byte masks (``distinct`` may be None).
-    None of them is written.  ``trace``: (rows, S_at_pick, S_k) as
-    ``liar_numpy`` returns them.  ``rows_out``: a device int64 tensor of more
-    than k entries to receive the rows (and, at entry k, their count) where the
-    caller reads them on the device afterwards."""
-    eng, dj, sp = fit.eng, fit.dj, fit.sp
-    t, lib = eng.torch, eng.lib
-    dset, n, _ = fit.sets[1]
-    k = min(int(k), P)
-    if k <= 0 or P == 0:
-        none = np.zeros(0, np.int64)
-        return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
-    if n:  # (the prepared set's head: log w (n + 1), then sigma and 1 / (sqrt(2) sigma))
-        sigma, sig_ptr = None, dset.data_ptr() + 8 * (n + 1)
-    else:
-        sig = lie_sigma(dj.models, 0, fit.bandwidth)
-        some = sig > 0.0
-        r = np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)
-        sigma = t.from_numpy(np.concatenate([sig, r])).to(eng.device)
-        sig_ptr = sigma.data_ptr()
-    # the rows, then their count: one readback
-    out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
-    scratch = t.empty(lib.tpe_joint_lie_scratch_bytes(P), dtype=t.uint8, device=eng.device)
-    at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
-    S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
-    _L.check(lib.tpe_joint_lie_picks(
-        dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models),
-        None if dj.tables is None else dj.tables.data_ptr(), dj.n_tables, sig_ptr,
-        d_vals.data_ptr(), ld, n_cols, P, S0.data_ptr(), A0.data_ptr(),
-        lie_log_total(n, fit.linear_forgetting, fit.prior_weight), math.log(lie_weight),
-        taken.data_ptr(), None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
-        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
-        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp), "tpe_joint_lie_picks")
-    got = out[:k + 1].cpu().numpy()
-    rows = got[:int(got[k])].copy()
-    if not trace:
-        return rows
-    return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
-
-
 class _LiePack(object):
-    """The groups of a tree fit as tpe_joint_lie_tree_picks takes them: the
-    label records concatenated in group order (``tab_off`` counted from the
-    start of the concatenated tables) on the host and on the device, the
-    tables, ``group_off``, log W_g, the liveness columns, and the sigmas.  Chain
-    fits (tpe_joint_lie_chain_picks) pack the same way: a fit's records are its
-    context's, then its own, ``n_ctx`` says how many lead, and the liveness column
-    is the first own label's."""
-    __slots__ = ("host", "dev", "tables", "n_tables", "off", "log_w", "col", "sigma", "n_ctx")
+    """The fits of a batch as tpe_joint_lie_chain_picks takes them: the label
+    records concatenated in fit order (``tab_off`` counted from the start of the
+    concatenated tables) on the host and on the device, the tables,
+    ``group_off``, log W_g, ``n_ctx`` (a fit's records are its context's, then
+    its own), the liveness columns (the first own label's; -1 for the root),
+    the sigmas, and ``fits`` itself."""
+    __slots__ = ("fits", "host", "dev", "tables", "n_tables", "off", "log_w", "col", "sigma",
+                 "n_ctx")
 
 
 def _lie_pack(fits):
-    """``_LiePack`` of ``fits`` (``fit(..., tree=True)`` or ``tree="chain"``),
-    made once per fit list and kept on its first fit."""
-    if fits[0].lie_pack is not None:
-        return fits[0].lie_pack
+    """``_LiePack`` of ``fits`` (``fit``'s list, or the joint labels' fit
+    alone), made once per fit list and kept on its first fit."""
+    pk = fits[0].lie_pack
+    if pk is not None and pk.fits == list(fits):  # (a JointFit equals itself alone)
+        return pk
     eng = fits[0].eng
     t = eng.torch
     recs, tabs, sig, off, base = [], [], [], [0], 0
@@ -1773,8 +1703,8 @@ def _lie_pack(fits):
         off.append(off[-1] + len(f.dj.models))
         sig.append(lie_sigma(f.dj.models, f.sets[1][1], f.bandwidth))
     sig = np.concatenate(sig)
-    some = sig > 0.0
     pk = _LiePack()
+    pk.fits = list(fits)
     pk.host = np.concatenate(recs)
     pk.dev = t.from_numpy(pk.host.view(np.uint8).copy()).to(eng.device)
     pk.tables, pk.n_tables = (t.cat(tabs) if tabs else None), base
@@ -1784,53 +1714,76 @@ def _lie_pack(fits):
     pk.n_ctx = np.asarray([f.n_ctx for f in fits], np.int32)
     pk.col = np.asarray([-1] + [f.dj.models[f.n_ctx].col for f in fits[1:]], np.int32)
     # (no label with a bandwidth: the call takes no sigmas)
-    pk.sigma = t.from_numpy(np.concatenate(
-        [sig, np.where(some, 1.0 / (math.sqrt(2.0) * np.where(some, sig, 1.0)), 0.0)])
-    ).to(eng.device) if some.any() else None
+    pk.sigma = (t.from_numpy(np.concatenate([sig, _inv_sqrt2_sigma(sig)])).to(eng.device)
+                if (sig > 0.0).any() else None)
     fits[0].lie_pack = pk
     return pk
 
 
-def liar_tree_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, taken, distinct, k, lie_weight,
-                     trace=False, rows_out=None):
-    """The batch of module doc "Batches in a tree" for rows [0, P) of the
-    label-major device pool ``d_vals`` / ``d_active``: ``liar_device`` with
-    ``fits`` the tree fits (``fit(..., tree=True)``) and ``A`` the (G, >= P)
-    device tensor ``score_tree_device(above=)`` filled.  One
-    tpe_joint_lie_tree_picks, one readback.  ValueError past
-    ``TPE_COND_MAX_LABELS`` groups, or labels over all the groups."""
+def _liar_picks_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, B, taken, distinct, k,
+                       lie_weight, trace, rows_out):
+    """The k picks of a batch over ``fits`` for rows [0, P) of the label-major
+    device pool ``d_vals`` / ``d_active``: the picks in order (numpy int64, at
+    most k), all enqueued by one tpe_joint_lie_chain_picks -- the joint labels'
+    fit alone is its G = 1, tree fits are its fits without a context -- and read
+    back once.  ``S0``: the score, a device vector (>= P doubles); ``A`` / ``B``:
+    log L_above and log L_ctx,above per fit, (G, >= P) (one fit: a vector; ``B``
+    is read where a fit has a context); ``taken`` / ``distinct``: device byte
+    masks (``distinct`` may be None).  None of them is written.  ``trace``:
+    (rows, S_at_pick, S_k) as ``liar_numpy`` returns them.  ``rows_out``: a
+    device int64 tensor of more than k entries to receive the rows (and, at
+    entry k, their count) where the caller reads them on the device afterwards."""
     eng, sp = fits[0].eng, fits[0].sp
     t, lib = eng.torch, eng.lib
     k = min(int(k), P)
     if k <= 0 or P == 0:
         none = np.zeros(0, np.int64)
         return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
-    G, D_tot = len(fits), sum(len(f.dj.models) for f in fits)
-    if G > _L.COND_MAX_LABELS or D_tot > _L.COND_MAX_LABELS:
-        raise ValueError("batch='liar-tree': %d groups of %d labels in all, at most %d of either"
-                         % (G, D_tot, _L.COND_MAX_LABELS))
     pk = _lie_pack(fits)
+    G, n_v = len(fits), int((pk.n_ctx > 0).sum())
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    # the rows, then their count: one readback
     out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
-    scratch = t.empty(lib.tpe_joint_lie_tree_scratch_bytes(P, G), dtype=t.uint8,
+    scratch = t.empty(lib.tpe_joint_lie_chain_scratch_bytes(P, G, n_v), dtype=t.uint8,
                       device=eng.device)
     at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
     S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
-    _L.check(lib.tpe_joint_lie_tree_picks(
-        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host),
-        None if pk.tables is None else pk.tables.data_ptr(), pk.n_tables, pk.off.ctypes.data,
-        pk.log_w.ctypes.data, pk.col.ctypes.data, G,
-        None if pk.sigma is None else pk.sigma.data_ptr(), d_vals.data_ptr(),
-        d_active.data_ptr(), ld, n_cols, P, S0.data_ptr(), A.data_ptr(), A.shape[1],
-        math.log(lie_weight), taken.data_ptr(),
-        None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
-        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
-        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp),
-        "tpe_joint_lie_tree_picks")
+    _L.check(lib.tpe_joint_lie_chain_picks(
+        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host), ptr(pk.tables), pk.n_tables,
+        pk.off.ctypes.data, pk.log_w.ctypes.data, pk.col.ctypes.data, pk.n_ctx.ctypes.data, G,
+        ptr(pk.sigma), d_vals.data_ptr(), ptr(d_active), ld, n_cols, P, S0.data_ptr(),
+        A.data_ptr(), A.shape[-1], ptr(B) if n_v else None, B.shape[-1] if n_v else 0,
+        math.log(lie_weight), taken.data_ptr(), ptr(distinct), k, out.data_ptr(),
+        out.data_ptr() + 8 * k, ptr(at), ptr(S_k), scratch.data_ptr(), sp),
+        "tpe_joint_lie_chain_picks")
     got = out[:k + 1].cpu().numpy()
     rows = got[:int(got[k])].copy()
     if not trace:
         return rows
     return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
+
+
+def liar_device(fit, d_vals, ld, n_cols, P, S0, A0, taken, distinct, k, lie_weight, trace=False,
+                rows_out=None):
+    """The batch of module doc "Batches": ``_liar_picks_device`` over ``fit``
+    alone, the joint labels' fit, whose above set lends its bandwidths; ``A0``: a
+    device vector (>= P doubles) of log L_above."""
+    return _liar_picks_device([fit], d_vals, None, ld, n_cols, P, S0, A0, None, taken, distinct,
+                              k, lie_weight, trace, rows_out)
+
+
+def liar_tree_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, taken, distinct, k, lie_weight,
+                     trace=False, rows_out=None):
+    """The batch of module doc "Batches in a tree": ``_liar_picks_device`` over
+    the tree fits (``fit(..., tree=True)``), ``A`` the (G, >= P) device tensor
+    ``score_tree_device(above=)`` filled.  ValueError past
+    ``TPE_COND_MAX_LABELS`` groups, or labels over all the groups."""
+    G, D_tot = len(fits), sum(len(f.dj.models) for f in fits)
+    if min(int(k), P) > 0 and (G > _L.COND_MAX_LABELS or D_tot > _L.COND_MAX_LABELS):
+        raise ValueError("batch='liar-tree': %d groups of %d labels in all, at most %d of either"
+                         % (G, D_tot, _L.COND_MAX_LABELS))
+    return _liar_picks_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, None, taken, distinct,
+                              k, lie_weight, trace, rows_out)
 
 
 def check_chain_lie_limits(groups, contexts):
@@ -1846,45 +1799,16 @@ def check_chain_lie_limits(groups, contexts):
 
 def liar_chain_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, B, taken, distinct, k,
                       lie_weight, trace=False, rows_out=None):
-    """The batch of module doc "Batches in a chain" for rows [0, P) of the
-    label-major device pool ``d_vals`` / ``d_active``: ``liar_tree_device`` with
-    ``fits`` the chain fits (``fit(..., tree="chain")``) and ``A`` / ``B`` the (G,
-    >= P) device tensors ``score_tree_device(above=, above_ctx=)`` filled.  One
-    tpe_joint_lie_chain_picks, one readback.  ValueError past
-    ``TPE_COND_MAX_LABELS`` groups, or records over all the fits, before
+    """The batch of module doc "Batches in a chain": ``_liar_picks_device`` over
+    the chain fits (``fit(..., tree="chain")``), ``A`` / ``B`` the (G, >= P)
+    device tensors ``score_tree_device(above=, above_ctx=)`` filled.  ValueError
+    past ``TPE_COND_MAX_LABELS`` groups, or records over all the fits, before
     anything is packed."""
-    eng, sp = fits[0].eng, fits[0].sp
-    t, lib = eng.torch, eng.lib
-    k = min(int(k), P)
-    if k <= 0 or P == 0:
-        none = np.zeros(0, np.int64)
-        return (none, np.zeros(0), S0[:P].cpu().numpy()) if trace else none
-    check_chain_lie_limits([f.dj.models[f.n_ctx:] for f in fits],
-                           [f.dj.models[:f.n_ctx] for f in fits])
-    pk = _lie_pack(fits)
-    G, n_v = len(fits), int((pk.n_ctx > 0).sum())
-    out = t.empty(k + 1, dtype=t.int64, device=eng.device) if rows_out is None else rows_out
-    scratch = t.empty(lib.tpe_joint_lie_chain_scratch_bytes(P, G, n_v), dtype=t.uint8,
-                      device=eng.device)
-    at = t.empty(k, dtype=t.float64, device=eng.device) if trace else None
-    S_k = t.empty(P, dtype=t.float64, device=eng.device) if trace else None
-    _L.check(lib.tpe_joint_lie_chain_picks(
-        pk.host.ctypes.data, pk.dev.data_ptr(), len(pk.host),
-        None if pk.tables is None else pk.tables.data_ptr(), pk.n_tables, pk.off.ctypes.data,
-        pk.log_w.ctypes.data, pk.col.ctypes.data, pk.n_ctx.ctypes.data, G,
-        None if pk.sigma is None else pk.sigma.data_ptr(), d_vals.data_ptr(),
-        d_active.data_ptr(), ld, n_cols, P, S0.data_ptr(), A.data_ptr(), A.shape[1],
-        B.data_ptr() if n_v else None, B.shape[1] if n_v else 0,
-        math.log(lie_weight), taken.data_ptr(),
-        None if distinct is None else distinct.data_ptr(), k, out.data_ptr(),
-        out.data_ptr() + 8 * k, None if at is None else at.data_ptr(),
-        None if S_k is None else S_k.data_ptr(), scratch.data_ptr(), sp),
-        "tpe_joint_lie_chain_picks")
-    got = out[:k + 1].cpu().numpy()
-    rows = got[:int(got[k])].copy()
-    if not trace:
-        return rows
-    return rows, at.cpu().numpy()[:rows.size], S_k.cpu().numpy()
+    if min(int(k), P) > 0:
+        check_chain_lie_limits([f.dj.models[f.n_ctx:] for f in fits],
+                               [f.dj.models[:f.n_ctx] for f in fits])
+    return _liar_picks_device(fits, d_vals, d_active, ld, n_cols, P, S0, A, B, taken, distinct,
+                              k, lie_weight, trace, rows_out)
 
 
 def refine_device(fit, d_block, ld, n_cols, k, refine, trace=None):

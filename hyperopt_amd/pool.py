@@ -65,15 +65,16 @@ interacts with a branch label; its sampled pools draw the rows of ``"tree"``.
 with ``joint=True`` on a ``Pool`` / ``SampledPool``) makes the k rows of one
 call see each other: the top-k of one score is replaced by k picks made one
 after the other on the device, each joining the above mixture as the pending
-trial it is about to become (joint.py "Batches"; csrc/tpe_joint_lie.hip).  The
-host still reads back the k rows only, once.  ``batch="liar-tree"`` (with
+trial it is about to become (joint.py "Batches").  The host still reads back
+the k rows only, once.  ``batch="liar-tree"`` (with
 ``joint="tree"``) is that batch on a conditional space: the tree scoring keeps
 log L_above per group, and a pick lies in every group it is live in (joint.py
-"Batches in a tree"; csrc/tpe_joint_lie_tree.hip).  ``batch="liar-chain"`` (with
+"Batches in a tree").  ``batch="liar-chain"`` (with
 ``joint="chain"``) is the batch under the chain criterion: the scoring keeps log
 L_above and log L_ctx,above per chain fit, and a pick joins each fit's mixture and
-its context marginal at once (joint.py "Batches in a chain";
-csrc/tpe_joint_lie_chain.hip).
+its context marginal at once (joint.py "Batches in a chain").  The three are
+one engine (csrc/tpe_joint_lie.hip) entered in three ways: a flat space is a
+tree of one group, a tree a chain whose contexts are all empty.
 """
 from __future__ import annotations
 
@@ -1576,11 +1577,13 @@ def _settings(prior_weight, gamma, lf, joint=False, bandwidth=_J.BANDWIDTH,
 
 
 def _liar_device(eng, d, P, k, mask, lie_weight, trace=False, tree=False):
-    """``_topk_device`` for ``batch="liar"``: the rows of ``joint.liar_device``
-    on d.S, with the fit and the log L_above the scoring left in the mirror
-    (``_joint_device``); ``mask``: ``distinct``'s device mask or None.  The rows
-    stay in d.rows_out.  ``tree`` (``st.lie_tree``, ``batch="liar-tree"``): the
-    rows of ``joint.liar_tree_device`` on the tree fits and ``d.above``."""
+    """``_topk_device`` for a liar batch: its rows on d.S, with the fits and the
+    log L_above the scoring left in the mirror (``_joint_device``); ``mask``:
+    ``distinct``'s device mask or None.  The rows stay in d.rows_out.  ``tree``,
+    the settings' ``joint["tree"]``, names the joint entry: False
+    ``joint.liar_device`` (``batch="liar"``), True ``joint.liar_tree_device`` on
+    ``d.above`` (``"liar-tree"``), "chain" ``joint.liar_chain_device`` on
+    ``d.above`` and ``d.above_ctx`` (``"liar-chain"``)."""
     t = eng.torch
     k = min(int(k), P)
     if d.rows_out is None or d.rows_out.numel() < k + 1:
@@ -1588,42 +1591,28 @@ def _liar_device(eng, d, P, k, mask, lie_weight, trace=False, tree=False):
         # entry k of the rows, read back with them)
         d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
         d.count = t.zeros(1, dtype=t.int64, device=eng.device)
+    ld, n_cols = d.vals.shape[1], d.vals.shape[0]
+    tail = (d.taken, mask, k, lie_weight, trace, d.rows_out)
+    if tree == "chain":
+        return _J.liar_chain_device(d.fits, d.vals, d.active, ld, n_cols, P, d.S, d.above,
+                                    d.above_ctx, *tail)
     if tree:
-        return _J.liar_tree_device(d.fits, d.vals, d.active, d.vals.shape[1], d.vals.shape[0], P,
-                                   d.S, d.above, d.taken, mask, k, lie_weight, trace, d.rows_out)
-    return _J.liar_device(d.fits[0], d.vals, d.vals.shape[1], d.vals.shape[0], P, d.S, d.parts[1],
-                          d.taken, mask, k, lie_weight, trace, d.rows_out)
-
-
-def _liar_chain_device(eng, d, P, k, mask, lie_weight, trace=False):
-    """``_liar_device`` for ``batch="liar-chain"``: the rows of
-    ``joint.liar_chain_device`` on d.S, with the chain fits, ``d.above`` and
-    ``d.above_ctx`` the scoring left in the mirror.  The rows stay in d.rows_out."""
-    t = eng.torch
-    k = min(int(k), P)
-    if d.rows_out is None or d.rows_out.numel() < k + 1:
-        d.rows_out = t.empty(k + 1, dtype=t.int64, device=eng.device)
-        d.count = t.zeros(1, dtype=t.int64, device=eng.device)
-    return _J.liar_chain_device(d.fits, d.vals, d.active, d.vals.shape[1], d.vals.shape[0], P, d.S,
-                                d.above, d.above_ctx, d.taken, mask, k, lie_weight, trace,
-                                d.rows_out)
+        return _J.liar_tree_device(d.fits, d.vals, d.active, ld, n_cols, P, d.S, d.above, *tail)
+    return _J.liar_device(d.fits[0], d.vals, ld, n_cols, P, d.S, d.parts[1], *tail)
 
 
 def _pick(eng, pool, d, k, hist, distinct, st, trace=False):
     """The k rows to hand out, by the scores in the mirror ``d``: the first k
-    untaken rows by d.S (``_topk_device``), or with ``st.lie`` the liar batch
-    (``_liar_device``, under ``st.lie_chain`` ``_liar_chain_device``; ``trace``:
-    its (rows, S_at_pick, S_k)).  ``distinct``:
-    fresh rows only (``_distinct_device`` against ``hist``).  The rows stay in
-    d.rows_out."""
+    untaken rows by d.S (``_topk_device``), or with ``st.lie`` the liar batch of
+    the joint criterion in force (``_liar_device``; ``trace``: its (rows,
+    S_at_pick, S_k)).  ``distinct``: fresh rows only (``_distinct_device``
+    against ``hist``).  The rows stay in d.rows_out."""
     if distinct:
         _distinct_device(eng, pool, d, hist)
     mask = d.mask if distinct else None
     if st.lie is None:
         return _topk_device(eng, d, len(pool), k, mask)
-    if st.lie_chain:
-        return _liar_chain_device(eng, d, len(pool), k, mask, st.lie, trace)
-    return _liar_device(eng, d, len(pool), k, mask, st.lie, trace, st.lie_tree)
+    return _liar_device(eng, d, len(pool), k, mask, st.lie, trace, st.joint["tree"])
 
 
 def pick_batch(domain, trials, pool, k, distinct=False, return_trace=False, lie_weight=1.0,

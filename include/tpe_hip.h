@@ -1129,7 +1129,13 @@ int tpe_joint_chain_rows_keep(const tpe_joint_label* host_labels, const tpe_join
  * the block a row falls in or block scheduling; no floating-point atomics.
  * Limits as tpe_joint_score (TPE_E_UNSUPPORTED); bad arguments return TPE_E_ARG
  * before any launch; k <= 0 or n_rows == 0 writes the count 0 (and S0 to S_k
- * where given).  Asynchronous on `stream`, no allocation. */
+ * where given).  Asynchronous on `stream`, no allocation.
+ *
+ * This entry and the two below are one engine (csrc/tpe_joint_lie.hip): it is
+ * tpe_joint_lie_tree_picks with one group of all the labels, live in every row,
+ * and that one is tpe_joint_lie_chain_picks with every n_ctx = 0.  The three run
+ * the same kernels, and the scratch sizes agree: lie(P) = tree(P, 1), tree(P, G) =
+ * chain(P, G, 0). */
 int64_t tpe_joint_lie_scratch_bytes(int64_t n_rows);
 int tpe_joint_lie_picks(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
                         int n_labels, const double* tables, int64_t n_tables,
@@ -1184,7 +1190,7 @@ int tpe_joint_lie_picks(const tpe_joint_label* host_labels, const tpe_joint_labe
  * (tpe_rows_compact's): the dense result of a tpe_joint_score_rows call with
  * out_mode 0, put where its rows are.  d_count is read on the device only; an
  * entry outside [0, ld) is skipped; dst holds ld doubles.  max_rows == 0 and
- * ld == 0 are no-ops. */
+ * ld == 0 are no-ops.  (csrc/tpe_joint_tree.hip, beside tpe_rows_compact.) */
 int64_t tpe_joint_lie_tree_scratch_bytes(int64_t n_rows, int n_groups);
 int tpe_joint_lie_tree_picks(const tpe_joint_label* host_labels, const tpe_joint_label* labels,
                              int n_labels, const double* tables, int64_t n_tables,

@@ -146,7 +146,7 @@ def test_the_calls_the_chain_batch_builds(monkeypatch):
     calls = []
     monkeypatch.setattr(pool_mod, "_score_device", lambda *a, **kw: calls.append(
         ("score", a[3], a[4:], set(kw))) or ("eng", "mirror"))
-    for name in ("_topk_device", "_liar_device", "_liar_chain_device"):
+    for name in ("_topk_device", "_liar_device"):
         monkeypatch.setattr(pool_mod, name, lambda *a, name=name: calls.append(
             (name, a)) or np.asarray([6, 2]))
     tpe.suggest_from_pool([100, 101], domain, trials, 0, pool=pool, joint="chain",
@@ -155,4 +155,4 @@ def test_the_calls_the_chain_batch_builds(monkeypatch):
     assert rest == (False,) and kws == {"hist"}
     assert st.joint == dict(bandwidth=J.BANDWIDTH, cat_smoothing=J.CAT_SMOOTHING, tree="chain")
     assert (st.lie, st.lie_tree, st.lie_chain) == (2.0, False, True)
-    assert (which, args) == ("_liar_chain_device", ("eng", "mirror", 8, 2, None, 2.0, False))
+    assert (which, args) == ("_liar_device", ("eng", "mirror", 8, 2, None, 2.0, False, "chain"))

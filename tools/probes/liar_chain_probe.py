@@ -1,13 +1,13 @@
 #!/usr/bin/env python
 """Times the liar batch under the chain criterion (batch="liar-chain",
-csrc/tpe_joint_lie_chain.hip) against the plain top-k on the C5 shape: the
+csrc/tpe_joint_lie.hip) against the plain top-k on the C5 shape: the
 ``nested`` space (tests/golden/spaces.py), P pool rows and a T-trial history
 sampled from its prior with uniform losses, same scored pool, same process,
 k = 8.
 
   topk        pool._topk_device: tpe_pool_topk of the k best rows of the chain S
               and the readback of the rows;
-  liar_chain  pool._liar_chain_device: tpe_joint_lie_chain_picks (k picks, each a
+  liar_chain  pool._liar_device(tree="chain"): one tpe_joint_lie_chain_picks (k picks, each a
               lie in every chain fit the pick is live in -- mixture and context
               marginal -- and a new argmax) and the one readback of the rows;
   score       one tpe.score_configs(joint="chain") of the pool; k of them is what
@@ -81,7 +81,7 @@ def main():
 
         fns = {
             "topk": lambda: pool_mod._topk_device(eng, d, P, k),
-            "liar_chain": lambda: pool_mod._liar_chain_device(eng, d, P, k, None, st.lie),
+            "liar_chain": lambda: pool_mod._liar_device(eng, d, P, k, None, st.lie, False, "chain"),
             "score": lambda: score(plain),
             "score_kept": lambda: score(st),
         }

@@ -7,7 +7,8 @@ and rows drawn from the joint below mixture (``Pool.sample(joint=True)``, what
 
   topk    pool._topk_device: tpe_pool_topk of the k best rows of S_0 and the
           readback of the rows -- what a call without ``batch`` does after scoring;
-  liar    pool._liar_device: tpe_joint_lie_picks (k picks, each a lie added to the
+  liar    pool._liar_device: one tpe_joint_lie_chain_picks over the joint labels' fit
+          alone (k picks, each a lie added to the
           above mixture and a new argmax) and the one readback of the rows;
   score   one tpe.score_configs(joint=True) of the pool; k of them is what
           re-scoring the pool after every pick would cost, for scale.

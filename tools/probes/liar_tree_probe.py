@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """Times the liar batch per group (batch="liar-tree",
-csrc/tpe_joint_lie_tree.hip) against the plain top-k on the C5 shape: the
+csrc/tpe_joint_lie.hip) against the plain top-k on the C5 shape: the
 ``nested`` space (tests/golden/spaces.py), P pool rows and a T-trial history
 sampled from its prior with uniform losses, same scored pool, same process,
 k = 8.
 
   topk        pool._topk_device: tpe_pool_topk of the k best rows of the tree S
               and the readback of the rows;
-  liar_tree   pool._liar_device: tpe_joint_lie_tree_picks (k picks, each a lie in
+  liar_tree   pool._liar_device(tree=True): one tpe_joint_lie_chain_picks over fits
+              without a context (k picks, each a lie in
               every group the pick is live in, and a new argmax) and the one
               readback of the rows;
   score       one tpe.score_configs(joint="tree") of the pool; k of them is what
