@@ -1,7 +1,7 @@
 // tpe_grid_joint.hip -- the joint Parzen criterion (tpe_joint.hip) on a block
 // of a grid pool (tpe_grid.hip), from per-axis factor tables.
 //
-// In the walk of tpe_joint_pass.hpp every joint label d adds to a_i a factor
+// In tpe_joint_pass.hpp's joint_walk every joint label d adds to a_i a factor
 // f_{d,i}(x_d) that depends on the label, the component and the label's value
 // alone.  On a grid x_d is one of the n_d values of the label's axis, so the
 // factors of a set form a table F of (sum_d n_d) x C doubles:
@@ -29,7 +29,7 @@
 //                           by the walk's statements (phase B).  The chunk's
 //                           (m, s) goes to scratch; after the set's last
 //                           component window a second kernel merges a row's
-//                           chunks (tpe_joint_pass.hpp's merge text).
+//                           chunks (tpe_joint_pass.hpp's joint_merge).
 //
 // The decode is tpe_grid.hip's: quotient and remainder of the tile's first row
 // once per (tile, label) in 64 bits; a row's digit then takes 32-bit
@@ -40,7 +40,7 @@
 //
 // A row's bits depend on the row, the set and kJChunk / kJPer alone: not on the
 // tile, the row window, the component windows or block scheduling.  No atomics.
-#include "tpe_joint.hpp"
+#include "tpe_joint_pass.hpp"
 
 namespace tpe {
 namespace {
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kJBS) void k_grid_joint_score(
         a[k + 1] = a[k + 1] + v.y;
       }
     }
-    // (from here on: the walk's statements, tpe_joint_pass.hpp)
+    // (from here on: the statements of tpe_joint_pass.hpp's joint_walk)
     // a place past the last component holds no component
 #pragma unroll
     for (int k = 0; k < kJPer; ++k)
@@ -246,8 +246,7 @@ __global__ __launch_bounds__(kJBS) void k_grid_joint_merge(const double2* __rest
                                                            double* __restrict__ out, int add) {
   const int64_t r = (int64_t)blockIdx.x * kJBS + threadIdx.x;
   if (r >= n_rows) return;
-#define TPE_JOINT_PASS_MERGE
-#include "tpe_joint_pass.hpp"
+  double v = joint_merge(partial, n_chunks, n_rows, r);
   if (sub) v = v - sub[r];
   out[r] = add ? out[r] + v : v;
 }

@@ -1,8 +1,8 @@
-// tpe_joint.hpp -- what the joint criterion's scorer (tpe_joint.hip), its
-// scorer by row list (tpe_joint_tree.hip) and its sampler
-// (tpe_joint_sample.hip) share: the layout of a prepared set, the fit
-// coordinate, the label checks of the entry points and the scorers' constants.
-// (The two scorers' one arithmetic is in tpe_joint_pass.hpp.)
+// tpe_joint.hpp -- what the joint criterion's scorers (tpe_joint.hip), its row
+// lists (tpe_joint_tree.hip) and its sampler (tpe_joint_sample.hip) share: the
+// layout of a prepared set, the fit coordinate, the label checks of the entry
+// points, the scorers' constants and the window of a device list of rows.
+// (The scorers' arithmetic, the walk and the merge: tpe_joint_pass.hpp.)
 #pragma once
 
 #include "tpe_common.hpp"
@@ -46,6 +46,17 @@ __host__ __device__ inline int64_t set_comp_off(int n_labels, int64_t C) {
 // the fit coordinate of a stored value
 __device__ __forceinline__ double fit_coord(double v, bool is_log) {
   return is_log ? log(fmax(v, kEps)) : v;
+}
+
+// chunks (partials per row) of a set of n trials and the prior
+inline int64_t joint_chunks(int64_t n) { return (n + 1 + kJChunk - 1) / kJChunk; }
+
+// how many list positions the window [list_begin, list_begin + max_rows) of a
+// device list holds (<= 0: none); the list's length stays on the device
+__device__ __forceinline__ int64_t window_rows(const int64_t* __restrict__ d_count,
+                                               int64_t list_begin, int64_t max_rows) {
+  const int64_t left = *d_count - list_begin;
+  return left < max_rows ? left : max_rows;
 }
 }  // namespace
 }  // namespace tpe

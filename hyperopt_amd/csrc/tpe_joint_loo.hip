@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kJBS) void k_loo_prep(const tpe_joint_label* __rest
     const double t = lab.kind == TPE_JOINT_CAT ? (double)llrint(x) : fit_coord(x, is_log);
     if (b == 0) mu[(int64_t)d * n + j] = t;
     if (lab.kind == TPE_JOINT_QUANT) {
-      if (b == 0) {  // (the edges of tpe_joint_pass.hpp's walk)
+      if (b == 0) {  // (the edges of tpe_joint_pass.hpp's joint_walk)
         const double lb = x - 0.5 * lab.q;
         double tu = fit_coord(x + 0.5 * lab.q, is_log), tl = fit_coord(lb, is_log);
         if (lab.flags & TPE_JOINT_BOUNDED) {

@@ -34,7 +34,7 @@
 //                 component (a rolled loop that rotates the two arrays) the B
 //                 exponents join their (m, s), one exp each.  j == i and the
 //                 places past n are reset to -inf before they can join.
-//   k_lool_merge  per row and b: tpe_joint_pass.hpp's merge over the chunks in
+//   k_lool_merge  per row and b: tpe_joint_pass.hpp's joint_merge over the chunks in
 //                 chunk order and the prior's slot last, minus log(W - v_i),
 //                 times v_i; a block tree over the rows.
 //   k_loo_final   (tpe_joint_loo.hpp) thread b: the blocks in block order.
@@ -43,6 +43,7 @@
 // label quantized): a list without a quantized label never calls log_mass.  No
 // atomics, every sum has a fixed order: out's bits depend on the inputs alone.
 #include "tpe_joint_loo.hpp"
+#include "tpe_joint_pass.hpp"
 
 namespace tpe {
 namespace {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(kJBS) void k_lool_prep(
       const double u = (t - lab.prior_mu) * lab.prior_r;
       prior = fma(-u, u, prior - log(lab.prior_sigma * sqrt(kTwoPi)));
       if (d != which) acc = acc - log(sigma * sqrt(kTwoPi));
-    } else {  // (the edges of tpe_joint_pass.hpp's walk)
+    } else {  // (the edges of tpe_joint_pass.hpp's joint_walk)
       coord[(int64_t)d * n + j] = t;
       const double lb = x - 0.5 * lab.q;
       double tu = fit_coord(x + 0.5 * lab.q, is_log), tl = fit_coord(lb, is_log);
@@ -286,13 +287,11 @@ __global__ __launch_bounds__(kJBS) void k_lool_merge(const double* __restrict__ 
   const bool live = r < n;
   const double vi = live ? wts[r] : 0.0;
   const double log_rest = log(W - vi);
-  const int64_t n_rows = n, n_chunks = n_slots;  // (the chunks, then the prior's slot)
   for (int b = 0; b < n_grid; ++b) {
     double val = 0.0;
     if (live) {
-      const double2* __restrict__ partial = all + (int64_t)b * n_slots * n;
-#define TPE_JOINT_PASS_MERGE
-#include "tpe_joint_pass.hpp"
+      // (the slots: the chunks, then the prior's)
+      const double v = joint_merge(all + (int64_t)b * n_slots * n, n_slots, n, r);
       val = vi * (v - log_rest);
     }
     __syncthreads();  // (the previous grid value's tree has been read)

@@ -1,24 +1,70 @@
-// tpe_joint_pass.hpp -- the arithmetic the joint criterion's two scorers share
-// (k_joint_score in tpe_joint.hip: a dense row window; k_joint_score_rows in
-// tpe_joint_tree.hip: a device list of rows), as text: a thread's walk over one
-// chunk of components, and a row's merge of its chunks.  Included inside the
-// kernels' bodies, once per part (define TPE_JOINT_PASS_WALK or
-// TPE_JOINT_PASS_MERGE first; no include guard).  Text, not a function: as an
-// inlined function the same statements gave k_joint_score another scalar
-// register assignment, and the dense scorer's code is to stay instruction for
-// instruction what it was.
-#if defined(TPE_JOINT_PASS_WALK)
-#undef TPE_JOINT_PASS_WALK
-// in:  labels, n_labels, tables, logw, sig, comp (the prepared set's parts), n,
-//      C = n + 1, vals, ld, row (the pool row this thread reads), i_first (the
-//      chunk's first component), tile (kJMaxD * kJPer JComp of LDS)
-// out: m, s -- the running maximum and sum of the chunk's a_i.  Every thread
-//      of the kJBS block walks it (it syncs on `tile`).
-// With TPE_JOINT_PASS_CTX defined (k_joint_chain_rows in tpe_joint_chain.hip,
-// which undefines it again) also in: n_ctx in (0, n_labels), and m_ctx = -inf,
-// s_ctx = 0 declared by the kernel; out: m_ctx, s_ctx -- the same running pair
-// over the a_i cut off after the first n_ctx labels.
-  double m = kNegInf, s = 0.0;
+// tpe_joint_pass.hpp -- the arithmetic of the joint criterion's scorers
+// (k_joint_rows / k_joint_rows_merge in tpe_joint.hip; the merge also in
+// tpe_grid_joint.hip and tpe_joint_loo_label.hip): a thread's walk over one
+// chunk of components, and a row's merge of its chunks.  Every sum has a fixed
+// order, so a row's bits depend on the row, the set and kJChunk / kJPer only.
+#pragma once
+
+#include "tpe_joint.hpp"
+
+namespace tpe {
+namespace {
+
+// a pass's a[] joins a running (m, s), in component order.  a[] comes back as
+// it was: the rolled loop (one exp body) rotates it by one place per step, so
+// every index is static and the array stays in registers.
+__device__ __forceinline__ void joint_join(double (&a)[kJPer], double& m, double& s) {
+  double pm = a[0];
+#pragma unroll
+  for (int k = 1; k < kJPer; ++k) pm = a[k] > pm ? a[k] : pm;
+  if (pm > m) {
+    s = s * exp(m - pm);  // (m = -inf: s is 0 and stays 0)
+    m = pm;
+  }
+#pragma unroll 1
+  for (int k = 0; k < kJPer; ++k) {
+    const double head = a[0];
+    s = s + (head == kNegInf ? 0.0 : exp(head - m));
+#pragma unroll
+    for (int j = 0; j + 1 < kJPer; ++j) a[j] = a[j + 1];
+    a[kJPer - 1] = head;
+  }
+}
+
+// a place past the last component holds no component: whatever the label loop
+// added to its -inf from the zero pad (a NaN where a factor was inf * 0), it
+// counts for nothing
+__device__ __forceinline__ void joint_clear_past(double (&a)[kJPer], int64_t i0, int64_t C) {
+#pragma unroll
+  for (int k = 0; k < kJPer; ++k)
+    if (i0 + k >= C) a[k] = kNegInf;
+}
+
+struct JWalk {  // the running maximum and sum of a chunk's a_i; with a context,
+  double m, s;  // the same pair over the a_i cut off after the first n_ctx labels
+  double m_ctx, s_ctx;
+};
+
+// A thread's walk over the chunk of components that starts at i_first, for
+// pool row `row`: passes of kJPer components whose a_i it keeps in registers,
+// labels outside, components inside, the pass's {mu, constant} pairs staged in
+// `tile` (kJMaxD * kJPer JComp of LDS) and read as broadcasts.  Every thread of
+// the kJBS block walks it (it syncs on `tile`).  set: a prepared set of n
+// trials.  kCtx: n_ctx in (0, n_labels); at the label boundary a[] holds the
+// a_i of the first n_ctx labels, which join (m_ctx, s_ctx), and the walk goes
+// on to the full a_i in the same registers.
+template <bool kCtx>
+__device__ __forceinline__ JWalk joint_walk(const tpe_joint_label* __restrict__ labels,
+                                            int n_labels, int n_ctx,
+                                            const double* __restrict__ tables,
+                                            const double* __restrict__ set, int64_t n,
+                                            const double* __restrict__ vals, int64_t ld,
+                                            int64_t row, int64_t i_first, JComp* tile) {
+  const int64_t C = n + 1;
+  const double* __restrict__ logw = set;
+  const double* __restrict__ sig = set + C;
+  const JComp* __restrict__ comp = reinterpret_cast<const JComp*>(set + set_comp_off(n_labels, C));
+  JWalk w{kNegInf, 0.0, kNegInf, 0.0};
   for (int64_t i0 = i_first; i0 < i_first + kJChunk && i0 < C; i0 += kJPer) {
     __syncthreads();  // (the previous pass has read the tile)
     for (int e = threadIdx.x; e < n_labels * kJPer; e += kJBS) {
@@ -31,32 +77,12 @@
     for (int k = 0; k < kJPer; ++k) a[k] = i0 + k < C ? logw[i0 + k] : kNegInf;
     const int k_prior = n - i0 < kJPer ? (int)(n - i0) : -1;  // the prior's place in this pass
     for (int d = 0; d < n_labels; ++d) {
-#if defined(TPE_JOINT_PASS_CTX)
-      // (k_joint_chain_rows alone defines it: the two scorers' text is unchanged)
-      // at the label boundary a[] holds the a_i of the first n_ctx labels: it
-      // joins a second running (m_ctx, s_ctx) by the pass's join below, word
-      // for word, and the walk goes on to the full a_i in the same registers
-      if (d == n_ctx) {
-#pragma unroll
-        for (int k = 0; k < kJPer; ++k)
-          if (i0 + k >= C) a[k] = kNegInf;
-        double pm = a[0];
-#pragma unroll
-        for (int k = 1; k < kJPer; ++k) pm = a[k] > pm ? a[k] : pm;
-        if (pm > m_ctx) {
-          s_ctx = s_ctx * exp(m_ctx - pm);
-          m_ctx = pm;
-        }
-#pragma unroll 1
-        for (int k = 0; k < kJPer; ++k) {
-          const double head = a[0];
-          s_ctx = s_ctx + (head == kNegInf ? 0.0 : exp(head - m_ctx));
-#pragma unroll
-          for (int j = 0; j + 1 < kJPer; ++j) a[j] = a[j + 1];
-          a[kJPer - 1] = head;
+      if constexpr (kCtx) {
+        if (d == n_ctx) {
+          joint_clear_past(a, i0, C);
+          joint_join(a, w.m_ctx, w.s_ctx);
         }
       }
-#endif
       const tpe_joint_label lab = labels[d];
       const double x = vals[(int64_t)lab.col * ld + row];
       const JComp* __restrict__ t = tile + d * kJPer;
@@ -104,44 +130,27 @@
           a[k] = a[k] + (k == k_prior ? lp : (t[k].mu == xc ? hit : miss));
       }
     }
-    // a place past the last component holds no component: whatever the label
-    // loop added to its -inf from the zero pad (a NaN where a factor was
-    // inf * 0), it counts for nothing
-#pragma unroll
-    for (int k = 0; k < kJPer; ++k)
-      if (i0 + k >= C) a[k] = kNegInf;
-    // the pass joins the running (m, s), in component order
-    double pm = a[0];
-#pragma unroll
-    for (int k = 1; k < kJPer; ++k) pm = a[k] > pm ? a[k] : pm;
-    if (pm > m) {
-      s = s * exp(m - pm);  // (m = -inf: s is 0 and stays 0)
-      m = pm;
-    }
-#pragma unroll 1  // (rolled like the quantized loop: one exp body, a[] rotates)
-    for (int k = 0; k < kJPer; ++k) {
-      const double head = a[0];
-      s = s + (head == kNegInf ? 0.0 : exp(head - m));
-#pragma unroll
-      for (int j = 0; j + 1 < kJPer; ++j) a[j] = a[j + 1];
-      a[kJPer - 1] = head;
-    }
+    joint_clear_past(a, i0, C);
+    joint_join(a, w.m, w.s);
   }
-#elif defined(TPE_JOINT_PASS_MERGE)
-#undef TPE_JOINT_PASS_MERGE
-// in:  partial, n_chunks, n_rows (the partials' stride), r (the list position)
-// out: v = log L from the row's partials in chunk order
+  return w;
+}
+
+// log L of list position r from its (m, s) partials, in chunk order
+// (partial[c * stride + r]); -inf when every chunk's maximum is
+__device__ __forceinline__ double joint_merge(const double2* __restrict__ partial,
+                                              int64_t n_chunks, int64_t stride, int64_t r) {
   double m = kNegInf;
   for (int64_t c = 0; c < n_chunks; ++c) {
-    const double pm = partial[c * n_rows + r].x;
+    const double pm = partial[c * stride + r].x;
     m = pm > m ? pm : m;
   }
   double s = 0.0;
   for (int64_t c = 0; c < n_chunks; ++c) {
-    const double2 p = partial[c * n_rows + r];
+    const double2 p = partial[c * stride + r];
     s = s + (p.x == kNegInf ? 0.0 : p.y * exp(p.x - m));
   }
-  double v = m == kNegInf ? kNegInf : m + log(s);
-#else
-#error "tpe_joint_pass.hpp: define TPE_JOINT_PASS_WALK or TPE_JOINT_PASS_MERGE"
-#endif
+  return m == kNegInf ? kNegInf : m + log(s);
+}
+}  // namespace
+}  // namespace tpe

@@ -249,7 +249,7 @@ __device__ __forceinline__ void refine_setup(const tpe_joint_label* __restrict__
     const double v = vals[(int64_t)lab.col * ld + row];
     x.kind = lab.kind;
     x.prior_sigma = lab.prior_sigma;
-    if (lab.kind == TPE_JOINT_QUANT) {  // (the edges of tpe_joint_pass.hpp's walk)
+    if (lab.kind == TPE_JOINT_QUANT) {  // (the edges of tpe_joint_pass.hpp's joint_walk)
       const bool is_log = (lab.flags & TPE_JOINT_LOG) != 0;
       const double lb = v - 0.5 * lab.q;
       double tu = fit_coord(v + 0.5 * lab.q, is_log), tl = fit_coord(lb, is_log);

@@ -194,7 +194,7 @@ fits (``_lie_pack``) and makes the one call, tpe_joint_lie_chain_picks, for
 csrc/tpe_joint_lie.hip holds one driver and one kernel pair behind the three C
 entries.  The three model texts are the specification of their mode.
 
-Chains (``joint="chain"``, csrc/tpe_joint_chain.hip).  The
+Chains (``joint="chain"``, csrc/tpe_joint.hip).  The
 groups above are independent mixtures: a label at the root (a tile size) that
 is good only together with a label inside one branch (that variant's unroll
 factor) is ranked by two separate terms.  ``joint="chain"`` conditions every
@@ -1605,6 +1605,76 @@ def fit(eng, domain, hist, seen, gamma, n_cols, prior_weight, linear_forgetting,
     return fits
 
 
+def _score_fit(fit, d_vals, ld, n_cols, P, out, listed=None, above_to=None, ctx_to=None,
+               below_to=None, j_to=None):
+    """J of one fit, per window of ``ROWS_PER_CALL`` rows: the above set's value
+    into a temporary, the below set's minus it into ``out``.
+
+    Dense (``listed`` None): rows [0, P) by tpe_joint_score, ``out[r]`` = J.
+    ``above_to``: a device vector (>= P) that takes the temporary's place, so
+    log L_above stays; ``below_to``: a device vector (>= P) that receives log
+    L_below, by one more call.
+
+    ``listed`` = (rows, count), a device list of pool rows and its length:
+    windows of list positions by tpe_joint_score_rows, J added to ``out`` at
+    the listed rows; a fit with a context takes tpe_joint_chain_rows, and J is
+    C_g.  ``j_to``: a device vector that receives J itself at the listed rows,
+    by one more call.  ``above_to`` receives log L_above at the listed rows: the
+    temporary by one tpe_rows_scatter per window, or with a context from the
+    merge that forms it (tpe_joint_chain_rows_keep), which leaves log L_ctx,above
+    in ``ctx_to`` where that is given."""
+    eng, dj, sets, sp, n_ctx = fit.eng, fit.dj, fit.sets, fit.sp, fit.n_ctx
+    t, lib = eng.torch, eng.lib
+    labels = (dj.host.ctypes.data, dj.dev.data_ptr(), len(dj.models))
+    pool = (d_vals.data_ptr(), ld, n_cols)
+    tab = None if dj.tables is None else dj.tables.data_ptr()
+    win = min(max(P, 1), ROWS_PER_CALL)
+    size = lib.tpe_joint_chain_scratch_bytes if n_ctx else lib.tpe_joint_scratch_bytes
+    scratch = t.empty(max(max(size(win, n) for _, n, _ in sets), 16), dtype=t.uint8,
+                      device=eng.device)
+    dense_to = None if listed is not None else above_to
+    temp = t.empty(win, dtype=t.float64, device=eng.device) if dense_to is None else None
+    lst = () if listed is None else (listed[0].data_ptr(), listed[1].data_ptr())
+    end = (scratch.data_ptr(), sp)
+    kept = None
+    if lst and n_ctx and above_to is not None:
+        # (the kept vectors' common length: no row past either is written)
+        kept = (above_to.data_ptr(), None if ctx_to is None else ctx_to.data_ptr(),
+                min(v.shape[0] for v in (above_to, ctx_to) if v is not None))
+
+    def score(which, r0, sub, dst, mode=0, keep=None):
+        dset, n, _ = sets[which]
+        data = (tab, dj.n_tables, dset.data_ptr(), n) + pool + lst + (r0, min(win, P - r0), sub, dst)
+        if not lst:
+            _L.check(lib.tpe_joint_score(*labels, *data, *end), "tpe_joint_score")
+        elif not n_ctx:
+            _L.check(lib.tpe_joint_score_rows(*labels, *data, mode, *end), "tpe_joint_score_rows")
+        elif keep is None:
+            _L.check(lib.tpe_joint_chain_rows(*labels, n_ctx, *data, mode, *end),
+                     "tpe_joint_chain_rows")
+        else:  # (the two values the merge subtracts stay)
+            _L.check(lib.tpe_joint_chain_rows_keep(*labels, n_ctx, *data, mode, *keep, *end),
+                     "tpe_joint_chain_rows_keep")
+
+    for r0 in range(0, P, win):
+        # above first: the below call subtracts it
+        la = temp.data_ptr() if dense_to is None else dense_to.data_ptr() + 8 * r0
+        score(1, r0, None, la, keep=kept)
+        if not lst:
+            if below_to is not None:
+                # log L_below by itself costs one more call: J keeps the bits of the
+                # call without it because it is made by the same call
+                score(0, r0, None, below_to.data_ptr() + 8 * r0)
+            score(0, r0, la, out.data_ptr() + 8 * r0)
+            continue
+        if above_to is not None and kept is None:
+            _L.check(lib.tpe_rows_scatter(la, *lst, r0, min(win, P - r0), above_to.data_ptr(),
+                                          above_to.shape[0], sp), "tpe_rows_scatter")
+        if j_to is not None:  # (the same call as the one added to S: the same bits)
+            score(0, r0, la, j_to.data_ptr(), _L.JOINT_OUT_SCATTER)
+        score(0, r0, la, out.data_ptr(), _L.JOINT_OUT_SCATTER | _L.JOINT_OUT_ADD)
+
+
 def score_device(fit, d_vals, ld, n_cols, P, out, parts=None, keep_above=None):
     """J of rows [0, P) of the label-major device pool ``d_vals`` (leading
     dimension ``ld``, ``n_cols`` columns) under ``fit`` into the device vector
@@ -1612,37 +1682,10 @@ def score_device(fit, d_vals, ld, n_cols, P, out, parts=None, keep_above=None):
     log L_below and log L_above.  ``keep_above`` (without ``parts``): a device
     vector (>= P doubles) that takes the temporary's place, so log L_above stays
     -- the same calls."""
-    eng, dj, sets, sp = fit.eng, fit.dj, fit.sets, fit.sp
-    t, lib = eng.torch, eng.lib
-    D = len(dj.models)
-    tab = None if dj.tables is None else dj.tables.data_ptr()
-    win = min(max(P, 1), ROWS_PER_CALL)
-    need = max(lib.tpe_joint_scratch_bytes(win, n) for _, n, _ in sets)
-    scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
-    above = None
-    if parts is None and keep_above is None:
-        above = t.empty(win, dtype=t.float64, device=eng.device)
-
-    def score(which, r0, k, sub, dst):
-        dset, n, _ = sets[which]
-        _L.check(lib.tpe_joint_score(dj.host.ctypes.data, dj.dev.data_ptr(), D, tab, dj.n_tables,
-                                     dset.data_ptr(), n, d_vals.data_ptr(), ld, n_cols, r0, k,
-                                     sub, dst, scratch.data_ptr(), sp), "tpe_joint_score")
-
-    for r0 in range(0, P, win):
-        k = min(win, P - r0)
-        # above first: the below call subtracts it (with ``parts`` it lands in
-        # row 1 and is the subtrahend from there)
-        if parts is not None:
-            la = parts[1].data_ptr() + 8 * r0
-        else:
-            la = above.data_ptr() if keep_above is None else keep_above.data_ptr() + 8 * r0
-        score(1, r0, k, None, la)
-        if parts is not None:
-            # log L_below by itself costs one more call: J keeps the bits of the
-            # call without ``parts`` because it is made by the same call
-            score(0, r0, k, None, parts[0].data_ptr() + 8 * r0)
-        score(0, r0, k, la, out.data_ptr() + 8 * r0)
+    if parts is not None:
+        _score_fit(fit, d_vals, ld, n_cols, P, out, above_to=parts[1], below_to=parts[0])
+    else:
+        _score_fit(fit, d_vals, ld, n_cols, P, out, above_to=keep_above)
 
 
 def sample_device(fit, seed, d_vals, ld, n_cols, row_base, n_rows, comp_out=None, comp_key=None):
@@ -2071,63 +2114,22 @@ def score_tree_device(fits, d_vals, d_active, ld, n_cols, P, out, parts=None, ab
     ``above[g]`` as above.  Both None: exactly the calls above."""
     eng = fits[0].eng
     t, lib = eng.torch, eng.lib
-    if above is None:
-        score_device(fits[0], d_vals, ld, n_cols, P, out)
-    else:
-        score_device(fits[0], d_vals, ld, n_cols, P, out, keep_above=above[0])
+    score_device(fits[0], d_vals, ld, n_cols, P, out, keep_above=None if above is None else above[0])
     if parts is not None:
         parts[0, :P].copy_(out[:P])
     if len(fits) == 1 or P == 0:
         return
-    win = min(P, ROWS_PER_CALL)
-    need = max((lib.tpe_joint_chain_scratch_bytes if f.n_ctx else lib.tpe_joint_scratch_bytes)
-               (win, n) for f in fits[1:] for _, n, _ in f.sets)
-    scratch = t.empty(max(need, 16), dtype=t.uint8, device=eng.device)
-    dense = t.empty(win, dtype=t.float64, device=eng.device)
     rows = t.empty(P, dtype=t.int64, device=eng.device)
     count = t.empty(1, dtype=t.int64, device=eng.device)
     cscratch = t.empty(lib.tpe_rows_compact_scratch_bytes(P), dtype=t.uint8, device=eng.device)
-    both = _L.JOINT_OUT_SCATTER | _L.JOINT_OUT_ADD
-    # (the kept vectors' common length: no row past either is written)
-    keep_ld = min(m.shape[1] for m in (above, above_ctx) if m is not None) if above is not None \
-        else 0
     for g, f in enumerate(fits[1:], 1):
-        dj, sets, sp = f.dj, f.sets, f.sp
-        D = len(dj.models)
-        tab = None if dj.tables is None else dj.tables.data_ptr()
-        n_ctx = f.n_ctx
-        flags = d_active.data_ptr() + dj.models[n_ctx].col * ld
+        flags = d_active.data_ptr() + f.dj.models[f.n_ctx].col * ld
         _L.check(lib.tpe_rows_compact(flags, P, rows.data_ptr(), count.data_ptr(),
-                                      cscratch.data_ptr(), sp), "tpe_rows_compact")
-
-        keep = above is not None and n_ctx
-
-        def score(which, p0, sub, dst, mode):
-            dset, n, _ = sets[which]
-            head = (dj.host.ctypes.data, dj.dev.data_ptr(), D)
-            tail = (tab, dj.n_tables, dset.data_ptr(), n, d_vals.data_ptr(), ld, n_cols,
-                    rows.data_ptr(), count.data_ptr(), p0, min(win, P - p0), sub, dst, mode,
-                    scratch.data_ptr(), sp)
-            if keep and which == 1:  # (the two values the merge subtracts stay)
-                kept = (above[g].data_ptr(),
-                        None if above_ctx is None else above_ctx[g].data_ptr(), keep_ld)
-                _L.check(lib.tpe_joint_chain_rows_keep(*(head + (n_ctx,) + tail[:-2] + kept +
-                                                         tail[-2:])), "tpe_joint_chain_rows_keep")
-            elif n_ctx:
-                _L.check(lib.tpe_joint_chain_rows(*(head + (n_ctx,) + tail)),
-                         "tpe_joint_chain_rows")
-            else:
-                _L.check(lib.tpe_joint_score_rows(*(head + tail)), "tpe_joint_score_rows")
-
-        for p0 in range(0, P, win):
-            score(1, p0, None, dense.data_ptr(), 0)
-            if above is not None and not keep:
-                _L.check(lib.tpe_rows_scatter(dense.data_ptr(), rows.data_ptr(), count.data_ptr(),
-                                              p0, min(win, P - p0), above[g].data_ptr(),
-                                              above.shape[1], sp), "tpe_rows_scatter")
-            if parts is not None:  # (the same call as the one added to S: the same bits)
-                score(0, p0, dense.data_ptr(), parts[g].data_ptr(), _L.JOINT_OUT_SCATTER)
-            score(0, p0, dense.data_ptr(), out.data_ptr(), both)
+                                      cscratch.data_ptr(), f.sp), "tpe_rows_compact")
+        _score_fit(f, d_vals, ld, n_cols, P, out, listed=(rows, count),
+                   above_to=None if above is None else above[g],
+                   ctx_to=None if above_ctx is None else above_ctx[g],
+                   j_to=None if parts is None else parts[g])
 
 
 # -- a grid pool: factor tables per axis (DESIGN 3.5.7) ---------------------------

@@ -58,7 +58,7 @@ one per group of labels that share an activation condition (joint.py
 "Groups"; csrc/tpe_joint_tree.hip), so the candidates themselves follow an
 interaction between labels.  ``joint="chain"`` (not on a ``GridPool``; its
 batch is ``batch="liar-chain"``) conditions each of those groups on the labels
-live around it (joint.py "Chains"; csrc/tpe_joint_chain.hip), so a root label
+live around it (joint.py "Chains"; csrc/tpe_joint.hip), so a root label
 interacts with a branch label; its sampled pools draw the rows of ``"tree"``.
 
 ``batch="liar"`` (``suggest_from_pool``, ``suggest_sampled``, ``pick_batch``;
@@ -631,23 +631,11 @@ def _sample(domain, trials, seed, n_rows, st, keep_terms, hist=None):
             n_active = _rows_active(eng, domain, labels, d, P, sp)
         # S starts from J of the drawn rows; the fold below adds the other labels
         # (with the groups every label is joint: S is theirs, and nothing is folded)
-        if st.lie_chain:  # (the fits' log L_above and log L_ctx,above stay)
-            d.fits, d.above, d.above_ctx = fits, _above(eng, fits, P), _above(eng, fits, P)
-            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above,
-                                 above_ctx=d.above_ctx)
-        elif st.lie_tree:  # (the groups' log L_above stays)
-            d.fits, d.above = fits, _above(eng, fits, P)
-            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S, above=d.above)
-        elif joint["tree"]:
-            if st.refine_tree:  # (the fits stay, for the climb)
-                d.fits = fits
-            _J.score_tree_device(fits, d.vals, d.active, P, L, P, d.S)
-        else:
-            if st.lie is not None:  # (log L_above of the born rows stays, for the batch)
-                d.fits, d.parts = fits, _parts(eng, domain, st, P)
-            elif st.refine:  # (the fit stays, for the climb)
-                d.fits = fits
-            _J.score_device(fits[0], d.vals, P, L, P, d.S, d.parts)
+        if st.lie is not None or st.refine or st.refine_tree:
+            d.fits = fits  # (the fit stays, for the batch or the climb)
+        if st.lie is not None and not joint["tree"]:
+            d.parts = _parts(eng, domain, st, P)  # (log L_above of the born rows stays)
+        _joint_score(eng, d, st, fits, P, L, P)
         init = 0
         if keep_terms:  # the joint labels have no term of their own
             for j in jcols:
@@ -1209,21 +1197,27 @@ def _joint_device(eng, domain, pool, d, st, hist):
     L_ctx,above in ``d.above_ctx``."""
     P, L, ld = len(pool), len(pool.labels), d.vals.shape[1]
     d.fits = _fit(eng, domain, hist, L, st)
-    if st.lie_chain:
-        d.above, d.above_ctx = _above(eng, d.fits, P), _above(eng, d.fits, P)
-        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts, above=d.above,
-                             above_ctx=d.above_ctx)
-        return
-    if st.lie_tree:
-        d.above = _above(eng, d.fits, P)
-        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts, above=d.above)
-        return
-    if st.joint["tree"]:
-        _J.score_tree_device(d.fits, d.vals, d.active, ld, L, P, d.S, d.parts)
-        return
-    _J.score_device(d.fits[0], d.vals, ld, L, P, d.S, d.parts)
-    if d.parts is not None:  # (row 2: J itself, before the fold adds to S)
+    _joint_score(eng, d, st, d.fits, ld, L, P)
+    if d.parts is not None and not st.joint["tree"]:  # (row 2: J itself, before the fold adds to S)
         d.parts[2, :P].copy_(d.S[:P])
+
+
+def _joint_score(eng, d, st, fits, ld, n_cols, P):
+    """J of rows [0, P) of the mirror ``d`` under ``fits`` into ``d.S``, by one
+    scoring call: ``joint.score_device`` (flat), or with the groups
+    ``joint.score_tree_device``.  The parts go into ``d.parts`` where that is a
+    tensor; what the settings' batch needs stays on the mirror: the groups' log
+    L_above in ``d.above`` (``lie_tree``, ``lie_chain``) and their log
+    L_ctx,above in ``d.above_ctx`` (``lie_chain``), both ``_above`` tensors."""
+    if st.lie_tree or st.lie_chain:
+        d.above = _above(eng, fits, P)
+    if st.lie_chain:
+        d.above_ctx = _above(eng, fits, P)
+    if st.joint["tree"]:
+        _J.score_tree_device(fits, d.vals, d.active, ld, n_cols, P, d.S, d.parts, above=d.above,
+                             above_ctx=d.above_ctx)
+    else:
+        _J.score_device(fits[0], d.vals, ld, n_cols, P, d.S, d.parts)
 
 
 def _score_device(domain, trials, pool, st, want_terms, hist=None, want_parts=False):

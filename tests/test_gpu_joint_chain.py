@@ -1,6 +1,6 @@
 """``joint="chain"`` on the GPU, through the public functions: every group of
 labels conditioned on its context by the chain rule (hyperopt_amd/joint.py
-"Chains", csrc/tpe_joint_chain.hip).
+"Chains", csrc/tpe_joint.hip).
 
 Values are checked against the scalar restatement of tests/joint_chain_util.py:
 |got - ref| <= 1e-6 * sum over the row's live groups of (|log L_below| + |log

@@ -1,4 +1,4 @@
-"""tpe_joint_chain_rows through the C ABI (csrc/tpe_joint_chain.hip): one walk
+"""tpe_joint_chain_rows through the C ABI (csrc/tpe_joint.hip): one walk
 that gives log L - log L_ctx, against the two-call form -- tpe_joint_score_rows
 on the same prepared set, minus tpe_joint_score_rows with n_labels = n_ctx on a
 set that tpe_joint_prep builds from the first n_ctx labels with the head's

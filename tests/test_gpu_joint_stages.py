@@ -1,5 +1,5 @@
 """The joint Parzen kernels stage by stage (csrc/tpe_joint.hip: k_joint_prep,
-k_joint_score, k_joint_merge), through tpe_joint_prep / tpe_joint_score on
+k_joint_rows, k_joint_rows_merge), through tpe_joint_prep / tpe_joint_score on
 torch tensors, against the 50-digit values of tests/golden/joint_cases.npz.
 
 Every value is held to |got - ref| <= K_DEV * 2**-53 * cond, cond the fixture's
